@@ -7,6 +7,9 @@ Workloads (BASELINE.json configs; synthetic KITTI-shaped inputs, seed 1234 + ran
               stack, forward + backward + Adam  (configs[2]; the configuration the metric is quoted on)
   loss_stack  the loss stack alone on synthetic net outputs, forward + backward (hot path in isolation)
 Unit: frame pair = one (target, source) direction of one triplet; a batch of B triplets is 2B pairs.
+A plain run sets up, warms up, times the steps and prints the line.  --full adds what the headline does not need: the fused
+loss stack's kernel times inside the timed region and the roofline object priced from them, the CPU baseline (N=1) and the
+multi-GPU evidence block (N>1 or --force-ddp).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import ctypes
@@ -16,6 +19,7 @@ import json
 import os
 import sys
 import time
+import types
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -53,7 +57,14 @@ def parse():
                     "(train_step.GraphedTrainStep; single process).  The roofline kernel is then timed in eager steps AFTER the timed region")
     ap.add_argument("--net-streams", type=int, default=None, help="1 = the three networks one after the other on one stream; 3 = flow / pose "
                     "nets on side streams (default: the package default)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the figures beyond the headline: the loss stack's in-step kernel times + "
+                    "roofline object, the CPU baseline (N=1, unless --no-cpu-baseline) and the multi-GPU evidence block (N>1 or --force-ddp)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "as DIR/<name>.npy (float32, at most 64 MB in all: see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def visible_devices():
@@ -173,7 +184,24 @@ class LossStackWorkload:
                              self.pose, self.fb, self.ff, self.K, self.Ki, num_scales=self.S)
         loss = sum(self.weights[k] * v.mean() for k, v in lp.items())
         loss.backward()
-        return loss
+        return loss, lp
+
+    def keep_initial_state(self):
+        """Nothing to keep: every step starts from the same seeded inputs (their gradients are reset each step)."""
+
+    def rewind(self):
+        """See keep_initial_state."""
+
+    def outputs(self, res):
+        """What a caller of the loss stack receives from one step: the weighted total, every loss term and the gradient of
+        every input that takes one."""
+        loss, lp = res
+        out = {"loss": loss}
+        out.update((k, v) for k, v in lp.items())
+        leaves = [("disp_%s_s%d" % (f, s), t) for f, lst in zip("ltr", self.disps) for s, t in enumerate(lst)] + [("pose", self.pose)]
+        leaves += [("flow_bwd_s%d" % s, t) for s, t in enumerate(self.fb)] + [("flow_fwd_s%d" % s, t) for s, t in enumerate(self.ff)]
+        out.update(("grad_" + k, t.grad) for k, t in leaves if t.grad is not None)
+        return out
 
     def cpu_step_fn(self, threads):
         """The oracle (CPU restatement of the reference) on the same inputs: forward + backward."""
@@ -246,8 +274,44 @@ class TrainStepWorkload:
         if self.use_graph and not eager:
             if self.graphed is None:
                 self.graphed = GraphedTrainStep(self.model, self.opt, self.inputs, self.cfg)
-            return self.graphed()[0]
-        return train_step(self.model, self.opt, self.inputs, self.cfg)[0]
+            return self.graphed()
+        return train_step(self.model, self.opt, self.inputs, self.cfg)
+
+    def _state(self):
+        from unsupervised_depth_opticalflow_egomotion_amd import ddp
+        return types.SimpleNamespace(model=ddp.unwrap(self.model), optimizer=self.opt)
+
+    def keep_initial_state(self):
+        """Snapshot of the seeded initial state before the first step: parameters, buffers and the optimiser's (still
+        empty) state -- GraphedTrainStep's own snapshot, which it uses to undo its warm-up steps."""
+        from unsupervised_depth_opticalflow_egomotion_amd.train_step import GraphedTrainStep
+        self.initial_state = GraphedTrainStep._snapshot(self._state())
+
+    def rewind(self):
+        """Put that snapshot back IN PLACE (a captured step replays on the same addresses; Adam's moments and counts back to
+        zero; the cached Winograd filters refreshed), so that the next step starts from the seeded initial state.  Each
+        training step moves the weights, and MIOpen's split-K weight gradients add in a varying order, so after a few steps
+        two runs are no longer on the same weights; a step that starts from here computes the same thing in every run."""
+        from unsupervised_depth_opticalflow_egomotion_amd.train_step import GraphedTrainStep
+        GraphedTrainStep._restore(self._state(), self.initial_state)
+
+    # mask-pack entries that the step does not compute: reading them runs operators of their own (the epipolar map and its
+    # top-ratio selection, an inverse warp), which turn rounding-level differences of their inputs into flipped pixels
+    COMPUTED_ON_READ = ("rigid_fwd_mask", "inlier_fwd_mask", "valid_fwd_mask")
+
+    def outputs(self, res):
+        """What the train step computed: the total loss, the loss pack (every term; a disabled one is its (2,) zeros), the
+        mask pack entries it produced and the gradients its backward left, flattened in model.parameters() order.  The
+        gradients stand for the update: the dumped step is Adam's first (rewind), ~ lr * sign(g), so an element whose
+        gradient is within rounding of zero moves by +-lr depending on the order MIOpen's split-K weight gradients add in,
+        while the gradient itself repeats to rounding and fixes the update element by element."""
+        from unsupervised_depth_opticalflow_egomotion_amd import ddp
+        loss, loss_pack, mask_pack = res
+        out = {"loss": loss}
+        out.update(loss_pack.items())
+        out.update((k, mask_pack[k]) for k in mask_pack.keys() if k not in self.COMPUTED_ON_READ)
+        out["grads"] = torch.cat([p.grad.reshape(-1) for p in ddp.unwrap(self.model).parameters() if p.grad is not None])
+        return out
 
     def cpu_step_fn(self, threads):
         """CPU baseline: the same networks on the host + the oracle's loss stack + Adam."""
@@ -436,6 +500,36 @@ def multi_gpu_evidence(wl, world, rank, dev, dt_local, args):
     return ev
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000     # the dump may take 64 MB: room left for the directory and file-system rounding
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write name -> tensor / array as out_dir/<name>.npy in float32, so that two builds run with the same arguments (and
+    so the same seeded inputs) can be compared output for output.  The arrays are written whole when they fit in `limit`
+    bytes together; otherwise every array larger than a common cap (the largest that makes them fit) is replaced by a
+    fixed, seeded sample of `cap` of its flattened elements, in index order: the same elements on every run."""
+    import zlib
+    arrays = {}
+    for k, v in outputs.items():
+        if torch.is_tensor(v):
+            v = v.detach().float().cpu().numpy()
+        arrays[k] = np.asarray(v, dtype=np.float32)
+    left = (limit - 256 * len(arrays)) // 4            # elements; 256 bytes per file cover the .npy header
+    sizes = sorted(a.size for a in arrays.values())
+    cap = None
+    for i, n in enumerate(sizes):
+        if n > left // (len(sizes) - i):
+            cap = left // (len(sizes) - i)
+            break
+        left -= n
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        if cap is not None and a.size > cap:
+            pick = np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, size=cap, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     args = parse()
     launch_ranks_if_needed(args)
@@ -452,17 +546,24 @@ def main():
         wl = TrainStepWorkload(args, dev, seed=1234 + rank, world=world)
     else:
         wl = LossStackWorkload(args, dev, seed=1234 + rank)
+    if args.dump_outputs:
+        wl.keep_initial_state()
     for _ in range(args.warmup):
         wl.step()
     from unsupervised_depth_opticalflow_egomotion_amd import loss_stack as LS
     barrier(world)
-    LS.timing_begin()           # HIP events between the fused stack's launches (stream-ordered, no host sync)
+    if args.full:
+        LS.timing_begin()       # HIP events between the fused stack's launches (stream-ordered, no host sync)
     # stream-ordered marks (no host sync): the whole region, and its first 20 steps (what rounds 1-4 timed) for comparison
     ev_beg, ev_20, ev_end = (torch.cuda.Event(enable_timing=True) for _ in range(3))
     t0 = time.perf_counter()
     ev_beg.record()
     for i in range(args.steps):
-        wl.step()
+        if args.dump_outputs and i == args.steps - 1:
+            wl.rewind()         # the dumped step starts from the seeded initial state: its outputs depend on the arguments only
+        last = wl.step()
+        if i < args.steps - 1:
+            last = None         # a step's outputs are not held while the next one runs
         if i == 19:
             ev_20.record()
     ev_end.record()
@@ -470,15 +571,19 @@ def main():
     barrier(world)
     dt_local = time.perf_counter() - t0
     dt = max_over_ranks(dt_local, world, dev)
-    graph_mode = bool(getattr(wl, "use_graph", False))
-    if graph_mode:      # events recorded inside a captured graph cannot be read back: time the roofline kernel in eager steps, after the region
-        LS.timing_collect()
-        LS.timing_begin()
-        for _ in range(5):
-            wl.step(eager=True)
-        torch.cuda.synchronize()
-    fwd_ms, bwd_ms = LS.timing_collect()
-    evidence = multi_gpu_evidence(wl, world, rank, dev, dt_local, args) if (world > 1 or args.force_ddp) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(last), args.dump_outputs)
+    evidence = None
+    if args.full:
+        if getattr(wl, "use_graph", False):   # events recorded inside a captured graph cannot be read back: time the roofline kernel in eager steps, after the region
+            LS.timing_collect()
+            LS.timing_begin()
+            for _ in range(5):
+                wl.step(eager=True)
+            torch.cuda.synchronize()
+        fwd_ms, bwd_ms = LS.timing_collect()
+        if world > 1 or args.force_ddp:
+            evidence = multi_gpu_evidence(wl, world, rank, dev, dt_local, args)
     pairs_per_step = 2 * args.batch * world
     value = pairs_per_step * args.steps / dt
     out = {
@@ -510,11 +615,12 @@ def main():
         sys.stdout.flush()
         dist.barrier()
     if rank == 0:
-        roof, segs = point_fwd_roofline(args, args.mode if wl.name == "train_step" else "geom", fwd_ms, bwd_ms)
-        out["roofline"] = roof
-        out["kernel_ms"] = segs
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(wl, args, 2 * args.batch)
+        if args.full:
+            roof, segs = point_fwd_roofline(args, args.mode if wl.name == "train_step" else "geom", fwd_ms, bwd_ms)
+            out["roofline"] = roof
+            out["kernel_ms"] = segs
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(wl, args, 2 * args.batch)
         # keep the JSON line the LAST line of stdout: RCCL prints a "Librccl path" banner through C stdio when the communicator
         # is made, which a pipe buffers until exit -- flush it out before the line
         try:

@@ -1061,6 +1061,35 @@ def test_occupancy_critical_kernels_keep_their_resources():
     assert len(ssim_bwd) == 1 and ssim_bwd[0]["vgpr"] <= 96 and ssim_bwd[0]["scratch"] == 0, ssim_bwd
 
 
+def test_bench_dump_outputs_float32_whole_or_a_fixed_sample(tmp_path):
+    """bench.dump_outputs (bench.py --dump-outputs): every output as <name>.npy in float32; when they do not fit in the limit
+    together, the small ones stay whole and the largest are cut to one common number of elements, the same seeded sample on
+    every call, in index order."""
+    import bench
+    r = np.random.default_rng(0)
+    outs = {"loss": torch.tensor(1.5, dtype=torch.float64), "mask": r.integers(0, 2, (64, 80)).astype(np.uint8),
+            "big": torch.from_numpy(r.standard_normal(300_000)), "bigger": r.standard_normal((2, 400_000))}
+    bench.dump_outputs(outs, str(tmp_path / "whole"))
+    for k, v in outs.items():
+        got = np.load(str(tmp_path / "whole" / (k + ".npy")))
+        assert got.dtype == np.float32 and got.shape == tuple(np.shape(v))
+        np.testing.assert_array_equal(got, np.asarray(v, dtype=np.float32))
+    limit = 1_000_000
+    for sub in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / sub), limit=limit)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == sorted(k + ".npy" for k in outs)
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= limit
+    for f in files:
+        np.testing.assert_array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f)))
+    assert np.load(str(tmp_path / "a" / "mask.npy")).shape == (64, 80)
+    big, bigger = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "a" / "bigger.npy"))
+    assert big.ndim == 1 and big.shape == bigger.shape and 100_000 < big.size < 300_000
+    src = np.asarray(outs["big"], dtype=np.float32)
+    pos = np.array([np.flatnonzero(src == x)[0] for x in big[:200]])
+    assert (np.diff(pos) > 0).all()
+
+
 def test_hw_queue_limit_is_raised_only_when_it_can_take_effect(monkeypatch):
     """The package raises GPU_MAX_HW_QUEUES to 8 at import (three network streams + a process group's streams need more than the
     runtime's 4 queues); a value the user exported wins, and models._side_streams only drops the high stream priorities under a

@@ -671,7 +671,7 @@ def test_bench_two_ranks_on_one_gpu(mode):
     env = dict(os.environ, DFE_BENCH_ALL_ON_DEVICE0="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--backend", "gloo", "--mode", mode, "--batch", "2"]
+           "--warmup", "1", "--backend", "gloo", "--mode", mode, "--batch", "2", "--full"]
     j = _bench_json(subprocess.run(cmd, capture_output=True, text=True, cwd=repo, env=env, timeout=900))
     assert j["n_gpus"] == 2 and j["steps"] == 2 and j["scaling"] == "weak" and j["config"]["global_batch"] == 4
     assert j["value"] > 0 and "roofline" in j and "cpu_baseline" not in j   # CPU baseline only at N=1
@@ -788,7 +788,7 @@ def test_bench_force_ddp_prints_the_multi_gpu_block_on_one_gpu():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     clean = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     j = _bench_json(subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--force-ddp", "--steps", "2", "--warmup", "1",
-                                    "--batch", "2", "--no-cpu-baseline"], capture_output=True, text=True, cwd=repo, env=clean, timeout=900))
+                                    "--batch", "2", "--no-cpu-baseline", "--full"], capture_output=True, text=True, cwd=repo, env=clean, timeout=900))
     mg = j["multi_gpu"]
     assert j["n_gpus"] == 1 and mg["data_parallel"] == "FlatAllReduce" and mg["backend"] == "nccl" and mg["collective_library"] == "RCCL"
     assert mg["ranks"] == 1 and mg["rank_id_allreduce_ok"] is True and mg["param_checksums_equal"] is True
@@ -803,7 +803,7 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = [sys.executable, os.path.join(repo, "bench.py"), "--steps", "2", "--warmup", "1", "--mode", "depth", "--batch", "2"]
     clean = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    j = _bench_json(subprocess.run(base + ["--gpus", "2", "--backend", "gloo"], capture_output=True, text=True, cwd=repo,
+    j = _bench_json(subprocess.run(base + ["--gpus", "2", "--backend", "gloo", "--full"], capture_output=True, text=True, cwd=repo,
                                    env=dict(clean, DFE_BENCH_ALL_ON_DEVICE0="1"), timeout=900))
     assert j["n_gpus"] == 2 and j["config"]["parallelism"] == "dp2"
     assert j["multi_gpu"]["ranks"] == 2 and j["multi_gpu"]["param_checksums_equal"] is True
@@ -817,6 +817,41 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     out = subprocess.run(base + ["--gpus", "2"], capture_output=True, text=True, cwd=repo,
                          env=dict(clean, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0"), timeout=300)
     assert out.returncode != 0 and "contradicts" in out.stderr
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` line holds the headline only (the kernel times, roofline, CPU baseline and multi-GPU block
+    are --full's), and --dump-outputs writes what the last timed step computed: the loss, every loss term, the mask pack
+    and a sample of the gradients, float32, within 64 MB -- the loss being the weighted sum of the dumped terms -- and two
+    runs with the same arguments write the same outputs to rounding (the dumped step starts from the seeded state)."""
+    import subprocess, sys
+    from unsupervised_depth_opticalflow_egomotion_amd.train_step import DEFAULT_CFG, LOSS_WEIGHT_ATTR
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    clean = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    runs = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        j = _bench_json(subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                                        "--dump-outputs", d], capture_output=True, text=True, cwd=repo, env=clean, timeout=900))
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "f32"
+        assert not {"roofline", "kernel_ms", "cpu_baseline", "multi_gpu"} & set(j)
+        files = os.listdir(d)
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64e6
+        runs.append({f[:-4]: np.load(os.path.join(d, f)) for f in files})
+    a, b = runs
+    assert {"loss", "grads", "loss_depth_pixel", "loss_flow_pixel", "fwd_mask", "pred_depth_img", "pred_flow_img"} <= set(a)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["loss_depth_pixel"].shape == (4,) and a["pred_depth_img"].shape == (1, 256, 832) and a["grads"].ndim == 1
+    total = sum(DEFAULT_CFG[w] * float(a[k].astype(np.float64).mean()) for k, w in LOSS_WEIGHT_ATTR.items())
+    assert abs(float(a["loss"]) - total) <= 1e-5 * abs(total)
+    # measured: losses <= 3e-5 of their scale (the epipolar term's top-ratio selection), gradients and predictions <= 3e-6,
+    # the fused stack's masks bit for bit; before the rewind, 25 steps apart drifted to 2e-3 and flipped 0.25 % of a mask
+    assert set(a) == set(b)
+    for k in a:
+        if k.endswith("mask"):
+            assert np.count_nonzero(a[k] != b[k]) <= 1e-4 * a[k].size, k
+        else:
+            assert np.abs(a[k].astype(np.float64) - b[k]).max() <= 1e-4 * max(np.abs(a[k]).max(), 1e-30), k
 
 
 def test_test_py_cli_surface(tmp_path):

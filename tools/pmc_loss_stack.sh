@@ -7,7 +7,7 @@ B=${2:-4}; H=${3:-256}; W=${4:-832}; S=${5:-3}
 SHAPE="--batch $B --height $H --width $W --scales $S"
 R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out; mkdir -p $OUT
-CMD="python3 $R/bench.py --workload loss_stack $SHAPE --steps 30 --warmup 5 --no-cpu-baseline"
+CMD="python3 $R/bench.py --workload loss_stack $SHAPE --steps 30 --warmup 5 --no-cpu-baseline --full"
 rm -rf /tmp/ks; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o t -- $CMD > /tmp/ks.log 2>&1
 cp /tmp/ks/t_kernel_stats.csv $OUT/${TAG}_loss_stack_kernel_stats.csv
 grep '^{"metric"' /tmp/ks.log > $OUT/${TAG}_loss_stack_bench_line.json

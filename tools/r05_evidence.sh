@@ -10,9 +10,9 @@ fi
 bash tools/pmc_loss_stack.sh r05 > /dev/null 2>&1
 cp $out/r05_pmc_point_fwd_traffic.json profiles/pmc_point_fwd_traffic.json 2>/dev/null
 # the default bench line (with the CPU baseline), twice more without it, the forced-DDP line
-timeout 900 python bench.py > $out/r05_bench_default.log 2>&1; grep '^{"metric"' $out/r05_bench_default.log > $out/r05_bench_line.json; cut -c1-260 $out/r05_bench_line.json
+timeout 900 python bench.py --full > $out/r05_bench_default.log 2>&1; grep '^{"metric"' $out/r05_bench_default.log > $out/r05_bench_line.json; cut -c1-260 $out/r05_bench_line.json
 for i in 1 2; do timeout 600 python bench.py --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | cut -c1-200; done
-timeout 600 python bench.py --force-ddp --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $out/r05_bench_force_ddp_line.json; cut -c1-200 $out/r05_bench_force_ddp_line.json
+timeout 600 python bench.py --force-ddp --no-cpu-baseline --full 2>/dev/null | grep '^{"metric"' > $out/r05_bench_force_ddp_line.json; cut -c1-200 $out/r05_bench_force_ddp_line.json
 for m in depth flow; do timeout 600 python bench.py --mode $m --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | cut -c1-200; done
 for b in 1 2; do timeout 600 python bench.py --batch $b --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('B=$b host floor: ms_per_step', d['ms_per_step'], 'host_enqueue_ms', d['host_enqueue_ms'])"; done
 python tools/instep_roofline.py $out/r05_bench_line.json > $out/r05_instep_roofline.md

@@ -11,10 +11,10 @@ bash tools/pmc_loss_stack.sh r06 > /dev/null 2>&1
 cp $out/r06_pmc_point_fwd_traffic.json profiles/pmc_point_fwd_traffic.json 2>/dev/null
 bash tools/pmc_loss_stack.sh r06_config5_b2 2 375 1242 6 > /dev/null 2>&1
 bash tools/pmc_loss_stack.sh r06_config5_b16 16 375 1242 6 > /dev/null 2>&1
-timeout 900 python bench.py > $out/r06_bench_default.log 2>&1; grep '^{"metric"' $out/r06_bench_default.log > $out/r06_bench_line.json; cut -c1-260 $out/r06_bench_line.json
+timeout 900 python bench.py --full > $out/r06_bench_default.log 2>&1; grep '^{"metric"' $out/r06_bench_default.log > $out/r06_bench_line.json; cut -c1-260 $out/r06_bench_line.json
 timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{"metric"' > $out/r06_bench_driver_cmd_line.json; cut -c1-200 $out/r06_bench_driver_cmd_line.json
 for i in 1 2; do timeout 600 python bench.py --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | cut -c1-200; done
-timeout 600 python bench.py --force-ddp --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $out/r06_bench_force_ddp_line.json; cut -c1-200 $out/r06_bench_force_ddp_line.json
+timeout 600 python bench.py --force-ddp --no-cpu-baseline --full 2>/dev/null | grep '^{"metric"' > $out/r06_bench_force_ddp_line.json; cut -c1-200 $out/r06_bench_force_ddp_line.json
 for m in depth flow; do timeout 600 python bench.py --mode $m --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | cut -c1-200; done
 { for b in 1 2 4; do for g in "" "--graph"; do timeout 600 python bench.py --batch $b $g --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('B=$b ${g:-eager}: ms_per_step', d['ms_per_step'], 'host_enqueue_ms', d['host_enqueue_ms'])"; done; done; } > $out/r06_graph_mode.txt 2>&1; cat $out/r06_graph_mode.txt
 python tools/instep_roofline.py $out/r06_bench_line.json > $out/r06_instep_roofline.md
