@@ -126,6 +126,31 @@ int dfe_dynamic_mask(const float* flow, const float* rigid, float* mask, float* 
 int dfe_prepare_triplets(const unsigned char* in_u8, const unsigned char* flip, float* out, int B, int H0, int W0,
                          int H, int W, void* stream);
 
+/* ---- the same image half in the reference's own 8-bit arithmetic  core/dataset/kitti_prepared.py:63-90,132-152 -----
+ * cv2.imread (BGR) -> per frame cv2.resize(frame, (W, H)) (INTER_LINEAR on uint8) -> cv2.flip(img, 1) -> / 255.0, for a
+ * batch whose samples each have their own raw size.  OpenCV 4.1.1 modules/imgproc/src/resize.cpp, restated: cv::resize
+ * (same size: copy), cv::hal::resize (exact 1/2 on both axes: INTER_AREA), resizeGeneric_ with HResizeLinear (11-bit
+ * fixed-point coefficients saturate_cast<short>((1 - fx) * 2048), saturate_cast<short>(fx * 2048)), VResizeLinear with
+ * FixedPtCast<int, uchar, 22> (scalar rule) and VResizeLinearVec_32s8u (vector rule), resizeAreaFast_.  The host
+ * (ops.prepare_triplets_u8) builds the per-size tables; this entry point is integer-only up to the final table lookup.
+ *   in_u8 : sample b is uint8 [3*h0][w0][3] (frames stacked along H) at byte desc[b].offset
+ *   desc  : B descriptors (below); flip = cv2.flip(img, 1) of the resized strip
+ *   xtab  : int pairs (x0, a0 | a1 << 16), W per size, sample b's at pair index desc[b].xtab
+ *   ytab  : int quads (y0, y1, b0 | b1 << 16, 0), H per size (rows already clamped), at quad index desc[b].ytab
+ *   lut   : 256 floats, lut[u] = float32(u / 255.0) computed in double
+ *   out   : fp32 [B][3][3*H][W] (channels B, G, R)
+ *   nvec  : bytes of each resized row (3*W of them) that take the vector rule; the rest take the scalar rule
+ *   rgb   : non-zero when in_u8 holds R, G, B (a PIL decode): written in cv2.imread's B, G, R order
+ * All pointers are device pointers. */
+typedef struct {
+  long long offset;   /* byte offset of the sample's strip in in_u8 */
+  int h0, w0;         /* frame size: the strip is 3*h0 rows of w0 pixels */
+  int xtab, ytab;     /* first pair / quad of this size's tables */
+  int flip, pad;
+} dfe_u8_desc;
+int dfe_prepare_triplets_u8(const unsigned char* in_u8, const dfe_u8_desc* desc, const int* xtab, const int* ytab,
+                            const float* lut, float* out, int B, int H, int W, int nvec, int rgb, void* stream);
+
 /* ---- forward-splat occlusion map  core/networks/model_flow.py:33-39 (get_occlusion_mask_from_flow) -----------
  * The reference calls an undefined `transformerFwd`; this is its TrianFlow meaning: out [B,1,H,W] = bilinear forward
  * warp of a ones image by flow [B,2,H,W] (optionally clamped to [0,1]).  Order-independent scatter through ws

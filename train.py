@@ -6,8 +6,10 @@
 
 Differences from the reference, all forced by what it cannot do: data parallelism is one process per GPU
 with one process per GPU over RCCL (ddp.wrap: one flat gradient all-reduce per step) instead of nn.DataParallel (``--multi_gpu`` is accepted and ignored; launch with
-torchrun); the data source is the synthetic KITTI-shaped triplet generator (no KITTI on this machine);
-periodic KITTI evaluation (train.py:136-164) needs the datasets and is skipped (``--no_test`` semantics).
+torchrun); the data source is the synthetic KITTI-shaped triplet generator by default (``data_source: synthetic``), or the
+reference's prepared KITTI tree with ``--data_source prepared --prepared_base_dir DIR`` (train.txt, stacked-triplet PNGs and
+calib files as KITTI_RAW.prepare_data_mp writes them; read by prepared_data.PreparedFeeder on ``--num_workers`` decode threads
+with the image half on the device); periodic KITTI evaluation (train.py:136-164) needs the datasets and is skipped (``--no_test`` semantics).
 Checkpoints keep the reference format: {iteration, model_state_dict, optimizer_state_dict} in
 iter_{N}.pth and last.pth (train.py:21-29)."""
 import argparse
@@ -19,7 +21,7 @@ import time
 import torch
 import yaml
 
-from unsupervised_depth_opticalflow_egomotion_amd import ddp, ops, synthetic
+from unsupervised_depth_opticalflow_egomotion_amd import ddp, ops, prepared_data, synthetic
 from unsupervised_depth_opticalflow_egomotion_amd.models import get_model
 from unsupervised_depth_opticalflow_egomotion_amd.train_step import train_step, make_optimizer, GraphedTrainStep, LOSS_WEIGHT_ATTR
 
@@ -80,7 +82,16 @@ def train(cfg):
     h, w = cfg.img_hw
     n_iter = cfg.num_iterations - start
     raw_pipeline = bool(getattr(cfg, "device_pipeline", False))
-    if raw_pipeline:   # raw uint8 triplets at KITTI's native size; resize / flip / normalise run on the device
+    feeder = None
+    if getattr(cfg, "data_source", "synthetic") == "prepared":     # the reference's prepared tree (train.py:100-125)
+        if not getattr(cfg, "prepared_base_dir", None):
+            raise ValueError("data_source 'prepared' needs prepared_base_dir (--prepared_base_dir or the YAML key)")
+        source = prepared_data.PreparedKITTI(cfg.prepared_base_dir, cfg.num_scales, (h, w))
+        feeder = prepared_data.PreparedFeeder(source, cfg.batch_size, (h, w), dev, n_iter, num_workers=cfg.num_workers,
+                                              world=world, rank=rank)
+        if rank == 0:
+            print("A total of {} image pairs found".format(source.count()), flush=True)
+    elif raw_pipeline:   # raw uint8 triplets at KITTI's native size; resize / flip / normalise run on the device
         dataset = synthetic.SyntheticRawTriplets(n_iter * cfg.batch_size * world, (375, 1242), (h, w), cfg.num_scales, seed=1234)
     else:
         dataset = synthetic.SyntheticTriplets(n_iter * cfg.batch_size * world, (h, w), cfg.num_scales, seed=1234)
@@ -91,15 +102,18 @@ def train(cfg):
         prof = profiling.Profiler(silent=rank != 0)
     t0 = time.time()
     for it in range(start, cfg.num_iterations):
-        base = (it - start) * cfg.batch_size * world + rank * cfg.batch_size
-        samples = [dataset[base + j] for j in range(cfg.batch_size)]
-        if raw_pipeline:
-            raw = torch.stack([s[0] for s in samples]).pin_memory().to(dev, non_blocking=True)
-            flip = torch.tensor([s[3] for s in samples], dtype=torch.uint8)
-            inputs = [ops.prepare_triplets(raw, (h, w), flip)] + \
-                [torch.stack([s[i] for s in samples]).to(dev, non_blocking=True) for i in (1, 2)]
+        if feeder is not None:
+            inputs = next(feeder)      # batch it - start of the per-rank shard: idx = (it - start) * B * world + rank * B + j
         else:
-            inputs = [torch.stack([s[i] for s in samples]).to(dev, non_blocking=True) for i in range(3)]
+            base = (it - start) * cfg.batch_size * world + rank * cfg.batch_size
+            samples = [dataset[base + j] for j in range(cfg.batch_size)]
+            if raw_pipeline:
+                raw = torch.stack([s[0] for s in samples]).pin_memory().to(dev, non_blocking=True)
+                flip = torch.tensor([s[3] for s in samples], dtype=torch.uint8)
+                inputs = [ops.prepare_triplets(raw, (h, w), flip)] + \
+                    [torch.stack([s[i] for s in samples]).to(dev, non_blocking=True) for i in (1, 2)]
+            else:
+                inputs = [torch.stack([s[i] for s in samples]).to(dev, non_blocking=True) for i in range(3)]
         if prof is not None:
             prof.reset()
         if use_graph:      # one hipGraph launch per iteration (train_step.GraphedTrainStep): captured on the first batch
@@ -113,6 +127,8 @@ def train(cfg):
         if rank == 0 and (it + 1) % cfg.save_interval == 0:
             save_model(it + 1, cfg.model_dir, "iter_{}.pth".format(it + 1), model, optimizer)
             save_model(it + 1, cfg.model_dir, "last.pth", model, optimizer)
+    if feeder is not None:
+        feeder.close()
     if rank == 0:
         print("done: %d iterations in %.1f s" % (cfg.num_iterations - start, time.time() - t0))
     if world > 1:
@@ -134,6 +150,10 @@ if __name__ == "__main__":
     ap.add_argument("--mode", type=str, default="geom", help="flow | depth | geom")
     ap.add_argument("--model_dir", type=str, default=None)
     ap.add_argument("--prepared_save_dir", type=str, default="data_s1")
+    ap.add_argument("--data_source", type=str, default=None, choices=("synthetic", "prepared"),
+                    help="synthetic triplets (the YAML's default) or the reference's prepared KITTI tree under --prepared_base_dir")
+    ap.add_argument("--prepared_base_dir", type=str, default=None,
+                    help="directory holding train.txt, the stacked-triplet PNGs and calib files (KITTI_RAW.prepare_data_mp's output)")
     ap.add_argument("--flow_pretrained_model", type=str, default=None)
     ap.add_argument("--depth_pretrained_model", type=str, default=None)
     ap.add_argument("--resume", action="store_true")
@@ -158,7 +178,7 @@ if __name__ == "__main__":
     cfg["img_hw"] = (cfg["img_hw"][0], cfg["img_hw"][1])
     cfg["model_dir"] = os.path.join(args.model_dir or "./models", args.mode)
     for k, v in vars(args).items():        # every CLI attribute overrides / extends the YAML (train.py:272-274)
-        if k in ("model_dir",) or (k == "num_iterations" and v is None):
+        if k in ("model_dir",) or (k in ("num_iterations", "data_source", "prepared_base_dir") and v is None):
             continue
         cfg[k] = v
     os.makedirs(cfg["model_dir"], exist_ok=True)

@@ -8,11 +8,12 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 
 import torch
 
 from . import _lib, convs
-from ._lib import check, f32c, get_lib, ptr, stream_ptr
+from ._lib import DfeError, check, f32c, get_lib, ptr, stream_ptr
 
 _ALIGN_CORNERS = False
 
@@ -400,6 +401,159 @@ def prepare_triplets(raw_u8, img_hw, flip=None):
     out = torch.empty(B, 3, 3 * H, W, device=raw_u8.device)
     check(lib.dfe_prepare_triplets(ptr(raw_u8), ptr(fl), ptr(out), B, H0, W0, H, W, stream_ptr()), "dfe_prepare_triplets")
     return out
+
+
+def _cv_linear_axis(n_out, n_in, clamp):
+    """OpenCV 4.1.1 resize.cpp's coordinate set-up for INTER_LINEAR on 8-bit data along one axis: ``scale = 1. / ((double)
+    n_out / n_in)``, ``f = (float)((d + 0.5) * scale - 0.5)``, ``s = cvFloor(f)``, ``f -= s`` (float), the x axis clamped
+    (``s < 0 -> f = 0, s = 0``; ``s >= n_in - 1 -> f = 0, s = n_in - 1``), the y axis not; coefficients
+    ``saturate_cast<short>((1.f - f) * 2048)`` and ``saturate_cast<short>(f * 2048)`` (round half to even).  float32 where
+    OpenCV computes in float, float64 where it computes in double; numpy contracts nothing into an FMA."""
+    import numpy as np
+    scale = 1.0 / (float(n_out) / float(n_in))
+    f = ((np.arange(n_out, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f)
+    f = (f - s).astype(np.float32)
+    s = s.astype(np.int64)
+    if clamp:
+        lo = s < 0
+        f[lo], s[lo] = 0, 0
+        hi = s >= n_in - 1
+        f[hi], s[hi] = 0, n_in - 1
+    c0 = np.rint((np.float32(1.0) - f) * np.float32(2048)).astype(np.int64)
+    c1 = np.rint(f * np.float32(2048)).astype(np.int64)
+    return s, c0, c1
+
+
+def resize_u8_tables(h0, w0, h, w):
+    """Host tables of ``dfe_prepare_triplets_u8`` for a (h0, w0) -> (h, w) frame: int32 xtab [w, 2] = (x0, a0 | a1 << 16) and
+    ytab [h, 4] = (y0, y1, b0 | b1 << 16, 0).  Same size: cv::resize copies (x0 = dx, a = (2048, 0): both vertical rules
+    return the byte).  Exact 1/2 on both axes: cv::hal::resize switches to INTER_AREA, (a + b + c + d + 2) >> 2 (a = b =
+    (1024, 1024) on the pixel pairs: both vertical rules reduce to it exactly).  Otherwise INTER_LINEAR (_cv_linear_axis)."""
+    import numpy as np
+    h0, w0, h, w = int(h0), int(w0), int(h), int(w)
+    xt, yt = np.zeros((w, 2), np.int32), np.zeros((h, 4), np.int32)
+    if (h0, w0) == (h, w):
+        xs, ys = np.arange(w), np.arange(h)
+        xt[:, 0], xt[:, 1] = xs, 2048
+        yt[:, 0], yt[:, 1], yt[:, 2] = ys, ys, 2048
+    elif w0 == 2 * w and h0 == 2 * h:
+        xt[:, 0], xt[:, 1] = 2 * np.arange(w), 1024 | (1024 << 16)
+        yt[:, 0], yt[:, 1], yt[:, 2] = 2 * np.arange(h), 2 * np.arange(h) + 1, 1024 | (1024 << 16)
+    else:
+        sx, a0, a1 = _cv_linear_axis(w, w0, True)
+        sy, b0, b1 = _cv_linear_axis(h, h0, False)
+        xt[:, 0], xt[:, 1] = sx, a0 | (a1 << 16)
+        yt[:, 0], yt[:, 1], yt[:, 2] = np.clip(sy, 0, h0 - 1), np.clip(sy + 1, 0, h0 - 1), b0 | (b1 << 16)
+    return xt, yt
+
+
+def resize_u8_vector_bytes(w):
+    """Bytes of a resized 3-channel row of width w that VResizeLinearVec_32s8u covers: 16 * floor(n / 16) of n = 3w, plus 8 when
+    more than 8 remain; the rest take VResizeLinear's scalar rule.  This split is a reading of OpenCV 4.1.1, not pinned
+    against cv2; at the training width 832 (2496 bytes) the whole row is vector."""
+    n = 3 * int(w)
+    v = 16 * (n // 16)
+    return v + 8 if n - v > 8 else v
+
+
+class _U8Tables:
+    """Device copy of every (h0, w0, h, w) table set seen so far, concatenated (one xtab, one ytab), plus the 256-entry lut.  A new
+    size re-uploads the concatenation; the superseded tensors are kept (a few KB each) because a launch still in flight on another
+    stream may read them."""
+
+    def __init__(self):
+        self.lock = threading.Lock()
+        self.keys, self.host_x, self.host_y = {}, [], []
+        self.dev = {}          # device index -> (xtab, ytab, lut, number of keys uploaded)
+        self.retired = []
+
+    def get(self, keys, device):
+        """([(xtab, ytab) first entry per key], xtab, ytab, lut) on ``device``, uploading new keys' tables first."""
+        import numpy as np
+        with self.lock:
+            for k in keys:
+                if k not in self.keys:
+                    xt, yt = resize_u8_tables(*k)
+                    self.keys[k] = (sum(len(a) for a in self.host_x), sum(len(a) for a in self.host_y))
+                    self.host_x.append(xt)
+                    self.host_y.append(yt)
+            cur = self.dev.get(device.index)
+            if cur is None or cur[3] != len(self.keys):
+                if cur is not None:
+                    self.retired.append(cur)
+                lut = (np.arange(256, dtype=np.float64) / 255.0).astype(np.float32)
+                # blocking uploads: complete before any stream reads them
+                self.dev[device.index] = cur = (torch.from_numpy(np.concatenate(self.host_x)).to(device),
+                                                torch.from_numpy(np.concatenate(self.host_y)).to(device),
+                                                torch.from_numpy(lut).to(device), len(self.keys))
+            return [self.keys[k] for k in keys], cur[0], cur[1], cur[2]
+
+
+_u8_tables = _U8Tables()
+# dfe_u8_desc (include/dfe_hip.h), 32 bytes
+U8_DESC = [("offset", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("xtab", "<i4"), ("ytab", "<i4"), ("flip", "<i4"), ("pad", "<i4")]
+
+
+def prepare_triplets_u8(raw_u8, sizes, img_hw, flip=None, offsets=None, rgb=False):
+    """KITTI_Prepared.__getitem__'s image half (kitti_prepared.py:63-90,132-152) in the reference's 8-bit arithmetic
+    (dfe_prepare_triplets_u8: cv2.resize INTER_LINEAR on uint8 as OpenCV 4.1.1 computes it, cv2.flip, / 255.0) for a batch of
+    stacked triplets that may each have their own raw size.
+
+    raw_u8: uint8 device tensor holding sample b's strip [3*h0_b, w0_b, 3] at byte ``offsets[b]`` (a [B, 3*H0, W0, 3] tensor
+    with ``offsets`` None is the uniform case); sizes: B (h0, w0) frame sizes (the strip's rows are 3*h0); flip: B host values
+    (non-zero = cv2.flip(img, 1)); rgb: the bytes are R, G, B (a PIL decode) and are written in cv2.imread's B, G, R order.
+    Returns a fresh fp32 [B, 3, 3*H, W] tensor (the models' ``images``) whose values are float32(u / 255.0) for the bytes u cv2
+    would produce."""
+    import numpy as np
+    if not isinstance(raw_u8, torch.Tensor) or not raw_u8.is_cuda:
+        raise DfeError("prepare_triplets_u8 takes a uint8 tensor on a HIP device; there is no CPU fallback in the product path")
+    lib = get_lib()
+    if raw_u8.dtype != torch.uint8 or not raw_u8.is_contiguous():
+        raise ValueError("raw_u8 must be a contiguous uint8 tensor")
+    sizes = [(int(a), int(b)) for a, b in sizes]
+    B = len(sizes)
+    H, W = int(img_hw[0]), int(img_hw[1])
+    if B == 0 or H <= 0 or W <= 0 or any(a <= 0 or b <= 0 for a, b in sizes):
+        raise ValueError("prepare_triplets_u8: empty batch or a non-positive size")
+    nbytes = [9 * a * b for a, b in sizes]
+    if offsets is None:
+        offsets = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).tolist()
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != B or any(o < 0 or o + n > raw_u8.numel() for o, n in zip(offsets, nbytes)):
+        raise ValueError("prepare_triplets_u8: a strip lies outside raw_u8 (%d bytes)" % raw_u8.numel())
+    fl = [0] * B if flip is None else [int(v) for v in (flip.tolist() if isinstance(flip, torch.Tensor) else flip)]
+    if len(fl) != B:
+        raise ValueError("prepare_triplets_u8: flip must have one entry per sample")
+    index, xtab, ytab, lut = _u8_tables.get([(a, b, H, W) for a, b in sizes], raw_u8.device)
+    desc = np.zeros(B, U8_DESC)
+    desc["offset"], desc["flip"] = offsets, [1 if v else 0 for v in fl]
+    desc["h0"], desc["w0"] = [a for a, _ in sizes], [b for _, b in sizes]
+    desc["xtab"], desc["ytab"] = [i[0] for i in index], [i[1] for i in index]
+    # pinned staging (torch's caching host allocator keeps the block until the copy has run): no host sync behind the stream
+    d_desc = torch.from_numpy(desc.view(np.uint8)).pin_memory().to(raw_u8.device, non_blocking=True)
+    return prepare_triplets_u8_desc(raw_u8, d_desc, B, (H, W), (xtab, ytab, lut), rgb)
+
+
+def prepare_triplets_u8_desc(raw_u8, desc_u8, B, img_hw, tables, rgb=False):
+    """The launch under ``prepare_triplets_u8`` for a caller that built the B ``U8_DESC`` descriptors itself (``u8_tables`` gives the
+    table offsets) and placed them in device memory: prepared_data.PreparedFeeder uploads them with the strips in one copy.  The
+    caller guarantees every descriptor's strip lies inside raw_u8 and its table offsets come from ``tables``."""
+    H, W = int(img_hw[0]), int(img_hw[1])
+    xtab, ytab, lut = tables
+    out = torch.empty(B, 3, 3 * H, W, device=raw_u8.device)
+    check(get_lib().dfe_prepare_triplets_u8(ptr(raw_u8), ptr(desc_u8), ptr(xtab), ptr(ytab), ptr(lut), ptr(out), B, H, W,
+                                            resize_u8_vector_bytes(W), 1 if rgb else 0, stream_ptr()), "dfe_prepare_triplets_u8")
+    return out
+
+
+def u8_tables(sizes, img_hw, device):
+    """Device tables for frames of ``sizes`` [(h0, w0)] resized to img_hw: ({(h0, w0): (xtab, ytab) first entries}, (xtab, ytab,
+    lut)), uploaded once per size and kept."""
+    H, W = int(img_hw[0]), int(img_hw[1])
+    sizes = sorted(set((int(a), int(b)) for a, b in sizes))
+    index, xtab, ytab, lut = _u8_tables.get([(a, b, H, W) for a, b in sizes], torch.device(device))
+    return dict(zip(sizes, index)), (xtab, ytab, lut)
 
 
 def rescale_intrinsics(K, img_hw_orig, img_hw_new, num_scales):
