@@ -1130,3 +1130,43 @@ def test_hw_queue_limit_is_raised_only_when_it_can_take_effect(monkeypatch):
     monkeypatch.setattr(models, "_SIDE_STREAMS", {})
     got = models._side_streams(torch.device("cuda", 0))
     assert (got[0][1], got[1][1]) == (-1, 0)
+
+
+def test_fused_adam_keeps_its_own_capturable_across_load_state_dict():
+    """The optimiser's checkpoint contract: eager, --graph and torch.optim.Adam checkpoints are interchangeable and
+    the mode comes from the constructor, never from the checkpoint.  torch's load_state_dict overwrites every group key with
+    the checkpoint's, ``capturable`` included, and moves ``step`` to the parameter's device when the checkpoint says capturable;
+    FusedAdam keeps its own flag, still takes lr / betas / eps from the checkpoint, and keeps every count a float32 host scalar.
+    Construction, loading and saving need no GPU (only step() does)."""
+    import copy
+    from unsupervised_depth_opticalflow_egomotion_amd.optim import FusedAdam
+    torch.manual_seed(0)
+    shapes = [(5,), (3, 4), (1,)]
+    src = [torch.randn(s, requires_grad=True) for s in shapes]
+    ref = torch.optim.Adam([dict(params=src[:2]), dict(params=src[2:], lr=3e-4, betas=(0.8, 0.99), eps=1e-6)], lr=2e-3)
+    for _ in range(3):
+        for p in src:
+            p.grad = torch.randn_like(p)
+        ref.step()
+    plain = ref.state_dict()
+    assert all(g["capturable"] is False for g in plain["param_groups"])
+    flagged = copy.deepcopy(plain)
+    for g in flagged["param_groups"]:
+        g["capturable"] = True
+    for ckpt, mine in ((plain, True), (flagged, False), (plain, False), (flagged, True)):
+        ps = [torch.zeros(s, requires_grad=True) for s in shapes]
+        opt = FusedAdam([dict(params=ps[:2]), dict(params=ps[2:])], lr=1.0, betas=(0.1, 0.2), eps=0.5, capturable=mine)
+        opt.load_state_dict(copy.deepcopy(ckpt))
+        assert [g["capturable"] for g in opt.param_groups] == [mine, mine]
+        assert [(g["lr"], tuple(g["betas"]), g["eps"]) for g in opt.param_groups] == [(2e-3, (0.9, 0.999), 1e-8), (3e-4, (0.8, 0.99), 1e-6)]
+        for p, q in zip(ps, src):
+            st = opt.state[p]
+            assert st["step"].device.type == "cpu" and st["step"].dtype == torch.float32 and st["step"].dim() == 0
+            assert float(st["step"]) == 3.0
+            assert torch.equal(st["exp_avg"], ref.state[q]["exp_avg"]) and torch.equal(st["exp_avg_sq"], ref.state[q]["exp_avg_sq"])
+        out = opt.state_dict()
+        assert [g["capturable"] for g in out["param_groups"]] == [mine, mine]
+        assert all(float(out["state"][i]["step"]) == 3.0 for i in range(3))
+        back = torch.optim.Adam([dict(params=ps[:2]), dict(params=ps[2:])], lr=1.0)       # and torch reads it back
+        back.load_state_dict(out)
+        assert all(torch.equal(back.state[p]["exp_avg"], ref.state[q]["exp_avg"]) for p, q in zip(ps, src))

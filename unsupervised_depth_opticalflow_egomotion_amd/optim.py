@@ -52,7 +52,19 @@ class FusedAdam(torch.optim.Optimizer):
         return sd
 
     def load_state_dict(self, state_dict):
+        """As torch.optim.Adam's, except that ``capturable`` stays what the constructor was given: it says how THIS
+        process steps (train.py --graph or not), not what the moments are, and a checkpoint written in either mode -- or by
+        the reference's torch.optim.Adam -- loads into either.  torch would overwrite the flag with the checkpoint's along
+        with lr / betas / eps (which are still taken from it), and, where the checkpoint says capturable, move every
+        ``step`` to the device; here the counts always live on the host as float32 scalars (step() reads them per
+        parameter; the device count of a capturable group is seeded from them)."""
+        mine = [bool(g["capturable"]) for g in self.param_groups]
         super().load_state_dict(state_dict)
+        for g, c in zip(self.param_groups, mine):
+            g["capturable"] = c
+        for st in self.state.values():
+            if "step" in st:
+                st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
         self._plans = {}                       # the moment tensors were replaced
         self._dev_count = {}                   # re-seeded from the loaded counts at the next step
         if self._captured:

@@ -98,7 +98,8 @@ class GraphedTrainStep:
     the fused loss stack, backward and the optimiser step become one graph launch per iteration -- no per-kernel host work.
     Where it pays: whenever the host is the bound (the host needs ~16 ms to enqueue a step whatever the batch: B = 1 on one
     MI355X 17.9 ms eager -> 8.4 ms replayed; at B = 4 the GPU is the bound: 19.6 -> 19.4).
-    Requirements: static shapes; an optimiser made with ``make_optimizer(..., capturable=True)`` (the step count on the device);
+    Requirements: static shapes; an optimiser made with ``make_optimizer(..., capturable=True)`` (the step count on the device;
+    one with a non-capturable group is refused -- a checkpoint never changes the flag, see FusedAdam.load_state_dict);
     a single process (a data-parallel reducer's collectives are not captured: use the eager step there).  ``warmup`` eager steps
     run first on a side stream (allocator, MIOpen's solver choice, the Winograd filter cache); with ``restore`` (default) the
     parameters, buffers and optimiser state they changed are put back IN PLACE afterwards, so constructing the object trains
@@ -112,6 +113,10 @@ class GraphedTrainStep:
         import torch
         if hasattr(model, "reduce_gradients") or type(model).__name__ == "DistributedDataParallel":
             raise NotImplementedError("GraphedTrainStep: single-process training only (collectives are not captured)")
+        if not all(g.get("capturable") for g in optimizer.param_groups):
+            # a non-capturable step takes its bias corrections as kernel arguments: every replay would repeat the captured step's
+            raise ValueError("GraphedTrainStep: every param group of the optimiser must have capturable=True (the step count on "
+                             "the device): make it with make_optimizer(..., capturable=True)")
         self.model, self.optimizer, self.cfg = model, optimizer, cfg
         self.static_inputs = [t.clone() for t in inputs]
         saved = self._snapshot() if restore else None
@@ -179,8 +184,14 @@ class GraphedTrainStep:
                 if gi in dev_count:
                     for t, v in zip(dc, dev_count[gi]):
                         t.copy_(v)
-                else:
-                    dc[0].zero_()
+                else:                   # created by the warm-up: back to the count it was seeded from, i.e. the (just restored)
+                    t0 = 0.0            # host count of the group's first parameter with state -- N after a resume, 0 when fresh
+                    for p in opt.param_groups[gi]["params"]:
+                        st = opt.state.get(p)
+                        if st and "step" in st:
+                            t0 = float(st["step"])
+                            break
+                    dc[0].fill_(t0)
         from . import ops
         ops.wino_weights.invalidate()       # parameters written in place without a step: cached transformed filters are stale
         ops.wino_weights.refresh()
