@@ -281,7 +281,9 @@ int dfe_wgrad3x3_fwd(const float* p, const float* gy, float* gweight, float* par
  * dfe_planeconv_dgrad: gx [B,Ci,H,W] = the data gradient of conv(x, weight) for the output gradient gy [B,Co,H,W].
  * dfe_planeconv_wgrad: gweight [Co,Ci,3,3] = the weight gradient.
  * ws: dfe_planeconv_ws_floats floats of scratch (partial sums of the split reductions; every sum is added in a fixed order:
- * results are reproducible).  DFE_ERR_UNSUPPORTED (dfe_planeconv_supported == 0) for larger planes: the caller keeps MIOpen. */
+ * results are reproducible).  DFE_ERR_UNSUPPORTED (dfe_planeconv_supported == 0) for larger planes: the caller keeps MIOpen.
+ * Memory: every pointer needs dword alignment only; ws needs no initialisation; only the B samples of Co*H*W floats of dst1 /
+ * dst2 are written (batch strides below that: DFE_ERR_DIMS). */
 int dfe_planeconv_supported(int B, int Ci, int Co, int H, int W);
 long dfe_planeconv_ws_floats(int B, int Ci, int Co, int H, int W);
 int dfe_planeconv_fwd(const float* x, const float* weight, const float* bias, float slope, float* dst1, long dst1_batch_stride,
@@ -303,7 +305,12 @@ int dfe_planeconv_wgrad(const float* gy, const float* x, float* gweight, float* 
  * wbuf: scratch, 16-byte aligned, wbuf_floats floats: at least dfe_wino_weight_floats(Ci, Co) (the transformed filters);
  * with dfe_wino_scratch_floats(B, Ci, Co, H, W, P) the planes that cannot fill the chip (few tiles, many channels) split their
  * input channels over several blocks whose partial outputs are added in a fixed order.
- * DFE_ERR_DIMS when B*Ci*H*W >= 2^30 (32-bit offsets). */
+ * DFE_ERR_DIMS when B*Ci*H*W >= 2^30 (32-bit offsets).
+ * Memory: x, weight, bias, y and y2 need dword alignment only; x 8-byte aligned with W even selects the pair loads, y (y2)
+ * 8-byte aligned with an even batch stride and Wo even the 8-byte stores -- the same bits either way.  wbuf / U / part must be
+ * 16-byte aligned (DFE_ERR_UNSUPPORTED otherwise) and need no initialisation.  Reads stay inside x [B*Ci*H*W], weight, bias
+ * [Co] and U; writes inside the B samples of Co*Ho*Wo floats of y / y2 (the gaps of a larger batch stride are not touched)
+ * and the stated floats of the scratch. */
 long dfe_wino_weight_floats(int Ci, int Co);
 long dfe_wino_scratch_floats(int B, int Ci, int Co, int H, int W, int P);
 int dfe_wino_conv3x3(const float* x, const float* weight, float* y, long y_batch_stride, float* wbuf, long wbuf_floats, int B, int Ci,
@@ -314,7 +321,11 @@ int dfe_wino_conv3x3(const float* x, const float* weight, float* y, long y_batch
  * ci * H*W + i, element (b,co,i) of gy at gy + b * gy_batch_stride + co * Ho*Wo + i.  Straight from NCHW: no layout
  * transposes, no zero fill, no atomics (fixed-order partial sums in ws: dfe_wino_wgrad_floats floats); any size and
  * channel count.  A dilated layer (pwc_tf.py:31-36) is this call on its dilation x dilation phase images (B d^2 samples of
- * H/d x W/d pixels, P = 1), which the caller gathers. */
+ * H/d x W/d pixels, P = 1), which the caller gathers.
+ * Memory: x and gy need dword alignment only (any float offset, any batch stride >= the dense sample size) and may be views of
+ * any size, down to a single float: nothing outside the B samples of Ci*H*W / Co*Ho*Wo floats is read (the staging loads' safe
+ * address is the workspace).  gweight and ws need dword alignment; ws needs no initialisation and nothing outside
+ * dfe_wino_wgrad_floats floats of it is touched. */
 long dfe_wino_wgrad_floats(int B, int Ci, int Co, int H, int W, int P);
 /* tuning hook (process-wide, not for concurrent use): tile = 0 (by shape) / 11 / 12 / 21 forces the wave tile (16 MH x 16 NH
  * channels); blocks1 / blocks2 > 0: the grid-size targets of the 64- / 128-accumulator kernels; chunk = 8 / 12 tiles per
@@ -328,7 +339,10 @@ int dfe_wino_wgrad3x3(const float* x, long x_batch_stride, const float* gy, long
  * dfe_sconv_wgrad: gweight [Co,Ci,K,K] = the weight gradient; ws holds dfe_sconv_wgrad_floats(...) floats of split partials,
  * added in split order (no atomics: bit-reproducible).  0 floats / DFE_ERR_UNSUPPORTED: a shape outside the kernel family
  * (3x3 with Ci >= 16; Ci K K <= 160; Ci K K <= 448 with Co <= 32).  dfe_sconv_tune: blocks >= 0 the grid-size target (0: two or
- * three resident blocks per CU, by kernel); rows >= 0 caps the output rows per chunk (0: no cap); negative: keep. */
+ * three resident blocks per CU, by kernel); rows >= 0 caps the output rows per chunk (0: no cap); negative: keep.
+ * Memory: as dfe_wino_wgrad3x3 (dword-aligned, batch-strided views; ws uninitialised), except that the staging loads' safe
+ * address is the first 16 bytes of a sample: a sample of x or gy of fewer than 4 floats (Ci*H*W < 4 or Co*Ho*Wo < 4) is
+ * outside the kernel family (0 floats / DFE_ERR_UNSUPPORTED). */
 int dfe_sconv_tune(int blocks, int rows);
 long dfe_sconv_wgrad_floats(int B, int Ci, int Co, int H, int W, int K, int stride, int P);
 int dfe_sconv_wgrad(const float* x, long x_batch_stride, const float* gy, long gy_batch_stride, float* gweight, float* ws, int B,

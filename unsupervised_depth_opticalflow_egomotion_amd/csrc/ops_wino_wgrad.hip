@@ -91,8 +91,10 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
         const float* p = p0 + static_cast<long>(8 * k) * HW;
         const bool cok = xc_ + 8 * k < Cfg::CIB && cib0 + xc_ + 8 * k < C;
         wg_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-        {            // straight-line: one 16-byte load from a safe address, zero unless the slot lies inside
-          const WgQuadU u = *reinterpret_cast<const WgQuadU*>(full && cok ? p : x);
+        {            // straight-line: one 16-byte load from a safe address, zero unless the slot lies inside.  The safe address is the
+                     // workspace's first 16 bytes (at least 9 floats, whatever they hold: the value is dropped) -- x or gy may be
+                     // views of fewer than 4 floats (a 1x1 gy of one channel)
+          const WgQuadU u = *reinterpret_cast<const WgQuadU*>(full && cok ? p : part);
           if (full && cok) v = wg_f32x4{u.a, u.b, u.c, u.d};
         }
         if (!full && some && cok) {      // a slot that straddles the image's edge: element by element
@@ -114,7 +116,7 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
         const bool cok = gc_ + Cfg::GCH * k < Cfg::COB && cob0 + gc_ + Cfg::GCH * k < K;
         wg_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
         {
-          const WgQuadU u = *reinterpret_cast<const WgQuadU*>(full && cok ? p : gy);
+          const WgQuadU u = *reinterpret_cast<const WgQuadU*>(full && cok ? p : part);
           if (full && cok) v = wg_f32x4{u.a, u.b, u.c, u.d};
         }
         if (!full && some && cok) {
