@@ -32,7 +32,9 @@ extern "C" {
 #define DFE_MAX_SCALES 8
 /* Bumped whenever an exported signature changes, an entry point is removed or the host side starts to rely on a new one
  * (2: round 5 changed dfe_wino_wgrad3x3 and removed dfe_thin_conv3x3 / dfe_cast_*; 3: round 6 added dfe_pwc_level_map_bytes /
- * _fwd_map / _bwd_map, which ops.py calls).  _lib.py compares the library's value with this header's. */
+ * _fwd_map / _bwd_map, which ops.py calls).  _lib.py compares the library's value with this header's.  It also reads every
+ * ctypes argument and return type from the prototypes below (a new entry point is bound by declaring it here), so a prototype
+ * stays within: pointers of any kind, int, long, float, double, unsigned long long; returning int, long or const char*. */
 #define DFE_ABI_VERSION 3
 
 int dfe_abi_version(void);

@@ -23,7 +23,8 @@ def test_library_exports_every_header_symbol():
     for n in names:
         assert hasattr(lib, n), n
     assert _lib.get_lib().dfe_abi_version() == _lib.header_abi_version() >= 2
-    assert set(names) <= set(_lib._SIGNATURES) | {"dfe_abi_version"}
+    # every argument and return type is read from the prototype (tests/test_binding_cpu.py pins them): nothing is left untyped
+    assert all(getattr(_lib.get_lib(), n).argtypes is not None for n in names) and set(names) == set(_lib.header_signatures())
 
 
 def test_error_strings_and_argument_checks_without_gpu():

@@ -21,122 +21,56 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dfe_hip.h")
 _lib = None
 _lock = threading.Lock()
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-
-# symbol -> argtypes (restype is int unless listed in _RESTYPES)
-_SIGNATURES = {
-    "dfe_abi_version": [],
-    "dfe_error_string": [_I],
-    "dfe_camera_floats": [],
-    "dfe_prepare_cameras": [_P, _P, _P, _I, _I, _I, _P, _P],
-    "dfe_pose_vec2mat_fwd": [_P, _P, _P, _I, _P],
-    "dfe_pose_vec2mat_bwd": [_P, _P, _P, _P, _I, _P],
-    "dfe_warp_flow_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_scatter_ws_bytes": [ctypes.c_long],
-    "dfe_adam_chunk": [],
-    "dfe_adam_step": [_P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P],
-    "dfe_adam_step_dev": [_P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P],
-    "dfe_warp_flow_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_pose_partials_floats": [_I, _I, _I],
-    "dfe_inverse_warp2_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_inverse_warp2_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_wgrad3x3_partials_floats": [_I, _I, _I, _I, _I],
-    "dfe_wgrad3x3_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_wino_weight_floats": [_I, _I],
-    "dfe_wino_conv3x3": [_P, _P, _P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_wino_scratch_floats": [_I, _I, _I, _I, _I, _I],
-    "dfe_wino_wgrad_floats": [_I, _I, _I, _I, _I, _I],
-    "dfe_wino_wgrad_tune": [_I, _I, _I, _I],
-    "dfe_sconv_tune": [_I, _I],
-    "dfe_sconv_wgrad_floats": [_I, _I, _I, _I, _I, _I, _I, _I],
-    "dfe_sconv_wgrad": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_wino_wgrad3x3": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_wino_conv3x3_dilated": [_P, _P, _P, ctypes.c_long, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_wino_transform_blocks": [_I, _I],
-    "dfe_wino_transform_weights_multi": [_P, _P, _I, _P],
-    "dfe_wino_conv3x3_u": [_P, _P, _P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_wino_conv3x3_u_act": [_P, _P, _P, ctypes.c_float, _P, ctypes.c_long, _P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_conv1x1_small_supported": [_I, _I, _I, _I, _I],
-    "dfe_conv1x1_small_fwd": [_P, _P, _P, ctypes.c_float, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_conv1x1_small_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_planeconv_supported": [_I, _I, _I, _I, _I],
-    "dfe_planeconv_ws_floats": [_I, _I, _I, _I, _I],
-    "dfe_planeconv_fwd": [_P, _P, _P, ctypes.c_float, _P, ctypes.c_long, _P, ctypes.c_long, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_planeconv_dgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_planeconv_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_disp_head_partials_floats": [_I, _I, _I, _I],
-    "dfe_disp_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_disp_head_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_flow_head_partials_floats": [_I, _I, _I, _I],
-    "dfe_flow_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_flow_head_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_bn_partials_floats": [_I, _I, _I, _I, _I],
-    "dfe_bn_fwd": [_P] * 10 + [_I] * 5 + [ctypes.c_float, ctypes.c_float, _I, _P],
-    "dfe_bn_bwd": [_P] * 12 + [_I] * 6 + [_P],
-    "dfe_bias_act_partials_floats": [_I, _I, _I, _I],
-    "dfe_bias_act_fwd": [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P],
-    "dfe_bias_act_bwd": [_P, _P, ctypes.c_long, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, _P],
-    "dfe_bias_act_fwd2": [_P, _P, _P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _I, _I, ctypes.c_float, _P],
-    "dfe_bias_act_bwd2": [_P, ctypes.c_long, _P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, _P],
-    "dfe_bias_grad_final_multi": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_glue_partials_floats": [_I, _I, _I, _I],
-    "dfe_elu_pad_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_elu_pad_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_elu_up2_cat_pad_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_elu_up2_cat_pad_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_rigid_flow_fwd": [_P, _P, _P, _I, _I, _I, _P],
-    "dfe_rigid_flow_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "dfe_occ_masks": [_P] * 7 + [_I, _I, _I, _P],
-    "dfe_texture_mask": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "dfe_dynamic_mask": [_P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _I, _I, _P],
-    "dfe_exact_math_selftest": [_P, ctypes.c_ulonglong, _P],
-    "dfe_prepare_triplets": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_prepare_triplets_u8": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_forward_splat_ones": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_ssim_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_ssim_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "dfe_corr_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_corr_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_maxpool3x3s2_out": [_I],
-    "dfe_maxpool3x3s2_fwd": [_P, _P, _P, _I, _I, _I, _P],
-    "dfe_maxpool3x3s2_bwd": [_P, _P, _P, _I, _I, _I, _P],
-    "dfe_pwc_level_channels": [_I],
-    "dfe_pwc_level_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_pwc_level_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_pwc_level_map_bytes": [_I, _I, _I],
-    "dfe_pwc_level_fwd_map": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_pwc_level_bwd_map": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dfe_resize": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "dfe_resize_bilinear_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _I, _P],
-    "dfe_resize_bilinear_bwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _I, _P],
-    "dfe_geom_workspace_floats": [_P],
-    "dfe_geom_maskpack_offset_bytes": [_P, _I],
-    "dfe_geom_loss_fwd": [_P, _P],
-    "dfe_geom_loss_bwd": [_P, _P],
-    "dfe_geom_loss_fwd_profiled": [_P, _P, _P],
-    "dfe_geom_loss_bwd_profiled": [_P, _P, _P],
-    "dfe_geom_loss_fwd_timed": [_P, _P, _P],
-    "dfe_geom_loss_bwd_timed": [_P, _P, _P],
-    "dfe_geom_timed_collect": [_P, _P],
-}
-_RESTYPES = {"dfe_error_string": ctypes.c_char_p, "dfe_geom_workspace_floats": ctypes.c_long,
-             "dfe_bias_act_partials_floats": ctypes.c_long, "dfe_glue_partials_floats": ctypes.c_long,
-             "dfe_bn_partials_floats": ctypes.c_long, "dfe_disp_head_partials_floats": ctypes.c_long,
-             "dfe_flow_head_partials_floats": ctypes.c_long, "dfe_pwc_level_map_bytes": ctypes.c_long,
-             "dfe_wgrad3x3_partials_floats": ctypes.c_long, "dfe_planeconv_ws_floats": ctypes.c_long, "dfe_wino_weight_floats": ctypes.c_long, "dfe_wino_scratch_floats": ctypes.c_long, "dfe_wino_wgrad_floats": ctypes.c_long, "dfe_sconv_wgrad_floats": ctypes.c_long, "dfe_wino_transform_blocks": ctypes.c_long,
-             "dfe_geom_maskpack_offset_bytes": ctypes.c_long, "dfe_scatter_ws_bytes": ctypes.c_long}
-
 
 class DfeError(RuntimeError):
     pass
 
 
+# The type language of the header's prototypes.  Every parameter whose type contains ``*`` is a c_void_p (what ptr(), ctypes
+# arrays, byref(struct) and None are passed through); anything outside these tables is refused at load time.
+_ARG_TYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+              "unsigned long long": ctypes.c_ulonglong}
+_RETURN_TYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
+_TYPE_WORDS = {"void", "char", "short", "int", "long", "float", "double", "signed", "unsigned", "const"}
+
+
+def _argtype(symbol, param):
+    if "*" in param:
+        return ctypes.c_void_p
+    m = re.fullmatch(r"(.+) ([A-Za-z_]\w*)", param)            # "type name"; a prototype may also leave the name out
+    ctype = _ARG_TYPES.get(m.group(1) if m and m.group(2) not in _TYPE_WORDS else param)
+    if ctype is None:
+        raise DfeError("%s: cannot bind the parameter '%s' (the binding knows pointers, %s)"
+                       % (symbol, param, ", ".join(_ARG_TYPES)))
+    return ctype
+
+
+def header_signatures(path: str = HEADER_PATH):
+    """``{symbol: (restype, [argtypes])}`` for every prototype of include/dfe_hip.h, in ctypes types.  The header is the one
+    statement of the C ABI: a prototype this cannot read raises DfeError (no symbol is left with ctypes' untyped default)."""
+    with open(path) as fh:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", fh.read(), flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\b[^{;]*\{[^}]*\}[^;]*;", " ", text)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text).replace("}", " ")   # the struct bodies are gone: the only brace left closes it
+    sigs = {}
+    for decl in text.split(";"):
+        decl = re.sub(r"\s*\*\s*", "* ", " ".join(decl.split())).strip()
+        if not decl:
+            continue
+        m = re.fullmatch(r"(.*?)\b(dfe_\w+) ?\((.*)\)", decl)
+        if m is None:
+            raise DfeError("%s: cannot read '%s' as a prototype" % (path, decl))
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if ret not in _RETURN_TYPES:
+            raise DfeError("%s: cannot bind the return type '%s' (the binding knows %s)" % (name, ret, ", ".join(_RETURN_TYPES)))
+        sigs[name] = (_RETURN_TYPES[ret], [] if params == "void" else [_argtype(name, p.strip()) for p in params.split(",")])
+    return sigs
+
+
 def header_symbols(path: str = HEADER_PATH):
     """Function names declared in include/dfe_hip.h."""
-    with open(path) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(dfe_[a-z0-9_]+)\s*\(", text)))
+    return sorted(header_signatures(path))
 
 
 def header_abi_version(path: str = HEADER_PATH) -> int:
@@ -158,11 +92,9 @@ def get_lib():
                     "libdfe_hip.so not found at %s: build it with `python -c 'import __graft_entry__ as g; "
                     "g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
             lib = ctypes.CDLL(LIB_PATH)
-            for name in header_symbols():
+            for name, (restype, argtypes) in header_signatures().items():
                 fn = getattr(lib, name)  # AttributeError if the header and the library disagree
-                if name in _SIGNATURES:
-                    fn.argtypes = _SIGNATURES[name]
-                fn.restype = _RESTYPES.get(name, ctypes.c_int)
+                fn.restype, fn.argtypes = restype, argtypes
             if lib.dfe_abi_version() != header_abi_version():
                 raise DfeError("libdfe_hip.so ABI version %d != include/dfe_hip.h's DFE_ABI_VERSION %d: a stale build; "
                                "rebuild with __graft_entry__.build()" % (lib.dfe_abi_version(), header_abi_version()))

@@ -1,11 +1,22 @@
 // Internal (non-ABI) declarations shared by the translation units of libdfe_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstdlib>
 #include "../../include/dfe_hip.h"
+
+// after a kernel launch inside an entry point: a failed launch ends the call with DFE_ERR_LAUNCH
+#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 
 namespace dfe {
 struct ScaleList { float v[DFE_MAX_SCALES]; };
 struct IntList { int v[DFE_MAX_SCALES]; };
+
+// host helpers of the launchers
+inline int launch_status() { return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH; }   // the value an entry point returns after its last launch
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }   // an integer tuning switch; dflt when unset
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ops_corr.hip: the PWC cost volume and its gradients (LDS-staged).  out / gout: 81 planes per sample with batch stride
 // obs / gbs (the planes may be a slice of a wider tensor); add1 (batch stride abs1) is added to g1 when given.

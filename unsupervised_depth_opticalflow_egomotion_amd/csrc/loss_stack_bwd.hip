@@ -1068,7 +1068,6 @@ __global__ void __launch_bounds__(256) k_geom_pose_finalize(GeomDev D, GeomBwd G
 
 using namespace dfe;
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 
 static int geom_bwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
   GeomLayout L;

@@ -1107,7 +1107,6 @@ static int check_args(const dfe_geom_args* a, const GeomLayout& L, bool bwd) {
   return DFE_OK;
 }
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 
 extern "C" {
 

@@ -83,7 +83,7 @@ extern "C" int dfe_adam_step(const void* table, const int* blockmap, int nblocks
   dfe::k_adam_step<<<nblocks, 256, 0, static_cast<hipStream_t>(stream)>>>(static_cast<const dfe::AdamRec*>(table), blockmap,
                                                                         static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
                                                                         static_cast<float>(1.0 - beta2), step_size, c2s, static_cast<float>(eps), nullptr);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }
 
 extern "C" int dfe_adam_step_dev(const void* table, const int* blockmap, int nblocks, double lr, double beta1, double beta2, double eps,
@@ -92,8 +92,8 @@ extern "C" int dfe_adam_step_dev(const void* table, const int* blockmap, int nbl
   if (nblocks <= 0) return DFE_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
   dfe::k_adam_tick<<<1, 1, 0, st>>>(step_count, coef, lr, beta1, beta2);
-  if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH;
+  DFE_LAUNCH_CHECK();
   dfe::k_adam_step<<<nblocks, 256, 0, st>>>(static_cast<const dfe::AdamRec*>(table), blockmap, static_cast<float>(1.0 - beta1),
                                             static_cast<float>(beta2), static_cast<float>(1.0 - beta2), 0.0f, 1.0f, static_cast<float>(eps), coef);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }

@@ -704,7 +704,6 @@ __global__ void __launch_bounds__(256) k_resize_bilinear_bwd(const float* __rest
 using namespace dfe;
 
 #define DFE_REQUIRE(cond, code) do { if (!(cond)) return (code); } while (0)
-#define DFE_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 
 static inline dim3 grid1d(long n, int bs) { return dim3(static_cast<unsigned>((n + bs - 1) / bs)); }
 

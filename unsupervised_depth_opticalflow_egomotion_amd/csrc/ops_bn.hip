@@ -438,10 +438,8 @@ __global__ void __launch_bounds__(T) k_bn_bwd_small(const float* __restrict__ x,
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
 
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int bn_nchunk(long hw) { return static_cast<int>((hw + BN_CHUNK - 1) / BN_CHUNK); }
 
 static int bn_dims(int G, int Bg, int C, int H, int W) {
@@ -465,7 +463,7 @@ extern "C" int dfe_bn_fwd(const float* x, const float* residual, const float* we
   const int hw = H * W, nchunk = bn_nchunk(hw);
   const dim3 grid(nchunk, C, G * Bg);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = hw % 4 == 0 && al16(x) && al16(y) && (!residual || al16(residual));
+  const bool vec = hw % 4 == 0 && aligned16(x) && aligned16(y) && (!residual || aligned16(residual));
   if (vec && hw <= BNS_MAXHW && Bg <= BNS_MAXB) {
 #define DFE_BNS_FWD(GB, T) k_bn_fwd_small<GB, T><<<C, T, 0, st>>>(x, residual, weight, bias, running_mean, running_var, y, \
                                                                 save_mean, save_invstd, G, Bg, C, hw, eps, momentum, relu)
@@ -497,7 +495,7 @@ extern "C" int dfe_bn_bwd(const float* x, const float* y, const float* gy, const
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* gmean = scratch_means;
   float* gxmean = scratch_means + static_cast<long>(G) * C;
-  const bool vec = hw % 4 == 0 && al16(x) && al16(gy) && al16(gx) && (!relu || al16(y)) && (!gres || al16(gres));
+  const bool vec = hw % 4 == 0 && aligned16(x) && aligned16(gy) && aligned16(gx) && (!relu || aligned16(y)) && (!gres || aligned16(gres));
   if (vec && hw <= BNS_MAXHW && Bg <= BNS_MAXB) {
 #define DFE_BNS_BWD(GB, T) k_bn_bwd_small<GB, T><<<C, T, 0, st>>>(x, y, gy, weight, save_mean, save_invstd, gx, gres, gweight, \
                                                                 gbias, G, Bg, C, hw, relu)

@@ -510,7 +510,7 @@ bool corr_fwd_config(int B, int C, int H, int W, CorrFwdCfg& g, int& NT, size_t&
   // blocks, a 3-row instead of a 9-row f2 tile each: 13.8 / 19.7 / 17.2 -> 11.4 / 11.0 / 12.1 us at levels 4 / 5 / 6)
   int KS = 0, CC = 0, DYG = static_cast<long>(B) * ((H + TH - 1) / TH) * ntx >= 256 ? CR_K : 3;
   env_triple("DFE_CORR_FWD", TH, KS, CC);
-  if (const char* e = std::getenv("DFE_CORR_DYG")) { const int v = std::atoi(e); if (v >= 1 && v <= CR_K) DYG = v; }
+  if (const int v = env_int("DFE_CORR_DYG", 0); v >= 1 && v <= CR_K) DYG = v;
   const int ndyg = (CR_K + DYG - 1) / DYG;
   int NI = TH * TXQ * DYG;
   while (NI > 512 && TH > 1) { TH >>= 1; NI = TH * TXQ * DYG; }

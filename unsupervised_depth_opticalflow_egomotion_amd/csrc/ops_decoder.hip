@@ -479,13 +479,9 @@ __global__ void __launch_bounds__(256) k_cat_pad_bwd_skip(const float* __restric
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
-
 using namespace dfe;
 
 static inline bool grid_ok(long plane_elems, long batch, long channels) { return plane_elems < (1L << 31) && batch <= 65535 && channels <= 65535; }
-static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline unsigned nblk(long n) { return static_cast<unsigned>((n + 255) / 256); }
 
 extern "C" long dfe_glue_partials_floats(int B, int C, int H, int W) {
@@ -498,7 +494,7 @@ extern "C" int dfe_elu_pad_fwd(const float* x, const float* bias, float* out, in
   if (!x || !out) return DFE_ERR_NULL;
   if (B <= 0 || C <= 0 || H < 2 || W < 2 || !grid_ok((H + 2L) * (W + 2L), B, C)) return DFE_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (W % 2 == 0 && W >= 4 && al8(out)) k_elu_pad_fwd_pair<<<dim3(nblk((H + 2L) * ((W + 2L) / 2)), C, B), 256, 0, st>>>(x, bias, out, C, H, W, apply_elu);
+  if (W % 2 == 0 && W >= 4 && aligned8(out)) k_elu_pad_fwd_pair<<<dim3(nblk((H + 2L) * ((W + 2L) / 2)), C, B), 256, 0, st>>>(x, bias, out, C, H, W, apply_elu);
   else k_elu_pad_fwd<<<dim3(nblk((H + 2L) * (W + 2L)), C, B), 256, 0, st>>>(x, bias, out, C, H, W, apply_elu);
   DFE_LAUNCH_CHECK();
   return DFE_OK;
@@ -509,8 +505,8 @@ extern "C" int dfe_elu_pad_bwd(const float* x, const float* bias, const float* g
   if (!gout || !gx || (apply_elu && !x) || (gbias && !partials)) return DFE_ERR_NULL;
   if (B <= 0 || C <= 0 || H < 2 || W < 2 || !grid_ok((H + 2L) * (W + 2L), B, C)) return DFE_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool pair = W % 2 == 0 && W >= 4 && al8(gx) && (!apply_elu || al8(x));
-  const bool quad = W % 4 == 0 && W >= 8 && al16(gx) && (!apply_elu || al16(x));
+  const bool pair = W % 2 == 0 && W >= 4 && aligned8(gx) && (!apply_elu || aligned8(x));
+  const bool quad = W % 4 == 0 && W >= 8 && aligned16(gx) && (!apply_elu || aligned16(x));
   const unsigned nb = nblk(quad ? static_cast<long>(H) * (W / 4) : pair ? static_cast<long>(H) * (W / 2) : static_cast<long>(H) * W);   // <= the scratch size
   if (quad) k_elu_pad_bwd_quad<<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
   else if (pair) k_elu_pad_bwd_pair<<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
@@ -528,7 +524,7 @@ extern "C" int dfe_elu_up2_cat_pad_fwd(const float* x, const float* bias, const 
   if (!x || !out || (C2 > 0 && !skip)) return DFE_ERR_NULL;
   if (B <= 0 || C1 <= 0 || C2 < 0 || h < 1 || w < 1 || !grid_ok((2L * h + 2) * (2L * w + 2), B, C1 + C2)) return DFE_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (w >= 2 && al8(out)) k_elu_up2_cat_pad_fwd_pair<<<dim3(nblk((2L * h + 2) * (w + 1L)), C1 + C2, B), 256, 0, st>>>(x, bias, skip, out, C1, C2, h, w);
+  if (w >= 2 && aligned8(out)) k_elu_up2_cat_pad_fwd_pair<<<dim3(nblk((2L * h + 2) * (w + 1L)), C1 + C2, B), 256, 0, st>>>(x, bias, skip, out, C1, C2, h, w);
   else k_elu_up2_cat_pad_fwd<<<dim3(nblk((2L * h + 2) * (2L * w + 2)), C1 + C2, B), 256, 0, st>>>(x, bias, skip, out, C1, C2, h, w);
   DFE_LAUNCH_CHECK();
   return DFE_OK;
@@ -543,7 +539,7 @@ extern "C" int dfe_elu_up2_cat_pad_bwd(const float* x, const float* bias, const 
     unsigned nb = nblk(static_cast<long>(h) * w);
     const int tw = w <= 32 ? 32 : 64;
     const int tiles_x = (w + tw - 1) / tw, tiles_y = (h + UT_H - 1) / UT_H;
-    if (al8(gout) && static_cast<unsigned>(tiles_x * tiles_y) <= nb) {     // (the partial-sum scratch holds nb per plane)
+    if (aligned8(gout) && static_cast<unsigned>(tiles_x * tiles_y) <= nb) {     // (the partial-sum scratch holds nb per plane)
       nb = static_cast<unsigned>(tiles_x * tiles_y);
       if (tw == 32) k_elu_up2_cat_pad_bwd_x_tile<32><<<dim3(nb, C1, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C1, C2, h, w, tiles_x);
       else k_elu_up2_cat_pad_bwd_x_tile<64><<<dim3(nb, C1, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C1, C2, h, w, tiles_x);
@@ -557,8 +553,8 @@ extern "C" int dfe_elu_up2_cat_pad_bwd(const float* x, const float* bias, const 
     }
   }
   if (gskip && C2 > 0) {
-    if (w % 2 == 0 && w >= 4 && al16(gskip)) k_cat_pad_bwd_skip_quad<<<dim3(nblk(1L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
-    else if (w >= 2 && al8(gskip)) k_cat_pad_bwd_skip_pair<<<dim3(nblk(2L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
+    if (w % 2 == 0 && w >= 4 && aligned16(gskip)) k_cat_pad_bwd_skip_quad<<<dim3(nblk(1L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
+    else if (w >= 2 && aligned8(gskip)) k_cat_pad_bwd_skip_pair<<<dim3(nblk(2L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
     else k_cat_pad_bwd_skip<<<dim3(nblk(4L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
     DFE_LAUNCH_CHECK();
   }

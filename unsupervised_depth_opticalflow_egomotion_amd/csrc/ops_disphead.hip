@@ -297,7 +297,6 @@ __global__ void __launch_bounds__(64) k_head_final(const float* __restrict__ par
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
 
 static int dh_dims(int B, int C, int H, int W, int ci = DH_CI) {

@@ -204,10 +204,7 @@ __global__ void __launch_bounds__(EP_BLOCK) k_bias_act_bwd2(const float* y, long
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" long dfe_bias_act_partials_floats(int B, int C, int H, int W) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;

@@ -48,7 +48,7 @@ extern "C" int dfe_prepare_triplets(const unsigned char* in_u8, const unsigned c
   if (B <= 0 || H0 <= 0 || W0 <= 0 || H <= 0 || W <= 0) return DFE_ERR_DIMS;
   const long n = static_cast<long>(B) * 3 * H * W;
   dfe::k_prepare_triplets<<<static_cast<unsigned>((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(in_u8, flip, out, B, H0, W0, H, W);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -113,5 +113,5 @@ extern "C" int dfe_prepare_triplets_u8(const unsigned char* in_u8, const dfe_u8_
   const long n = static_cast<long>(B) * 3 * H * W;
   dfe::k_prepare_triplets_u8<<<static_cast<unsigned>((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
       in_u8, desc, reinterpret_cast<const int2*>(xtab), reinterpret_cast<const int4*>(ytab), lut, out, B, H, W, nvec, rgb);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }

@@ -59,7 +59,6 @@ __global__ void k_dynamic_mask(const float* __restrict__ flow, const float* __re
 using namespace dfe;
 
 #define DFE_REQUIRE(cond, code) do { if (!(cond)) return (code); } while (0)
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 
 extern "C" {
 

@@ -306,7 +306,6 @@ __global__ void __launch_bounds__(256) k_conv1x1_small_wgrad(const float* __rest
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
 
 namespace {
@@ -315,8 +314,8 @@ constexpr long PC_MAX_PIXELS = 4096;      // per sample: "small plane"; larger i
 struct PcCfg { int nsub, KS, cps, RB, XP, KP, ntm, ntn, xt; size_t lds; };
 
 int pc_target_blocks() {
-  static const int v = [] { const char* e = getenv("DFE_PLANECONV_BLOCKS"); const int t = e ? atoi(e) : 0; return t > 0 ? t : 512; }();
-  return v;
+  static const int t = env_int("DFE_PLANECONV_BLOCKS", 0);
+  return t > 0 ? t : 512;
 }
 
 // forward / data gradient: Ck reduction channels, N output channels

@@ -146,7 +146,7 @@ extern "C" int dfe_maxpool3x3s2_fwd(const float* x, float* y, unsigned char* idx
   const int Ho = dfe_maxpool3x3s2_out(H), Wo = dfe_maxpool3x3s2_out(W);
   const int strips = (Wo + 63) / 64, rbs = (Ho + dfe::PL_ROWS - 1) / dfe::PL_ROWS;
   dfe::k_maxpool3x3s2_fwd<<<dim3(strips * rbs, planes), 64, 0, static_cast<hipStream_t>(stream)>>>(x, y, idx, H, W, Ho, Wo, strips);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }
 
 extern "C" int dfe_maxpool3x3s2_bwd(const float* gy, const unsigned char* idx, float* gx, int planes, int H, int W, void* stream) {
@@ -155,5 +155,5 @@ extern "C" int dfe_maxpool3x3s2_bwd(const float* gy, const unsigned char* idx, f
   const int Ho = dfe_maxpool3x3s2_out(H), Wo = dfe_maxpool3x3s2_out(W);
   const int strips = (Wo + 63) / 64, rbs = (Ho + dfe::PL_ROWS - 1) / dfe::PL_ROWS;
   dfe::k_maxpool3x3s2_bwd<<<dim3(strips * rbs, planes), 64, 0, static_cast<hipStream_t>(stream)>>>(gy, idx, gx, H, W, Ho, Wo, strips);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }

@@ -56,7 +56,7 @@ int scatter_amax_into(unsigned* header, const float* amax_of, long amax_n, hipSt
   if (!header || !amax_of || amax_n <= 0) return DFE_ERR_NULL;
   const long blocks = (amax_n + 256 * 4 * 4 - 1) / (256 * 4 * 4);      // >= 4 float4 per thread
   k_scatter_amax<<<static_cast<unsigned>(blocks > 1024 ? 1024 : blocks), 256, 0, st>>>(amax_of, amax_n, header);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }
 
 int scatter_begin(void* ws, long n, const float* amax_of, long amax_n, hipStream_t st) {
@@ -71,13 +71,13 @@ int scatter_begin_const(void* ws, long n, float bound, hipStream_t st) {
   const int rc = scatter_begin_bound(ws, n, st);
   if (rc != DFE_OK) return rc;
   k_scatter_set_bound<<<1, 1, 0, st>>>(static_cast<unsigned*>(ws), bound);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }
 
 int scatter_finish_at(const void* header, const long long* acc, float* out, long n, hipStream_t st) {
   if (!header || !acc || !out || n <= 0) return DFE_ERR_NULL;
   k_scatter_to_float<<<static_cast<unsigned>((n + 511) / 512), 256, 0, st>>>(static_cast<const unsigned*>(header), acc, out, n);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }
 
 int scatter_finish(const void* ws, float* out, long n, hipStream_t st) {

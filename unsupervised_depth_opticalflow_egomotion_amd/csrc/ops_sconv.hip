@@ -265,12 +265,10 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
 
 namespace {
-int sc_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-int g_sc_blocks = sc_env("DFE_SCONV_BLOCKS", 0), g_sc_th = sc_env("DFE_SCONV_TH", 0);
+int g_sc_blocks = env_int("DFE_SCONV_BLOCKS", 0), g_sc_th = env_int("DFE_SCONV_TH", 0);
 
 int sc_log2_ceil(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
 int sc_pad_stride(int v) { return v + ((34 - (v & 31)) & 31); }      // the next stride with stride % 32 == 2 (see the bank note below)

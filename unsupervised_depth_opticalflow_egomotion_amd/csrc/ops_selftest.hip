@@ -42,5 +42,5 @@ extern "C" int dfe_exact_math_selftest(unsigned long long* counts, unsigned long
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) return DFE_ERR_LAUNCH;
   dfe::k_exact_selftest<<<4096, 256, 0, st>>>(counts, npairs);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }

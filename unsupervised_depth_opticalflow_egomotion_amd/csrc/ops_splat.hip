@@ -49,5 +49,5 @@ extern "C" int dfe_forward_splat_ones(const float* flow, float* out, void* ws, i
   rc = dfe::scatter_finish(ws, out, n, st);
   if (rc != DFE_OK) return rc;
   if (clamp01) dfe::k_clamp01<<<static_cast<unsigned>((n + 255) / 256), 256, 0, st>>>(out, n);
-  return hipGetLastError() == hipSuccess ? DFE_OK : DFE_ERR_LAUNCH;
+  return dfe::launch_status();
 }

@@ -144,7 +144,6 @@ __global__ void __launch_bounds__(16 * WF_LANES) k_wgrad_final(const float* __re
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
 
 // Work split: units = B * ceil(H / R) * nseg waves per tile pair.  Measured on MI355X (12 images): with one or two tile

@@ -452,7 +452,6 @@ __global__ void __launch_bounds__(64 * NW, 2) k_wino_fwd16(const float* __restri
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
 
 static int wn_dims(int B, int Ci, int Co, int H, int W, int P) {
@@ -473,7 +472,7 @@ struct WinoSplit { int nsp, cps; long part_floats; };
 // channel splits for the planes that cannot fill the chip: ntb tile blocks x nkt k-tiles < 384 blocks
 static WinoSplit wino_split(long ntiles, int Kpad, int Ci, int B, int Co, int Ho, int Wo) {
   WinoSplit w{1, Ci, 0};
-  static const bool enabled = [] { const char* e = getenv("DFE_WINO_SPLIT"); return !e || atoi(e) != 0; }();
+  static const bool enabled = env_int("DFE_WINO_SPLIT", 1) != 0;
   const long nblk = (ntiles + 63) / 64 * (Kpad / 32);
   if (!enabled || nblk >= 384 || Ci < 64) return w;
   int nsp = static_cast<int>((512 + nblk - 1) / nblk);
@@ -520,13 +519,13 @@ static int wino_run(const float* x, const float* weight, float* y, long y_batch_
     const int tpb = 64;
     const long nblk = (ntiles + tpb - 1) / tpb * nkt * sp.nsp;
     if (nblk >= (1L << 31)) return DFE_ERR_DIMS;
-    static const bool pair_ok = [] { const char* e = getenv("DFE_WINO_PAIR"); return !e || atoi(e) != 0; }();
+    static const bool pair_ok = env_int("DFE_WINO_PAIR", 1) != 0;
     const bool pair = pair_ok && dil == 1 && W % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0;
     const unsigned nitems = static_cast<unsigned>(nblk);
     // DFE_WINO_PERSIST=512: one resident round of persistent blocks (two per CU x 256 CUs).  Default 0 = one block per item: the
     // persistent form is 1-2.5 % faster per layer on an idle GPU and 0.08 ms SLOWER in the training step (18.93 against 18.85 ms,
     // three alternating pairs on one box) -- resident blocks leave the other streams' kernels no slot to slip into
-    static const int persist = [] { const char* e = getenv("DFE_WINO_PERSIST"); return e ? atoi(e) : 0; }();
+    static const int persist = env_int("DFE_WINO_PERSIST", 0);
     const unsigned g = persist > 0 ? std::min(nitems, static_cast<unsigned>(persist)) : nitems;
     const int nt = static_cast<int>(ntiles);
     const int pp = pair ? P : -1;

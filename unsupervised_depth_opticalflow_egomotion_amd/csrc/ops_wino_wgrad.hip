@@ -263,15 +263,13 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
 
 }  // namespace dfe
 
-#define DFE_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return DFE_ERR_LAUNCH; } while (0)
 using namespace dfe;
 
 namespace {
 struct WgPlan { int mh, nh, twc, ncot, ncit, nchunks, cps, S, cpr, TH, TWn, Ho, Wo; };
 
-int wg_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 // tuning knobs (dfe_wino_wgrad_tune): forced wave tile (0 = by shape), block targets of the 64- / 128-accumulator kernels, chunk
-int g_wg_tune[4] = {wg_env("DFE_WGRAD_TILE", 0), wg_env("DFE_WGRAD_BLOCKS1", 768), wg_env("DFE_WGRAD_BLOCKS2", 512), wg_env("DFE_WGRAD_CHUNK", 12)};
+int g_wg_tune[4] = {env_int("DFE_WGRAD_TILE", 0), env_int("DFE_WGRAD_BLOCKS1", 768), env_int("DFE_WGRAD_BLOCKS2", 512), env_int("DFE_WGRAD_CHUNK", 12)};
 
 // H, W: the input's size; P: the forward padding (0 / 1)
 bool wg_plan(int B, int Ci, int Co, int H, int W, int P, WgPlan* pl) {

@@ -38,6 +38,23 @@ def scatter_ws(n, device):
     return torch.empty(get_lib().dfe_scatter_ws_bytes(int(n)), device=device, dtype=torch.uint8)
 
 
+def _dense_chw(t):
+    """fp32 [B,C,H,W] whose samples are dense C x H x W planes, a batch stride of at least C*H*W floats apart: a contiguous
+    tensor or a channel slice of a wider one (the gradient of a torch.cat).  The entry points that take a batch stride read
+    such a view in place (``ptr(t, strided=True)``, ``t.stride(0)``); anything else goes through ``f32c`` first."""
+    _, C, H, W = t.shape
+    return (t.dtype == torch.float32 and t.stride(3) == 1 and t.stride(2) == W and t.stride(1) == H * W
+            and t.stride(0) >= C * H * W)
+
+
+def _chan_ptr(t, off):
+    """Device pointer of channel ``off`` of sample 0 of an fp32 tensor with dense planes (None -> NULL): with ``t.stride(0)``
+    as the batch stride, the channel slice ``t[:, off:]``."""
+    if t is None:
+        return None
+    return ctypes.c_void_p(t.data_ptr() + 4 * int(off) * t.shape[2] * t.shape[3])
+
+
 # --------------------------------------------------------------------------- cameras
 def prepare_cameras(pose, K, downscales):
     """pose [B,ndir,6] or [B,6], K [B,3,3] -> opaque camera buffer [B*ndir*len(downscales), 66]."""
@@ -713,6 +730,21 @@ def elu_up2_cat_pad(x, bias=None, skip=None):
 
 
 # --------------------------------------------------------------------------- convolution epilogue (bias + activation)
+def _bias_act_bwd(y, gy, slope, want_bias):
+    """(gz, gbias) of y = act(z + bias) on dfe_bias_act_bwd: gz = gy act'(y), gbias = its sum over (b,h,w) (None unless
+    ``want_bias``).  ``gy`` is fp32 with dense planes (``_dense_chw``) and is read with its own batch stride."""
+    lib = get_lib()
+    B, C, H, W = y.shape
+    gz = torch.empty_like(y)
+    gb = part = None
+    if want_bias:
+        gb = torch.empty(C, device=y.device, dtype=torch.float32)
+        part = torch.empty(lib.dfe_bias_act_partials_floats(B, C, H, W), device=y.device, dtype=torch.float32)
+    check(lib.dfe_bias_act_bwd(ptr(y), ptr(gy, strided=True), gy.stride(0), ptr(gz), ptr(gb), ptr(part), B, C, H, W, slope,
+                               stream_ptr()), "dfe_bias_act_bwd")
+    return gz, gb
+
+
 class BiasActFn(torch.autograd.Function):
     """z <- act(z + bias[c]) in place on a fresh convolution output; act(v) = v > 0 ? v : slope * v."""
 
@@ -732,21 +764,9 @@ class BiasActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = get_lib()
         (y,) = ctx.saved_tensors
-        B, C, H, W = y.shape
-        if gy.dtype != torch.float32:
-            gy = gy.float()
         # a channel slice of a wider contiguous tensor (the gradient of a torch.cat) is read in place
-        if not (gy.stride(3) == 1 and gy.stride(2) == W and gy.stride(1) == H * W and gy.stride(0) >= C * H * W):
-            gy = gy.contiguous()
-        gz = torch.empty_like(y)
-        gb = part = None
-        if ctx.has_bias and ctx.needs_input_grad[1]:
-            gb = torch.empty(C, device=y.device, dtype=torch.float32)
-            part = torch.empty(lib.dfe_bias_act_partials_floats(B, C, H, W), device=y.device, dtype=torch.float32)
-        check(lib.dfe_bias_act_bwd(ptr(y), ptr(gy, strided=True), gy.stride(0), ptr(gz), ptr(gb), ptr(part), B, C, H, W, ctx.slope,
-                                   stream_ptr()), "dfe_bias_act_bwd")
+        gz, gb = _bias_act_bwd(y, gy if _dense_chw(gy) else f32c(gy), ctx.slope, ctx.has_bias and ctx.needs_input_grad[1])
         return gz, gb, None
 
 
@@ -778,11 +798,9 @@ def _planeconv_ws(B, Ci, Co, H, W, dev):
 def planeconv_fwd_into(x, w, bias, slope, d1, d1_off=0, d2=None, d2_off=0):
     """act(conv3x3(x, w) + bias) into channels d1_off.. of d1 and (optionally) d2_off.. of d2 (contiguous NCHW buffers)."""
     B, Ci, H, W = x.shape
-    Co, HW = int(w.shape[0]), H * W
-    p1 = ctypes.c_void_p(d1.data_ptr() + 4 * d1_off * HW)
-    p2 = ctypes.c_void_p(d2.data_ptr() + 4 * d2_off * HW) if d2 is not None else None
+    Co = int(w.shape[0])
     ws = _planeconv_ws(B, Ci, Co, H, W, x.device)
-    check(get_lib().dfe_planeconv_fwd(ptr(x), ptr(w), ptr(bias), float(slope), p1, d1.stride(0), p2,
+    check(get_lib().dfe_planeconv_fwd(ptr(x), ptr(w), ptr(bias), float(slope), _chan_ptr(d1, d1_off), d1.stride(0), _chan_ptr(d2, d2_off),
                                       d2.stride(0) if d2 is not None else 0, ptr(ws), B, Ci, Co, H, W, stream_ptr()),
           "dfe_planeconv_fwd")
 
@@ -958,28 +976,29 @@ def wino_conv3x3(x, w, padding=1, transposed=False, dilation=1, bias=None, slope
     P, d = int(padding), int(dilation)
     lib = get_lib()
     Ho, Wo = (H, W) if d > 1 else (H + 2 * P - 2, W + 2 * P - 2)
+
+    def split_scratch():
+        """(part, part_floats) of dfe_wino_conv3x3_u / _u_act: the partial outputs of the input-channel splits (None, 0: no splits)"""
+        n = 0 if d > 1 else lib.dfe_wino_scratch_floats(B, Ci, Co, H, W, P) - lib.dfe_wino_weight_floats(Ci, Co)
+        return (torch.empty(n, device=x.device, dtype=torch.float32) if n > 0 else None), n
     if fused:
         if U is None:
             U = WinoWeightCache.transform_now(w, transposed)
         y = torch.empty(B, Co, Ho, Wo, device=x.device, dtype=torch.float32) if out is None else out
-        HWo = Ho * Wo
         for t in (y, out2):
             if t is not None and not (t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape[2:]) == (Ho, Wo) and t.shape[0] == B):
                 raise _lib.DfeError("wino_conv3x3: out / out2 must be contiguous fp32 [B, >= Co, Ho, Wo] buffers")
         if y.shape[1] < int(out_off) + Co or (out2 is not None and out2.shape[1] < int(out2_off) + Co):
             raise _lib.DfeError("wino_conv3x3: the output channels do not fit the destination buffer")
-        p1 = ctypes.c_void_p(y.data_ptr() + 4 * int(out_off) * HWo)
-        p2 = ctypes.c_void_p(out2.data_ptr() + 4 * int(out2_off) * HWo) if out2 is not None else None
-        npart = 0 if d > 1 else lib.dfe_wino_scratch_floats(B, Ci, Co, H, W, P) - lib.dfe_wino_weight_floats(Ci, Co)
-        part = torch.empty(npart, device=x.device, dtype=torch.float32) if npart > 0 else None
-        check(lib.dfe_wino_conv3x3_u_act(ptr(x), ptr(U), ptr(f32c(bias)) if bias is not None else None, float(slope), p1, y.stride(0), p2,
+        part, npart = split_scratch()
+        check(lib.dfe_wino_conv3x3_u_act(ptr(x), ptr(U), ptr(f32c(bias)) if bias is not None else None, float(slope),
+                                         _chan_ptr(y, out_off), y.stride(0), _chan_ptr(out2, out2_off),
                                          out2.stride(0) if out2 is not None else 0, ptr(part), npart, B, Ci, Co, H, W, P, d, stream_ptr()),
               "dfe_wino_conv3x3_u_act")
         return y
     y = torch.empty(B, Co, Ho, Wo, device=x.device, dtype=torch.float32)
     if U is not None:
-        npart = 0 if d > 1 else lib.dfe_wino_scratch_floats(B, Ci, Co, H, W, P) - lib.dfe_wino_weight_floats(Ci, Co)
-        part = torch.empty(npart, device=x.device, dtype=torch.float32) if npart > 0 else None
+        part, npart = split_scratch()
         check(lib.dfe_wino_conv3x3_u(ptr(x), ptr(U), ptr(y), y.stride(0), ptr(part), npart, B, Ci, Co, H, W, P, d, stream_ptr()),
               "dfe_wino_conv3x3_u")
         return y
@@ -1009,21 +1028,9 @@ class ConvBiasActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = get_lib()
         x, w, y = ctx.saved_tensors
         slope, P, d, has_bias = ctx.cfg
-        B, C, H, W = y.shape
-        if gy.dtype != torch.float32:
-            gy = gy.float()
-        if not (gy.stride(3) == 1 and gy.stride(2) == W and gy.stride(1) == H * W and gy.stride(0) >= C * H * W):
-            gy = gy.contiguous()
-        gz = torch.empty_like(y)
-        gb = part = None
-        if has_bias and ctx.needs_input_grad[2]:
-            gb = torch.empty(C, device=y.device, dtype=torch.float32)
-            part = torch.empty(lib.dfe_bias_act_partials_floats(B, C, H, W), device=y.device, dtype=torch.float32)
-        check(lib.dfe_bias_act_bwd(ptr(y), ptr(gy, strided=True), gy.stride(0), ptr(gz), ptr(gb), ptr(part), B, C, H, W, slope,
-                                   stream_ptr()), "dfe_bias_act_bwd")
+        gz, gb = _bias_act_bwd(y, gy if _dense_chw(gy) else f32c(gy), slope, has_bias and ctx.needs_input_grad[2])
         pad = (d, d) if d > 1 else (P, P)
         gx, gw, _ = convs.raw_backward(gz, x, w, (1, 1), pad, (d, d), ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return gx, gw, gb, None, None, None
@@ -1057,10 +1064,8 @@ def wino_wgrad3x3(x, gy, padding=1, dilation=1):
         if x.shape[2] % d or x.shape[3] % d or gy.shape[2:] != x.shape[2:]:
             raise _lib.DfeError("wino_wgrad3x3: a dilated layer needs H and W to be multiples of the dilation and padding = dilation")
         x, gy, padding = phase_images(x, d), phase_images(gy, d), 1
-    def dense_chw(t):
-        return t.dtype == torch.float32 and t.stride(3) == 1 and t.stride(2) == t.shape[3] and t.stride(1) == t.shape[2] * t.shape[3]
-    x = x if dense_chw(x) else f32c(x)
-    gy = gy if dense_chw(gy) else f32c(gy)
+    x = x if _dense_chw(x) else f32c(x)
+    gy = gy if _dense_chw(gy) else f32c(gy)
     B, Ci, H, W = x.shape
     Co, P = int(gy.shape[1]), int(padding)
     lib = get_lib()
@@ -1072,10 +1077,6 @@ def wino_wgrad3x3(x, gy, padding=1, dilation=1):
     check(lib.dfe_wino_wgrad3x3(ptr(x, strided=True), x.stride(0), ptr(gy, strided=True), gy.stride(0), ptr(gw), ptr(ws), B, Ci, Co, H, W, P,
                                 stream_ptr()), "dfe_wino_wgrad3x3")
     return gw
-
-
-def _dense_chw(t):
-    return t.dtype == torch.float32 and t.stride(3) == 1 and t.stride(2) == t.shape[3] and t.stride(1) == t.shape[2] * t.shape[3]
 
 
 def sconv_wgrad_supported(x_shape, co, k, stride, padding):
@@ -1121,17 +1122,8 @@ class PlaneConvActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = get_lib()
         x, w, y = ctx.saved_tensors
-        B, C, H, W = y.shape
-        gy = f32c(gy)
-        gz = torch.empty_like(y)
-        gb = part = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = torch.empty(C, device=y.device, dtype=torch.float32)
-            part = torch.empty(lib.dfe_bias_act_partials_floats(B, C, H, W), device=y.device, dtype=torch.float32)
-        check(lib.dfe_bias_act_bwd(ptr(y), ptr(gy), gy.stride(0), ptr(gz), ptr(gb), ptr(part), B, C, H, W, ctx.slope,
-                                   stream_ptr()), "dfe_bias_act_bwd")
+        gz, gb = _bias_act_bwd(y, f32c(gy), ctx.slope, ctx.has_bias and ctx.needs_input_grad[2])
         gx, gw = planeconv_backward(gz, x, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return gx, gw, gb, None
 
@@ -1162,14 +1154,7 @@ class Conv1x1SmallFn(torch.autograd.Function):
         x, w, y = ctx.saved_tensors
         B, Co, H, W = y.shape
         Ci = int(x.shape[1])
-        gy = f32c(gy)
-        gz = torch.empty_like(y)
-        gb = part = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = torch.empty(Co, device=y.device, dtype=torch.float32)
-            part = torch.empty(lib.dfe_bias_act_partials_floats(B, Co, H, W), device=y.device, dtype=torch.float32)
-        check(lib.dfe_bias_act_bwd(ptr(y), ptr(gy), gy.stride(0), ptr(gz), ptr(gb), ptr(part), B, Co, H, W, ctx.slope,
-                                   stream_ptr()), "dfe_bias_act_bwd")
+        gz, gb = _bias_act_bwd(y, f32c(gy), ctx.slope, ctx.has_bias and ctx.needs_input_grad[2])
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         check(lib.dfe_conv1x1_small_bwd(ptr(gz), ptr(x), ptr(w), ptr(gx), ptr(gw), B, Ci, Co, H, W, stream_ptr()),
@@ -1207,7 +1192,6 @@ class DenseDecodeFn(torch.autograd.Function):
         x = f32c(x)
         w, b = list(wb[0:12:2]), list(wb[1:12:2])          # conv_0..conv_4, predict_flow
         B, _, H, W = x.shape
-        HW = H * W
         co = [int(t.shape[0]) for t in w[:5]]              # 128, 128, 96, 64, 32
         dev = x.device
         cat = [torch.empty(B, co[k] + co[k + 1], H, W, device=dev, dtype=torch.float32) for k in range(4)]   # [x_k | x_k+1]
@@ -1215,10 +1199,8 @@ class DenseDecodeFn(torch.autograd.Function):
 
         def epilogue(z, k, d1, d1_off, d2, d2_off):
             c = co[k]
-            p1 = ctypes.c_void_p(d1.data_ptr() + 4 * d1_off * HW)
-            p2 = ctypes.c_void_p(d2.data_ptr() + 4 * d2_off * HW) if d2 is not None else None
-            check(lib.dfe_bias_act_fwd2(ptr(z), ptr(b[k]), p1, d1.stride(0), p2, d2.stride(0) if d2 is not None else 0,
-                                        B, c, H, W, slope, st), "dfe_bias_act_fwd2")
+            check(lib.dfe_bias_act_fwd2(ptr(z), ptr(b[k]), _chan_ptr(d1, d1_off), d1.stride(0), _chan_ptr(d2, d2_off),
+                                        d2.stride(0) if d2 is not None else 0, B, c, H, W, slope, st), "dfe_bias_act_fwd2")
 
         plane = planeconv_eligible(x, w[0])      # levels 6 / 5: the convolution and its epilogue are this build's kernels
         if plane:
@@ -1261,7 +1243,6 @@ class DenseDecodeFn(torch.autograd.Function):
         x, x0, cat, w = saved[0], saved[1], list(saved[2:6]), list(saved[6:12])
         co, slope = ctx.co, ctx.slope
         B, _, H, W = x.shape
-        HW = H * W
         dev = x.device
         st = stream_ptr()
         need = ctx.needs_input_grad          # (slope, x, w0, b0, ..., wp, bp)
@@ -1280,9 +1261,8 @@ class DenseDecodeFn(torch.autograd.Function):
                 gb = torch.empty(c, device=dev, dtype=torch.float32)
                 part = torch.empty(lib.dfe_bias_act_partials_floats(B, c, H, W), device=dev, dtype=torch.float32)
                 pending.append((part, gb, c))
-            sl = lambda t, off: ctypes.c_void_p(t.data_ptr() + 4 * off * HW)
-            check(lib.dfe_bias_act_bwd2(sl(ysrc, y_off), ysrc.stride(0), sl(g1, g1_off), g1.stride(0),
-                                        sl(g2, g2_off) if g2 is not None else None, g2.stride(0) if g2 is not None else 0,
+            check(lib.dfe_bias_act_bwd2(_chan_ptr(ysrc, y_off), ysrc.stride(0), _chan_ptr(g1, g1_off), g1.stride(0),
+                                        _chan_ptr(g2, g2_off), g2.stride(0) if g2 is not None else 0,
                                         ptr(gz), None, ptr(part), B, c, H, W, slope, st), "dfe_bias_act_bwd2")
             return gz, gb
 
@@ -1298,8 +1278,7 @@ class DenseDecodeFn(torch.autograd.Function):
         else:
             g3 = torch.zeros_like(cat[3])
         if g_x4 is not None:     # usually a channel slice of the gradient of torch.cat([flow, x4]): read in place
-            if g_x4.dtype != torch.float32 or not (g_x4.stride(3) == 1 and g_x4.stride(2) == W and g_x4.stride(1) == HW
-                                                   and g_x4.stride(0) >= co[4] * HW):
+            if not _dense_chw(g_x4):
                 g_x4 = f32c(g_x4)
         gz, gbias[4] = epilogue_bwd(4, cat[3], co[3], g3, co[3], g_x4, 0)                 # x4: cat3 slice + the returned copy
         g2, gw[4], _ = cb(gz, cat[2], w[4], True, nw(4))                                  # d/d cat(x2, x3)
