@@ -241,3 +241,418 @@ def wino_wgrad(x, gy, P, dtype, absolute=False):
 
 def leaky(v, slope):
     return torch.where(v > 0, v, v * slope)
+
+
+# ========================================================================================================= glue and head kernels
+# Helpers of test_hip_glue_guarded.py and test_hip_head_guarded.py: a byte carve, float64 references (``dtype`` = float64) and
+# fp32 yardsticks (the same expression with ``dtype`` = float32, run by ATen on the host), absolute-sum companions A, the margin
+# every thresholded decision keeps, and plain restatements of the launchers' branch rules (csrc/ops_decoder.hip,
+# ops_epilogue.hip, ops_bn.hip, ops_disphead.hip) so that a test can say which kernel a case runs.
+BYTE_SENTINEL = 0xA5       # not a window position (0..8)
+BYTE_GUARD = 64
+MARGIN = 64 * U24          # a decision's distance from its threshold, in units of its absolute sum
+
+
+class CarvedBytes:
+    """``Carved`` for a dense uint8 view (the window positions of the max pooling): ``offset_bytes`` past a 16-byte boundary."""
+
+    def __init__(self, shape, offset_bytes=0, device=None):
+        shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
+        assert all(s > 0 for s in shape) and 0 <= offset_bytes < 16
+        n = math.prod(shape)
+        total = (BYTE_GUARD + offset_bytes + n + BYTE_GUARD + 15) // 16 * 16
+        dev = default_device() if device is None else device
+        self.bits = torch.full((total,), BYTE_SENTINEL, dtype=torch.uint8, device=dev)
+        assert self.bits.data_ptr() % 16 == 0
+        self.lo, self.span = BYTE_GUARD + offset_bytes, n
+        self.view = self.bits[self.lo:self.lo + n].view(shape)
+        self.guard = torch.ones(total, dtype=torch.bool, device=dev)
+        self.guard[self.lo:self.lo + n] = False
+
+    @property
+    def ptr(self):
+        return self.view.data_ptr()
+
+    def intact(self):
+        return bool((self.bits[self.guard] == BYTE_SENTINEL).all())
+
+    def untouched(self):
+        return bool((self.bits[~self.guard] == BYTE_SENTINEL).all())
+
+    def written(self):
+        """every byte is a window position"""
+        return bool((self.view <= 8).all())
+
+    def cpu(self):
+        return self.view.detach().cpu().contiguous()
+
+
+def bits_equal(a, b):
+    """bit for bit (NaN payloads and the sign of zero included)"""
+    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
+    return a.shape == b.shape and a.dtype == b.dtype == torch.float32 and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def margin_ok(value64, A):
+    """every decision ``value > 0`` of the float64 reference is at least MARGIN * A away from its threshold"""
+    return bool((value64.abs() >= MARGIN * A).all())
+
+
+def _bc(t, dtype):
+    return 0.0 if t is None else t.to(dtype)[None, :, None, None]
+
+
+def _abc(t):
+    return 0.0 if t is None else t.double().abs()[None, :, None, None]
+
+
+def vjp(fn, in_shape, g, dtype):
+    """the adjoint of the linear map fn applied to g"""
+    v = torch.zeros(in_shape, dtype=dtype, requires_grad=True)
+    return torch.autograd.grad(fn(v), v, g.to(dtype))[0]
+
+
+# --------------------------------------------------------------------------------------------------------- epilogue
+def away_from_zero(shape, gen, scale=1.0):
+    """randn with every |value| >= 2^-10"""
+    t = torch.randn(shape, generator=gen, dtype=torch.float32) * scale
+    return torch.where(t.abs() < 2.0 ** -10, torch.full_like(t, 2.0 ** -10).copysign(t), t)
+
+
+def bias_act_ref(z, bias, slope, dtype):
+    return leaky(z.to(dtype) + _bc(bias, dtype), slope)
+
+
+def bias_act_A(z, bias):
+    return z.double().abs() + _abc(bias)
+
+
+def bias_act_bwd_ref(y, g, slope):
+    """exact in the gradient's own type: one selection, one product"""
+    return torch.where(y > 0, g, g * slope)
+
+
+def plane_sums(v, dtype):
+    """[B,C,H,W] -> [C]"""
+    return v.to(dtype).sum((0, 2, 3))
+
+
+# --------------------------------------------------------------------------------------------------------- decoder glue
+def elu_ref(v):
+    return torch.where(v > 0, v, torch.expm1(v))
+
+
+def elu_slope_ref(v):
+    return torch.where(v > 0, torch.ones_like(v), torch.exp(v))
+
+
+def pad1(v):
+    return F.pad(v, (1, 1, 1, 1), mode="reflect")
+
+
+def up2(v):
+    return F.interpolate(v, scale_factor=2, mode="bilinear", align_corners=False)
+
+
+def elu_A(x, bias):
+    """ELU value and slope pass through the hardware exponential: |x| + |b| + 1"""
+    return x.double().abs() + _abc(bias) + 1.0
+
+
+def elu_pad_ref(x, bias, apply_elu, dtype):
+    v = x.to(dtype) + _bc(bias, dtype)
+    return pad1(elu_ref(v) if apply_elu else v)
+
+
+def elu_pad_bwd_ref(x, bias, gout, apply_elu, dtype, absolute=False):
+    """gx = pad1^T(gout) * elu'(x + bias); absolute: pad1^T(|gout|) * (|x| + |b| + 1) (or * 1 without the ELU)"""
+    B, C, Hp, Wp = gout.shape
+    shape = (B, C, Hp - 2, Wp - 2)
+    if absolute:
+        g = vjp(pad1, shape, gout.abs(), torch.float64)
+        return g * elu_A(x, bias) if apply_elu else g
+    g = vjp(pad1, shape, gout, dtype)
+    return g * elu_slope_ref(x.to(dtype) + _bc(bias, dtype)) if apply_elu else g
+
+
+def up2_cat_pad_ref(x, bias, skip, dtype):
+    v = up2(elu_ref(x.to(dtype) + _bc(bias, dtype)))
+    return pad1(v if skip is None else torch.cat([v, skip.to(dtype)], 1))
+
+
+def up2_cat_pad_A(x, bias):
+    """of the C1 interpolated channels (the skip channels are copies)"""
+    return pad1(up2(elu_A(x, bias)))
+
+
+def up2_cat_pad_bwd_ref(x, bias, gout, dtype, absolute=False):
+    """(gx, gskip or None): gx = (pad1 . up2)^T(gout[:, :C1]) * elu'(x + bias), gskip = pad1^T(gout[:, C1:])"""
+    B, C1, h, w = x.shape
+    C2 = gout.shape[1] - C1
+    g = gout.abs().double() if absolute else gout.to(dtype)
+    dt = torch.float64 if absolute else dtype
+    gv = vjp(lambda v: pad1(up2(v)), x.shape, g[:, :C1], dt)
+    gx = gv * (elu_A(x, bias) if absolute else elu_slope_ref(x.to(dtype) + _bc(bias, dtype)))
+    gskip = vjp(pad1, (B, C2, 2 * h, 2 * w), g[:, C1:], dt) if C2 else None
+    return gx, gskip
+
+
+# --------------------------------------------------------------------------------------------------------- grouped batch norm
+def bn_fwd_ref(x, res, weight, bias, rmean, rvar, G, Bg, eps, momentum, relu):
+    """float64.  Returns a dict: pre (before the ReLU), y, mean, invstd [G*C], rmean, rvar [C] after the G updates in group order,
+    and the companions A_* (A_y includes the cancellation in x - mean: (|x| + mean|x|) invstd |w| + |b| + |res|)."""
+    N, C, H, W = x.shape
+    assert N == G * Bg
+    xg = x.double().view(G, Bg, C, H, W)
+    n = Bg * H * W
+    mean = xg.mean((1, 3, 4), keepdim=True)
+    var = ((xg - mean) ** 2).mean((1, 3, 4), keepdim=True)
+    invstd = 1.0 / torch.sqrt(var + eps)
+    w = torch.ones(C, dtype=torch.float64) if weight is None else weight.double()
+    b = torch.zeros(C, dtype=torch.float64) if bias is None else bias.double()
+    r = torch.zeros_like(xg) if res is None else res.double().view(G, Bg, C, H, W)
+    pre = (xg - mean) * invstd * w[None, None, :, None, None] + b[None, None, :, None, None] + r
+    amean = xg.abs().mean((1, 3, 4), keepdim=True)
+    xa = xg.abs() + amean
+    A_y = xa * invstd * w.abs()[None, None, :, None, None] + b.abs()[None, None, :, None, None] + r.abs()
+    A_var = (xa ** 2).mean((1, 3, 4))                                        # [G,C]: d^2 with d = x - mean rounded at |x| + mean|x|
+    unb = n / (n - 1.0) if n > 1 else 1.0
+    rm = torch.zeros(C, dtype=torch.float64) if rmean is None else rmean.double().clone()
+    rv = torch.zeros(C, dtype=torch.float64) if rvar is None else rvar.double().clone()
+    A_rm, A_rv = rm.abs(), rv.abs()
+    for g in range(G):
+        rm = (1.0 - momentum) * rm + momentum * mean[g, 0, :, 0, 0]
+        rv = (1.0 - momentum) * rv + momentum * var[g, 0, :, 0, 0] * unb
+        A_rm = (1.0 - momentum) * A_rm + momentum * amean[g, 0, :, 0, 0]
+        A_rv = (1.0 - momentum) * A_rv + momentum * A_var[g] * unb
+    flat = lambda t: t.reshape(G * C)
+    return dict(pre=pre.view(N, C, H, W), y=(pre.clamp_min(0.0) if relu else pre).view(N, C, H, W), A_y=A_y.view(N, C, H, W),
+                mean=flat(mean), A_mean=flat(amean), invstd=flat(invstd), A_invstd=flat(invstd) + 0.5 * flat(invstd) ** 3 * flat(A_var),
+                rmean=rm, A_rmean=A_rm, rvar=rv, A_rvar=A_rv)
+
+
+def bn_fwd_yard(x, res, weight, bias, rmean, rvar, G, Bg, eps, momentum, relu):
+    """ATen's fp32 batch norm on the host, group by group.  (y, mean [G*C], invstd [G*C], rmean, rvar)"""
+    rm = None if rmean is None else rmean.clone()
+    rv = None if rvar is None else rvar.clone()
+    ys, ms, iss = [], [], []
+    for g in range(G):
+        y, m, i = torch.native_batch_norm(x[g * Bg:(g + 1) * Bg], weight, bias, rm, rv, True, momentum, eps)
+        ys.append(y), ms.append(m), iss.append(i)
+    y = torch.cat(ys, 0)
+    if res is not None:
+        y = y + res
+    return (y.clamp_min(0.0) if relu else y), torch.cat(ms), torch.cat(iss), rm, rv
+
+
+def bn_bwd_ref(x, y, gy, weight, mean, invstd, G, Bg, relu):
+    """float64 on the given inputs (mean / invstd [G*C] as the forward saved them, y the forward's output).  dict: gx, gres,
+    gweight, gbias and A_*."""
+    N, C, H, W = x.shape
+    n = Bg * H * W
+    sh = (G, Bg, C, H, W)
+    xg, gg = x.double().view(sh), gy.double().view(sh)
+    if relu:
+        gg = torch.where(y.view(sh) > 0, gg, torch.zeros_like(gg))
+    mu, isd = mean.double().view(G, 1, C, 1, 1), invstd.double().view(G, 1, C, 1, 1)
+    w = (torch.ones(C, dtype=torch.float64) if weight is None else weight.double())[None, None, :, None, None]
+    xh = (xg - mu) * isd
+    xa = (xg.abs() + xg.abs().mean((1, 3, 4), keepdim=True)) * isd
+    m0, m1 = gg.mean((1, 3, 4), keepdim=True), (gg * xh).mean((1, 3, 4), keepdim=True)
+    a0, a1 = gg.abs().mean((1, 3, 4), keepdim=True), (gg.abs() * xa).mean((1, 3, 4), keepdim=True)
+    gx = w * isd * (gg - m0 - xh * m1)
+    A_gx = w.abs() * isd * (gg.abs() + a0 + xa * a1)
+    return dict(gx=gx.view(N, C, H, W), A_gx=A_gx.view(N, C, H, W), gres=gg.view(N, C, H, W), gweight=(gg * xh).sum((0, 1, 3, 4)),
+                A_gweight=(gg.abs() * xa).sum((0, 1, 3, 4)), gbias=gg.sum((0, 1, 3, 4)), A_gbias=gg.abs().sum((0, 1, 3, 4)), n=n)
+
+
+def bn_bwd_yard(x, y, gy, weight, mean, invstd, G, Bg, relu, eps):
+    """ATen's fp32 batch-norm backward on the host, group by group.  (gx, gweight, gbias)"""
+    g = torch.where(y > 0, gy, torch.zeros_like(gy)) if relu else gy
+    C = x.shape[1]
+    gxs, gw, gb = [], torch.zeros(C), torch.zeros(C)
+    for k in range(G):
+        s = slice(k * Bg, (k + 1) * Bg)
+        a, b, c = torch.ops.aten.native_batch_norm_backward(g[s].contiguous(), x[s].contiguous(), weight, None, None, mean[k * C:(k + 1) * C].contiguous(),
+                                                            invstd[k * C:(k + 1) * C].contiguous(), True, eps, [True, True, True])
+        gxs.append(a)
+        gw, gb = gw + b, gb + c
+    return torch.cat(gxs, 0), gw, gb
+
+
+def bn_case(G, Bg, C, H, W, relu, with_res, seed, affine=True, eps=1e-5, momentum=0.1):
+    """inputs of one batch-norm case whose ReLU decisions keep the margin: the first seed from ``seed`` on (CPU only; a handful
+    of tries at these sizes).  dict of fp32 tensors + ref (bn_fwd_ref's dict)."""
+    for s in range(seed, seed + 40):
+        gen = torch.Generator().manual_seed(s)
+        x = torch.randn(G * Bg, C, H, W, generator=gen) * 1.5 + torch.randn(1, C, 1, 1, generator=gen)
+        res = torch.randn(G * Bg, C, H, W, generator=gen) if with_res else None
+        weight = torch.rand(C, generator=gen) + 0.5 if affine else None
+        bias = torch.randn(C, generator=gen) * 0.5 if affine else None
+        rmean, rvar = torch.randn(C, generator=gen), torch.rand(C, generator=gen) + 0.5
+        gy = torch.randn(G * Bg, C, H, W, generator=gen)
+        ref = bn_fwd_ref(x, res, weight, bias, rmean, rvar, G, Bg, eps, momentum, relu)
+        if not relu or margin_ok(ref["pre"], ref["A_y"]):
+            return dict(x=x, res=res, weight=weight, bias=bias, rmean=rmean, rvar=rvar, gy=gy, ref=ref, seed=s, eps=eps, momentum=momentum)
+    raise AssertionError("no seed keeps the ReLU margin")
+
+
+# --------------------------------------------------------------------------------------------------------- max pooling
+def pool_input(planes, H, W, gen):
+    """post-ReLU values on a grid of 1/8 (ties are exact ties: tied zeros and tied positives), a few -inf and NaN"""
+    x = torch.relu(torch.round(torch.randn(planes, H, W, generator=gen) * 8.0) / 8.0)
+    flat = x.view(-1)
+    n = flat.numel()
+    k = max(1, n // 37)
+    pos = torch.randperm(n, generator=gen)
+    flat[pos[:k]] = float("-inf")
+    flat[pos[k:k + max(1, n // 61)]] = float("nan")
+    return x
+
+
+def pool_ref(x, gy):
+    """F.max_pool2d(3, 2, 1) of x [planes,H,W] on the host: (y, gx, window position 0..8 of every output)"""
+    planes, H, W = x.shape
+    xr = x[None].clone().requires_grad_(True)
+    y, ind = F.max_pool2d(xr, 3, 2, 1, return_indices=True)
+    gx = torch.autograd.grad(y, xr, gy[None])[0][0]
+    ind = ind[0]
+    Ho, Wo = ind.shape[1:]
+    oy, ox = torch.arange(Ho)[None, :, None], torch.arange(Wo)[None, None, :]
+    pos = (ind // W - (2 * oy - 1)) * 3 + (ind % W - (2 * ox - 1))
+    return y[0].detach(), gx, pos
+
+
+# --------------------------------------------------------------------------------------------------------- heads
+def disp_head_ref(p, w, bias, dtype, absolute=False):
+    if absolute:
+        return 0.25 * F.conv2d(p.double().abs(), w.double().abs()) + (0.0 if bias is None else 0.25 * bias.double().abs()[None, :, None, None]) + 1.0
+    return torch.sigmoid(F.conv2d(p.to(dtype), w.to(dtype), None if bias is None else bias.to(dtype)))
+
+
+def disp_head_bwd_ref(p, w, out, gout, dtype, absolute=False):
+    """(gp, gweight, gbias) on the given out: g = gout * out * (1 - out)"""
+    g = gout.to(dtype) * (out.to(dtype) * (1.0 - out.to(dtype)))
+    if absolute:
+        g, p, w, dtype = g.double().abs(), p.abs(), w.abs(), torch.float64
+    return (conv_dgrad_ref(g, w, p.shape, 1, 0, 1, dtype), conv_wgrad_ref(g, p, 3, 1, 0, 1, dtype), g.to(dtype).sum((0, 2, 3)))
+
+
+def flow_head_ref(x, w, bias, dtype, absolute=False):
+    if absolute:
+        return F.conv2d(x.double().abs(), w.double().abs(), None if bias is None else bias.double().abs(), 1, 1)
+    return F.conv2d(x.to(dtype), w.to(dtype), None if bias is None else bias.to(dtype), 1, 1)
+
+
+def flow_head_bwd_ref(x, w, gout, dtype, absolute=False):
+    if absolute:
+        x, w, gout, dtype = x.abs(), w.abs(), gout.abs(), torch.float64
+    return (conv_dgrad_ref(gout, w, x.shape, 1, 1, 1, dtype), conv_wgrad_ref(gout, x, 3, 1, 1, 1, dtype), gout.to(dtype).sum((0, 2, 3)))
+
+
+# --------------------------------------------------------------------------------------------------------- launch rules
+# Offsets are in floats past a 16-byte boundary: 8-byte aligned iff even, 16-byte aligned iff a multiple of 4.
+def _a8(off):
+    return off % 2 == 0
+
+
+def _a16(off):
+    return off % 4 == 0
+
+
+def rule_elu_pad_fwd(W, out_off):
+    return "pair" if W % 2 == 0 and W >= 4 and _a8(out_off) else "scalar"
+
+
+def rule_elu_pad_bwd(W, gx_off, x_off, apply_elu):
+    if W % 4 == 0 and W >= 8 and _a16(gx_off) and (not apply_elu or _a16(x_off)):
+        return "quad"
+    if W % 2 == 0 and W >= 4 and _a8(gx_off) and (not apply_elu or _a8(x_off)):
+        return "pair"
+    return "scalar"
+
+
+def rule_up2_fwd(w, out_off):
+    return "pair" if w >= 2 and _a8(out_off) else "scalar"
+
+
+def rule_up2_bwd(h, w, gout_off):
+    """{'tile32', 'tile64', 'tile64-inner', 'element', 'element-interior'}: what the gradient wrt x runs through"""
+    nb = (h * w + 255) // 256
+    tw = 32 if w <= 32 else 64
+    tx, ty = (w + tw - 1) // tw, (h + 15) // 16
+    if _a8(gout_off) and tx * ty <= nb:
+        out = {"tile%d" % tw}
+        for i0 in range(0, h, 16):
+            for j0 in range(0, w, tw):
+                if i0 >= 2 and i0 + 16 <= h - 2 and j0 >= 2 and j0 + tw <= w - 2:
+                    out.add("tile%d-inner" % tw)
+        return out
+    return {"element", "element-interior"} if h >= 5 and w >= 5 else {"element"}
+
+
+def up2_bwd_blocks(h, w, gout_off):
+    """partial sums per plane the launcher finishes"""
+    nb = (h * w + 255) // 256
+    tw = 32 if w <= 32 else 64
+    t = ((w + tw - 1) // tw) * ((h + 15) // 16)
+    return t if _a8(gout_off) and t <= nb else nb
+
+
+def rule_skip(w, gskip_off):
+    if w % 2 == 0 and w >= 4 and _a16(gskip_off):
+        return "quad"
+    return "pair" if w >= 2 and _a8(gskip_off) else "scalar"
+
+
+def rule_epilogue_vec(hw, offs, strides):
+    """offs: the offsets of the pointers given (None skipped); strides: the batch strides of the strided ones"""
+    return hw % 4 == 0 and all(_a16(o) for o in offs if o is not None) and all(s % 4 == 0 for s in strides if s is not None)
+
+
+EP_CHUNK = 2048
+BN_CHUNK = 2048
+
+
+def rule_bn(G, Bg, hw, offs):
+    """('small', GB, T) / ('three', 'vec') / ('three', 'scalar'); offs: the offsets of the tensors the launcher looks at"""
+    vec = hw % 4 == 0 and all(_a16(o) for o in offs if o is not None)
+    if vec and hw <= 4096 and Bg <= 4:
+        return ("small", 3 if G == 3 else 1, 64 if hw <= 256 else 256 if hw <= 1024 else 1024)
+    return ("three", "vec" if vec else "scalar")
+
+
+def rule_head_fwd(B, C, H, W, flow):
+    """dict(par, R, ns, nrb): the forward plan of the disparity (flow=False) / flow head"""
+    ns = (W + 61) // 62
+    if flow and 4 <= C // 8 <= 16:
+        return dict(par=True, R=4, ns=ns, nrb=(H + 3) // 4)
+    R = 16
+    while R > 2 and B * ns * ((H + R - 1) // R) < 2048:
+        R //= 2
+    return dict(par=False, R=R, ns=ns, nrb=(H + R - 1) // R)
+
+
+def rule_head_bwd(C, H, W, flow):
+    """dict(ns, nrb, nz) of the backward grid (strips and 16-row blocks of the PADDED plane)"""
+    return dict(ns=(W + 2 + 61) // 62, nrb=(H + 2 + 15) // 16, nz=C // (8 if flow else 16))
+
+
+# --------------------------------------------------------------------------------------------------------- inputs with margins
+def epilogue_input(shape, seed):
+    """(z, bias): z = t - bias with |t| >= 2^-10, so the sign of z + bias is decided ~2^-10 away from zero"""
+    gen = torch.Generator().manual_seed(seed)
+    bias = torch.randn(shape[1], generator=gen) * 0.5
+    return away_from_zero(shape, gen) - bias[None, :, None, None], bias
+
+
+def elu_input(shape, with_bias, seed):
+    """(x, bias or None): x + bias = t with |t| >= 2^-10 (the ELU branch), |t| up to ~6"""
+    gen = torch.Generator().manual_seed(seed)
+    bias = torch.randn(shape[1], generator=gen) * 0.5 if with_bias else None
+    t = away_from_zero(shape, gen, 2.0)
+    return (t - bias[None, :, None, None] if with_bias else t), bias
+
+
+def bn_seed(case, with_res):
+    return 1000 * sum(case[:5]) + 500 * int(with_res)

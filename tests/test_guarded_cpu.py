@@ -94,3 +94,279 @@ def test_winograd_wgrad_emulation_in_float64_is_atens_weight_gradient(shape, fam
     ntiles = B * ((H + 2 * P - 1) // 2) * ((W + 2 * P - 1) // 2)
     assert emu.shape == ref.shape == Sw.shape == (Co, Ci, 3, 3)
     assert bool(((emu - ref).abs() <= (ntiles + 32) * 2.0 ** -53 * Sw).all()), float((emu - ref).abs().max())
+
+
+# ========================================================================================================= glue and head helpers
+# Self-tests of what test_hip_glue_guarded.py and test_hip_head_guarded.py rely on: the byte carve, the float64 references
+# against ATen's float64 operators, the restated launch rules on the shapes of the matrices (tests/glue_cases.py), that every
+# matrix reaches every branch of its launcher, and the margin of every thresholded decision.
+import torch.nn.functional as F
+
+from tests import glue_cases as GC
+
+
+@pytest.mark.parametrize("off", [0, 1, 5, 15])
+def test_byte_carve_notices_a_stray_byte(off):
+    c = G.CarvedBytes((2, 3, 5), off, device=CPU)
+    assert c.view.data_ptr() % 16 == off and c.intact() and c.untouched() and not c.written()
+    assert c.lo >= 64 and c.bits.numel() - (c.lo + c.span) >= 64 and G.BYTE_SENTINEL > 8
+    c.view.fill_(8)
+    c.view[1, 2, 4] = 0
+    assert c.intact() and c.written() and not c.untouched()
+    c.view[0, 0, 0] = 9                          # not a window position
+    assert not c.written()
+    c.view[0, 0, 0] = 3
+    for pos in (c.lo - 1, c.lo + c.span, 0, c.bits.numel() - 1):
+        c.bits[pos] = 0
+        assert not c.intact(), pos
+        c.bits[pos] = G.BYTE_SENTINEL
+        assert c.intact()
+
+
+def _close64(a, b, A=None):
+    """float64 expressions of the same value: a few float64 roundings of the absolute sum apart"""
+    A = b.abs() if A is None else A
+    return a.shape == b.shape and a.dtype == b.dtype == torch.float64 and bool(((a - b).abs() <= 64 * 2.0 ** -53 * (A + 1e-300)).all())
+
+
+def test_epilogue_and_decoder_references_are_atens_float64_operators():
+    gen = torch.Generator().manual_seed(3)
+    x, b = torch.randn(2, 3, 4, 6, generator=gen), torch.randn(3, generator=gen)
+    v = (x.double() + b.double()[None, :, None, None]).requires_grad_(True)
+    for slope in GC.EP_SLOPES:
+        assert torch.equal(G.bias_act_ref(x, b, slope, torch.float64), F.leaky_relu(v, slope).detach())
+        y = F.leaky_relu(v, slope)
+        g = torch.randn(x.shape, generator=gen, dtype=torch.float64)
+        assert torch.equal(G.bias_act_bwd_ref(y.detach(), g, slope), torch.autograd.grad(y, v, g)[0])
+    assert torch.equal(G.bias_act_ref(x, None, 0.1, torch.float32), F.leaky_relu(x, 0.1))
+    # ELU, reflection pad, bilinear x2: values and gradients through autograd
+    for apply_elu in (0, 1):
+        ref = F.pad(F.elu(v) if apply_elu else v, (1, 1, 1, 1), mode="reflect")
+        assert _close64(G.elu_pad_ref(x, b, apply_elu, torch.float64), ref.detach())
+        g = torch.randn(ref.shape, generator=gen)
+        assert _close64(G.elu_pad_bwd_ref(x, b, g, apply_elu, torch.float64), torch.autograd.grad(ref, v, g.double())[0],
+                        G.elu_pad_bwd_ref(x, b, g, apply_elu, torch.float64, absolute=True))
+    skip = torch.randn(2, 2, 8, 12, generator=gen)
+    sk = skip.double().requires_grad_(True)
+    ref = F.pad(torch.cat([F.interpolate(F.elu(v), scale_factor=2, mode="bilinear", align_corners=False), sk], 1), (1, 1, 1, 1), mode="reflect")
+    assert _close64(G.up2_cat_pad_ref(x, b, skip, torch.float64), ref.detach())
+    g = torch.randn(ref.shape, generator=gen)
+    gx, gs = torch.autograd.grad(ref, (v, sk), g.double())
+    rx, rs = G.up2_cat_pad_bwd_ref(x, b, g, torch.float64)
+    ax, as_ = G.up2_cat_pad_bwd_ref(x, b, g, torch.float64, absolute=True)
+    assert _close64(rx, gx, ax) and _close64(rs, gs, as_) and bool((ax >= rx.abs()).all()) and bool((as_ >= rs.abs()).all())
+    assert G.up2_cat_pad_bwd_ref(x, b, g[:, :3], torch.float64)[1] is None
+    assert bool((G.up2_cat_pad_A(x, b) >= G.up2_cat_pad_ref(x, b, None, torch.float64).abs()).all())
+
+
+@pytest.mark.parametrize("G_,relu,with_res", [(1, 0, False), (2, 1, True), (3, 1, False)])
+def test_batch_norm_reference_is_atens_float64_batch_norm(G_, relu, with_res):
+    Bg, C, H, W = 2, 3, 4, 5
+    c = G.bn_case(G_, Bg, C, H, W, relu, with_res, 11)
+    x, w, b, ref = c["x"].double(), c["weight"].double(), c["bias"].double(), c["ref"]
+    rm, rv = c["rmean"].double().clone(), c["rvar"].double().clone()
+    xr = x.clone().requires_grad_(True)
+    wr, br = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    ys = [F.batch_norm(xr[g * Bg:(g + 1) * Bg], rm, rv, wr, br, True, c["momentum"], c["eps"]) for g in range(G_)]
+    y = torch.cat(ys, 0)
+    res = c["res"].double().requires_grad_(True) if with_res else None
+    if with_res:
+        y = y + res
+    y = y.relu() if relu else y
+    assert _close64(ref["y"], y.detach(), ref["A_y"]) and _close64(ref["rmean"], rm, ref["A_rmean"]) and _close64(ref["rvar"], rv, ref["A_rvar"])
+    for g in range(G_):
+        xs = x[g * Bg:(g + 1) * Bg]
+        assert _close64(ref["mean"][g * C:(g + 1) * C], xs.mean((0, 2, 3)), ref["A_mean"][g * C:(g + 1) * C])
+        assert _close64(ref["invstd"][g * C:(g + 1) * C], 1.0 / torch.sqrt(xs.var((0, 2, 3), unbiased=False) + c["eps"]), ref["A_invstd"][g * C:(g + 1) * C])
+    gy = c["gy"]
+    grads = torch.autograd.grad(y, (xr, wr, br) + ((res,) if with_res else ()), gy.double())
+    bw = G.bn_bwd_ref(c["x"], ref["y"], gy, c["weight"], ref["mean"], ref["invstd"], G_, Bg, relu)
+    assert _close64(bw["gx"], grads[0], bw["A_gx"]) and _close64(bw["gweight"], grads[1], bw["A_gweight"]) and _close64(bw["gbias"], grads[2], bw["A_gbias"])
+    if with_res:
+        assert torch.equal(bw["gres"], grads[3])
+    # the fp32 yardsticks are the same functions
+    yy, m, i, rm32, rv32 = G.bn_fwd_yard(c["x"], c["res"], c["weight"], c["bias"], c["rmean"], c["rvar"], G_, Bg, c["eps"], c["momentum"], relu)
+    assert float((yy.double() - ref["y"]).abs().max()) < 1e-5 and float((m.double() - ref["mean"]).abs().max()) < 1e-6
+    assert float((i.double() - ref["invstd"]).abs().max()) < 1e-5 and float((rv32.double() - ref["rvar"]).abs().max()) < 1e-6
+    gx32, gw32, gb32 = G.bn_bwd_yard(c["x"], yy, gy, c["weight"], m, i, G_, Bg, relu, c["eps"])
+    assert float((gx32.double() - bw["gx"]).abs().max()) < 1e-4 and float((gw32.double() - bw["gweight"]).abs().max()) < 1e-3
+
+
+@pytest.mark.parametrize("shape", GC.POOL_SHAPES)
+def test_pool_reference_positions_point_at_atens_gradient(shape):
+    gen = torch.Generator().manual_seed(sum(shape))
+    x = G.pool_input(*shape, gen)
+    planes, H, W = shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    gy = torch.randn(planes, Ho, Wo, generator=gen)
+    y, gx, pos = G.pool_ref(x, gy)
+    assert y.shape == (planes, Ho, Wo) and int(pos.min()) >= 0 and int(pos.max()) <= 8
+    if H * W > 16:
+        assert bool(torch.isnan(x).any()) and bool(torch.isinf(x).any()) and int((x == 0).sum()) > 1
+    # scattering gy to the recorded positions in output order is ATen's gradient
+    acc = torch.zeros(planes, H, W)
+    for p in range(planes):
+        for oy in range(Ho):
+            for ox in range(Wo):
+                k = int(pos[p, oy, ox])
+                iy, ix = 2 * oy - 1 + k // 3, 2 * ox - 1 + k % 3
+                assert 0 <= iy < H and 0 <= ix < W
+                assert G.bits_equal(x[p, iy, ix].reshape(1), y[p, oy, ox].reshape(1))
+                acc[p, iy, ix] += gy[p, oy, ox]
+    assert G.bits_equal(acc, gx)
+
+
+def test_head_references_are_atens_float64_convolution_and_gradients():
+    gen = torch.Generator().manual_seed(8)
+    p, w, b = torch.randn(2, 16, 7, 9, generator=gen), torch.randn(1, 16, 3, 3, generator=gen) * 0.2, torch.randn(1, generator=gen)
+    pr, wr, br = p.double().requires_grad_(True), w.double().requires_grad_(True), b.double().requires_grad_(True)
+    out = torch.sigmoid(F.conv2d(pr, wr, br))
+    assert torch.equal(G.disp_head_ref(p, w, b, torch.float64), out.detach())
+    gout = torch.randn(out.shape, generator=gen)
+    grads = torch.autograd.grad(out, (pr, wr, br), gout.double())
+    mine = G.disp_head_bwd_ref(p, w, out.detach(), gout, torch.float64)
+    A = G.disp_head_bwd_ref(p, w, out.detach(), gout, torch.float64, absolute=True)
+    for m, g, a in zip(mine, grads, A):
+        assert _close64(m, g, a) and bool((a >= m.abs() * (1 - 1e-12)).all())
+    A = G.disp_head_ref(p, w, b, torch.float64, absolute=True)
+    assert bool((A >= 1.0).all()) and A.shape == out.shape
+    x, w2, b2 = torch.randn(2, 8, 5, 6, generator=gen), torch.randn(2, 8, 3, 3, generator=gen), torch.randn(2, generator=gen)
+    xr, wr, br = x.double().requires_grad_(True), w2.double().requires_grad_(True), b2.double().requires_grad_(True)
+    out = F.conv2d(xr, wr, br, 1, 1)
+    assert torch.equal(G.flow_head_ref(x, w2, b2, torch.float64), out.detach())
+    gout = torch.randn(out.shape, generator=gen)
+    for m, g, a in zip(G.flow_head_bwd_ref(x, w2, gout, torch.float64), torch.autograd.grad(out, (xr, wr, br), gout.double()),
+                       G.flow_head_bwd_ref(x, w2, gout, torch.float64, absolute=True)):
+        assert _close64(m, g, a)
+
+
+# --------------------------------------------------------------------------------------------------------- launch rules
+def test_launch_rules_on_the_listed_shapes():
+    assert G.rule_elu_pad_fwd(8, 0) == "pair" and G.rule_elu_pad_fwd(8, 1) == "scalar" and G.rule_elu_pad_fwd(2, 0) == "scalar" and G.rule_elu_pad_fwd(3, 0) == "scalar"
+    assert G.rule_elu_pad_bwd(8, 0, 0, 1) == "quad" and G.rule_elu_pad_bwd(8, 0, 2, 1) == "pair" and G.rule_elu_pad_bwd(8, 0, 2, 0) == "quad"
+    assert G.rule_elu_pad_bwd(12, 2, 0, 1) == "pair" and G.rule_elu_pad_bwd(12, 1, 0, 1) == "scalar" and G.rule_elu_pad_bwd(6, 0, 0, 1) == "pair"
+    assert G.rule_elu_pad_bwd(4, 0, 0, 1) == "pair" and G.rule_elu_pad_bwd(8, 0, 1, 1) == "scalar" and G.rule_elu_pad_bwd(2, 0, 0, 0) == "scalar"
+    assert G.rule_up2_bwd(1, 1, 0) == {"tile32"} and G.rule_up2_bwd(17, 33, 0) == {"tile64"} and G.rule_up2_bwd(5, 65, 0) == {"tile64"}
+    assert G.rule_up2_bwd(3, 65, 0) == {"element"} and G.rule_up2_bwd(3, 65, 1) == {"element"}
+    assert G.rule_up2_bwd(50, 196, 0) == {"tile64", "tile64-inner"} and G.rule_up2_bwd(50, 196, 1) == {"element", "element-interior"}
+    assert G.rule_up2_bwd(33, 65, 0) == {"tile64"} and G.rule_up2_bwd(19, 300, 0) == {"tile64"}      # the operator tests' largest: no inner tile
+    assert G.rule_up2_bwd(34, 130, 0) == {"tile64", "tile64-inner"} and G.rule_up2_bwd(33, 130, 0) == {"tile64"} and G.rule_up2_bwd(34, 129, 0) == {"tile64"}
+    assert G.up2_bwd_blocks(3, 65, 0) == 1 and G.up2_bwd_blocks(17, 33, 0) == 2 and G.up2_bwd_blocks(17, 33, 1) == 3 and G.up2_bwd_blocks(50, 196, 0) == 16
+    assert G.rule_skip(5, 0) == "pair" and G.rule_skip(2, 0) == "pair" and G.rule_skip(196, 0) == "quad" and G.rule_skip(196, 2) == "pair" and G.rule_skip(196, 1) == "scalar"
+    assert G.rule_skip(1, 0) == "scalar" and G.rule_up2_fwd(1, 0) == "scalar" and G.rule_up2_fwd(5, 0) == "pair" and G.rule_up2_fwd(5, 1) == "scalar"
+    assert G.rule_epilogue_vec(208, [0, 0, 0], [4]) and not G.rule_epilogue_vec(208, [0, 0, 0], [2]) and not G.rule_epilogue_vec(208, [0, 1, 0], [0])
+    assert not G.rule_epilogue_vec(63, [0, 0], []) and G.rule_epilogue_vec(52, [0, None, 0], [None, 288])
+    assert G.rule_bn(3, 2, 208, [0, 0]) == ("small", 3, 64) and G.rule_bn(1, 4, 256, [0, 0]) == ("small", 1, 64) and G.rule_bn(2, 2, 224, [0, 0]) == ("small", 1, 64)
+    assert G.rule_bn(2, 4, 260, [0]) == ("small", 1, 256) and G.rule_bn(3, 4, 1024, [0]) == ("small", 3, 256) and G.rule_bn(2, 4, 1028, [0]) == ("small", 1, 1024)
+    assert G.rule_bn(1, 4, 4096, [0]) == ("small", 1, 1024) and G.rule_bn(1, 4, 4100, [0]) == ("three", "vec") and G.rule_bn(1, 5, 256, [0]) == ("three", "vec")
+    assert G.rule_bn(2, 4, 1040, [1, 0]) == ("three", "scalar") and G.rule_bn(2, 4, 975, [0]) == ("three", "scalar") and G.rule_bn(4, 3, 4352, [0]) == ("three", "vec")
+    for R, B, H, W in GC.HEAD_R_CASES:
+        for flow, C in ((False, 16), (True, 8), (True, 136)):
+            plan = G.rule_head_fwd(B, C, H, W, flow)
+            assert plan == dict(par=False, R=R, ns=2 if W == 63 else 1, nrb=(H + R - 1) // R), (R, B, H, W, plan)
+    assert G.rule_head_fwd(12, 16, 64, 208, False)["R"] == 2 and G.rule_head_fwd(12, 16, 256, 832, False)["R"] == 16 and G.rule_head_fwd(12, 16, 128, 416, False)["R"] == 4
+    assert G.rule_head_fwd(2, 32, 5, 63, True) == dict(par=True, R=4, ns=2, nrb=2) and G.rule_head_fwd(2, 128, 1, 62, True) == dict(par=True, R=4, ns=1, nrb=1)
+    assert not G.rule_head_fwd(2, 24, 5, 63, True)["par"] and not G.rule_head_fwd(2, 136, 5, 63, True)["par"]
+    assert G.rule_head_bwd(16, 14, 60, False) == dict(ns=1, nrb=1, nz=1) and G.rule_head_bwd(48, 15, 61, False) == dict(ns=2, nrb=2, nz=3)
+    assert G.rule_head_bwd(24, 15, 62, True) == dict(ns=2, nrb=2, nz=3) and G.rule_head_bwd(8, 14, 62, True) == dict(ns=2, nrb=1, nz=1)
+
+
+def test_the_cases_reach_every_branch_of_the_epilogue():
+    for name, variants, rule in (("fwd2", GC.EP_FWD2, GC.ep_fwd2_vec), ("bwd", GC.EP_BWD, GC.ep_bwd_vec), ("bwd2", GC.EP_BWD2, GC.ep_bwd2_vec)):
+        reached = {(rule(s[2] * s[3], v), -(-s[2] * s[3] // G.EP_CHUNK)) for s in GC.EP_SHAPES for v in variants}
+        assert reached == {(True, 1), (False, 1), (True, 2), (False, 2)}, (name, reached)
+        # a strided operand four floats wider stays on the vector kernel, one or two floats wider leaves it
+        hw = 208
+        assert any(rule(hw, v) and any(x == 4 for x in v[3:-1] if isinstance(x, int)) for v in variants), name
+        assert any(not rule(hw, v) and all(o in (0, None) for o in v[:3]) for v in variants), name
+    assert {G.rule_epilogue_vec(s[2] * s[3], [o], []) for s in GC.EP_SHAPES for o in (0, 1)} == {True, False}
+
+
+def test_the_cases_reach_every_branch_of_elu_pad():
+    cases = GC.elu_pad_cases()
+    assert {(H, W) for H, W, _, _ in cases} == {(H, W) for H in GC.ELU_PAD_H for W in GC.ELU_PAD_W}
+    assert {(e, b) for _, _, e, b in cases} == {(0, False), (0, True), (1, False), (1, True)}
+    fwd = {(G.rule_elu_pad_fwd(W, oo), W % 2) for _, W, _, _ in cases for _, oo in GC.ELU_PAD_FWD_OFFS}
+    assert fwd == {("pair", 0), ("scalar", 0), ("scalar", 1)}                       # the scalar fallback at even W included
+    bwd = {(G.rule_elu_pad_bwd(W, go, xo, e), W % 4 == 0 and W >= 8) for _, W, e, _ in cases for xo, _, go in GC.ELU_PAD_BWD_OFFS}
+    assert bwd == {("quad", True), ("pair", True), ("scalar", True), ("pair", False), ("scalar", False)}
+    assert {o for _, o, _ in GC.ELU_PAD_BWD_OFFS} == {0, 1, 2} and {o for o, _ in GC.ELU_PAD_FWD_OFFS} == {0, 1, 2}    # the unchecked operands
+
+
+def test_the_cases_reach_every_branch_of_up2_cat_pad():
+    reached = set()
+    for B, C1, h, w, C2 in GC.UP2_SHAPES:
+        for o in GC.UP2_GOUT_OFFS:
+            reached |= G.rule_up2_bwd(h, w, o)
+    assert reached == {"tile32", "tile64", "tile64-inner", "element", "element-interior"}
+    assert "tile64-inner" in G.rule_up2_bwd(50, 196, 0) and G.rule_up2_bwd(3, 65, 0) == {"element"}       # the element kernel on an aligned gout
+    assert {G.rule_skip(w, o) for _, _, _, w, C2 in GC.UP2_SHAPES if C2 for o in GC.UP2_GSKIP_OFFS} == {"quad", "pair", "scalar"}
+    assert {(G.rule_skip(w, o), w % 2) for _, _, _, w, C2 in GC.UP2_SHAPES if C2 for o in GC.UP2_GSKIP_OFFS} >= {("scalar", 0), ("pair", 0), ("pair", 1)}
+    assert {G.rule_up2_fwd(w, o) for _, _, _, w, _ in GC.UP2_SHAPES for o in GC.UP2_OUT_OFFS} == {"pair", "scalar"}
+    assert {C2 > 0 for *_, C2 in GC.UP2_SHAPES} == {True, False}
+
+
+def test_the_cases_reach_every_branch_of_batch_norm():
+    for direction in ("fwd", "bwd"):
+        reached = set()
+        for case in GC.bn_cases():
+            for relu in (0, 1):
+                for with_res in (False, True):
+                    reached.add(GC.bn_rule(case, direction, relu, with_res))
+        want = {("small", gb, t) for gb in (1, 3) for t in (64, 256, 1024)} | {("three", "vec"), ("three", "scalar")}
+        assert reached == want, (direction, reached)
+    small = {(c[0], GC.bn_rule(c, "fwd", 1, False)) for c in GC.bn_cases()}
+    assert {(2, ("small", 1, t)) for t in (64, 256, 1024)} <= small                 # G = 2 on the single kernel at all three sizes
+    # both sides of every threshold, at the same G
+    for g in (1, 2, 3):
+        by = {(c[1], c[3] * c[4]): GC.bn_rule(c, "fwd", 1, False) for c in GC.bn_cases() if c[0] == g and c[2] == 2 and c[5] is None}
+        assert by[(4, 256)][2] == 64 and by[(4, 260)][2] == 256 and by[(4, 1024)][2] == 256 and by[(4, 1028)][2] == 1024 and by[(4, 4096)][2] == 1024
+        assert by[(4, 4100)] == ("three", "vec") and by[(5, 256)] == ("three", "vec") and by[(5, 4096)] == ("three", "vec")
+    # every tensor the launchers look at is off alignment once, at hw % 4 == 0
+    for name in ("x", "y", "res"):
+        assert GC.bn_rule((3, 2, 5, 8, 26, name), "fwd", 1, True) == ("three", "scalar")
+    for name in ("x", "y", "gy", "gx", "gres"):
+        assert GC.bn_rule((3, 2, 5, 8, 26, name), "bwd", 1, True) == ("three", "scalar")
+    assert any(c[3] * c[4] > G.BN_CHUNK and (c[3] * c[4]) % G.BN_CHUNK and GC.bn_rule(c, "fwd", 1, False)[0] == "three" for c in GC.bn_cases())
+
+
+def test_the_cases_reach_every_branch_of_the_heads():
+    fwd = set()
+    for R, B, H, W in GC.HEAD_R_CASES:
+        for flow, cs in ((False, GC.DISP_C), (True, GC.FLOW_C_SERIAL)):
+            for C in cs:
+                plan = G.rule_head_fwd(B, C, H, W, flow)
+                assert plan["R"] == R and not plan["par"]
+                fwd.add((flow, plan["R"], plan["ns"]))
+    assert fwd == {(f, r, 1) for f in (False, True) for r in (2, 4, 8, 16)} | {(False, 16, 2), (True, 16, 2)}
+    par = {(G.rule_head_fwd(GC.PAR_B, C, H, W, True)["par"], G.rule_head_fwd(GC.PAR_B, C, H, W, True)["nrb"], G.rule_head_fwd(GC.PAR_B, C, H, W, True)["ns"])
+           for C in GC.PAR_C for H in GC.PAR_H for W in GC.PAR_W}
+    assert par == {(True, 1, 1), (True, 2, 1), (True, 1, 2), (True, 2, 2)}
+    for flow, cs in ((False, GC.DISP_BWD_C), (True, GC.FLOW_BWD_C)):
+        bwd = {tuple(G.rule_head_bwd(C, H, W, flow).values()) for C in cs for H in GC.BWD_H for W in GC.BWD_W}
+        assert bwd == {(ns, nrb, nz) for ns in (1, 2) for nrb in (1, 2) for nz in (1, 3)}
+
+
+# --------------------------------------------------------------------------------------------------------- decisions near zero
+def test_every_decision_of_the_matrices_keeps_its_margin():
+    """LeakyReLU / ReLU sign, ELU branch: by construction (the sum is an exactly representable t with |t| >= 2^-10 up to one
+    rounding); BN + ReLU: bn_case picks the seed; max pooling: the inputs sit on a grid of 1/8, so unequal candidates differ by
+    >= 1/8 and the comparison involves no arithmetic."""
+    for shape in GC.EP_SHAPES:
+        z, bias = G.epilogue_input(shape, sum(shape))
+        assert G.margin_ok(z.double() + bias.double()[None, :, None, None], G.bias_act_A(z, bias))
+    for H, W, apply_elu, with_bias in GC.elu_pad_cases():
+        x, bias = G.elu_input((GC.ELU_PAD_BC[0], GC.ELU_PAD_BC[1], H, W), with_bias, 100 * H + W)
+        assert G.margin_ok(x.double() + (bias.double()[None, :, None, None] if with_bias else 0.0), G.elu_A(x, bias))
+    for B, C1, h, w, C2 in GC.UP2_SHAPES:
+        for with_bias in (False, True):
+            x, bias = G.elu_input((B, C1, h, w), with_bias, h * w + C2)
+            assert G.margin_ok(x.double() + (bias.double()[None, :, None, None] if with_bias else 0.0), G.elu_A(x, bias))
+    for case in GC.bn_cases():
+        for with_res in (False, True):
+            c = G.bn_case(*case[:5], 1, with_res, G.bn_seed(case, with_res))
+            assert c["seed"] - G.bn_seed(case, with_res) < 40 and G.margin_ok(c["ref"]["pre"], c["ref"]["A_y"])
+    for shape in GC.POOL_SHAPES:
+        x = G.pool_input(*shape, torch.Generator().manual_seed(sum(shape)))
+        fin = x[torch.isfinite(x)]
+        assert bool((fin * 8 == torch.round(fin * 8)).all())

@@ -593,7 +593,8 @@ def test_elu_pad(shape, apply_elu, with_bias):
 
 
 @pytest.mark.parametrize("shape,c2", [((2, 3, 4, 6), 2), ((1, 2, 1, 1), 1), ((2, 5, 8, 26), 0), ((1, 16, 33, 65), 7),
-                                      ((2, 3, 19, 300), 0), ((1, 2, 5, 257), 1)])   # w >= 256: the rolling-window backward
+                                      ((2, 3, 19, 300), 0), ((1, 2, 5, 257), 1),    # w > 32: the 64-column LDS tiles of the backward
+                                      ((1, 2, 50, 196), 1)])                        # ... with one tile clear of the plane's ring
 def test_elu_up2_cat_pad(shape, c2):
     from unsupervised_depth_opticalflow_egomotion_amd import ops
     b, c1, h, w = shape
