@@ -79,7 +79,13 @@ long dfe_scatter_ws_bytes(long n);
  * x [B,C,H,W], flow [B,2,H,W] -> out [B,C,H,W].  Backward: gflow [B,2,H,W] (NULL to skip),
  * gx [B,C,H,W] (NULL to skip; every element written, no zero-fill needed) through the scatter workspace gx_ws
  * (dfe_scatter_ws_bytes(B*C*H*W) bytes; may be NULL when gx is);
- * gflow is written once per pixel from fixed-order partial sums.  Both are bitwise reproducible. */
+ * gflow is written once per pixel from fixed-order partial sums.  Both are bitwise reproducible.
+ * Memory contract: the forward reads x and flow and writes every element of out; the backward reads x, flow and gout and writes
+ * every element of the gradients requested, and gx_ws, whose contents are undefined on entry and on return (the library
+ * initialises what it uses).  gx_ws must be 16-byte aligned (DFE_ERR_DIMS otherwise); every other pointer needs dword alignment only.
+ * Where the gradient is gathered (C >= 8 and 512 <= H*W < 2^28) the lists of the gather are laid out inside the
+ * dfe_scatter_ws_bytes(B*C*H*W) bytes, which hold them because C >= 8.  The gather and the scatter
+ * (forced by DFE_WARP_SCATTER in the environment, read at every call) return the same bits. */
 int dfe_warp_flow_fwd(const float* x, const float* flow, float* out, int B, int C, int H, int W, int use_mask,
                       int align_corners, void* stream);
 int dfe_warp_flow_bwd(const float* x, const float* flow, const float* gout, float* gflow, float* gx, void* gx_ws, int B,
@@ -173,10 +179,24 @@ int dfe_ssim_bwd(const float* x, const float* y, const float* gout, float* gx, f
                  void* stream);
 
 /* ---- PWC_tf.corr_naive(input1, input2, d=4)  pwc_tf.py:97-106 ------------------------------
- * out [B,(2d+1)^2,H,W]; only d == 4 is implemented (DFE_ERR_UNSUPPORTED otherwise). */
+ * out [B,(2d+1)^2,H,W]; only d == 4 is implemented (DFE_ERR_UNSUPPORTED otherwise).
+ * Memory contract: the forward reads f1, f2 [B,C,H,W] and writes every element of out, nothing else; the backward reads f1, f2
+ * and gout [B,81,H,W] and writes every element of g1 and / or g2 [B,C,H,W] (either may be NULL, not both), nothing else.  No
+ * scratch, no initialisation of an output.  Every pointer needs dword alignment only: with W % 4 == 0 and every pointer on 16
+ * bytes the kernels use 16-byte accesses, otherwise dword ones, and both return the same bits. */
 int dfe_corr_fwd(const float* f1, const float* f2, float* out, int B, int C, int H, int W, int d, void* stream);
 int dfe_corr_bwd(const float* f1, const float* f2, const float* gout, float* g1, float* g2, int B, int C, int H, int W,
                  int d, void* stream);
+/* The launch plan the two entry points above (and the PWC level below) pick for a shape: host only, nothing is launched and no
+ * device is needed; the tuning overrides of the environment are honoured as the launchers honour them.  `vec`: non-zero when
+ * every pointer and batch stride of the call is 16-byte aligned; `sides`: gradients requested (1 or 2).  DFE_ERR_UNSUPPORTED
+ * where the launcher would refuse the shape.
+ *   forward, 12 ints: tile rows TH, tile quads TXQ, tiles across ntx, channel split KS, channels per chunk CC, displacement
+ *     rows per block DYG, staged f2 quads per thread PF2, threads, bytes of LDS, chunks, coarse (0 / 1), 16-byte kernel (0 / 1);
+ *   backward, 10 ints: TH, TXQ, ntx, channel groups per block NCG, channel ranges ncr, displacement-row split IS, threads,
+ *     bytes of LDS, staging batches, 16-byte kernel (0 / 1). */
+int dfe_corr_fwd_plan(int B, int C, int H, int W, int vec, int* plan);
+int dfe_corr_bwd_plan(int B, int C, int H, int W, int sides, int vec, int* plan);
 
 /* ---- ResNet stem max pooling  nn.MaxPool2d(3, 2, 1) of torchvision's resnet as ResnetEncoder runs it
  * (core/networks/structures/depth_model.py:60-95).  x [planes,H,W] -> y [planes,Ho,Wo], Ho = (H-1)/2+1; `idx` keeps the
@@ -193,7 +213,18 @@ int dfe_maxpool3x3s2_bwd(const float* gy, const unsigned char* idx, float* gx, i
  * the three channel slices of gx = dL/dx in place and returns complete gradients:
  *   g_c1 = dcorr/dc1 + gx[:,81:81+C];  g_flow = dwarp/dflow + gx[:,81+C:];  g_c2 (order-independent scatter through
  *   g_c2_ws, dfe_scatter_ws_bytes(B*C*H*W) bytes; every element of g_c2 is written).
- * g_warped [B,C,H,W] is scratch.  g_c2 (with g_c2_ws) or g_flow may be NULL (not both). */
+ * g_warped [B,C,H,W] is scratch.  g_c2 (with g_c2_ws) or g_flow may be NULL (not both).
+ * Memory contract: the forward reads c1, c2, flow and writes every element of warped [B,C,H,W] and of x (dense), nothing else;
+ * planes [81,81+C) and [81+C,81+C+2) of x are bit copies of c1 and flow.  The backward reads c1, c2, flow, warped and gx (dense,
+ * [B,81+C+2,H,W]) and writes every element of g_warped (dL/dwarped: scratch that needs no initialisation), g_c1 and of whichever
+ * of g_c2 / g_flow is given.  g_c2_ws (dfe_scatter_ws_bytes(B*C*H*W) bytes) and map (dfe_pwc_level_map_bytes bytes) need no
+ * initialisation; the library writes inside those sizes only.  16 bytes are required of map and of g_c2_ws (DFE_ERR_DIMS otherwise: the
+ * gather, taken where C >= 8 and 512 <= H*W < 2^28, lays its lists out inside g_c2_ws).  Every other pointer needs dword
+ * alignment only.  The forward uses 16-byte accesses when W % 4 == 0 and c1, warped, x and flow are all on 16 bytes; the backward
+ * when W % 4 == 0 and c1, warped, gx, g_warped and g_c1 are.  Otherwise both use dword accesses, with the same bits either way.
+ * Gather, scatter (DFE_WARP_SCATTER in the environment), the map built in one launch (H*W <= 1024) or in three
+ * (DFE_WFG_MAP_LARGE in the environment) and the plain / _map pairs all return the same bits; both switches are read at every
+ * call. */
 int dfe_pwc_level_channels(int C);   /* 81 + C + 2 */
 int dfe_pwc_level_fwd(const float* c1, const float* c2, const float* flow, float* warped, float* x, int B, int C, int H,
                       int W, int align_corners, void* stream);

@@ -1,5 +1,6 @@
 """Helpers of the guarded convolution tests (test_hip_conv_guarded.py, test_hip_conv_wgrad_guarded.py,
-test_hip_planeconv_guarded.py; self-tests in test_guarded_cpu.py).  Not a conftest: imported explicitly.
+test_hip_planeconv_guarded.py; self-tests in test_guarded_cpu.py), further down of the glue / head and of the PWC-level tests.
+Not a conftest: imported explicitly.
 
 ``Carved``: a tensor view inside one int32 buffer pre-filled with a NaN bit pattern, at a chosen float offset past a 16-byte
 boundary, with guard bands on both sides and (optionally) sentinel gaps between its samples: a stray store breaks
@@ -13,6 +14,7 @@ held to 4 x max(1, e of a plain fp32 implementation of the same algorithm on the
 maximum over a few thousand elements.  A dropped or misplaced product is ~A / (9 Ci): orders of magnitude above."""
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -656,3 +658,226 @@ def elu_input(shape, with_bias, seed):
 
 def bn_seed(case, with_res):
     return 1000 * sum(case[:5]) + 500 * int(with_res)
+
+
+# ========================================================================================================= PWC decoder level
+# Helpers of test_hip_corr_guarded.py, test_hip_warp_guarded.py and test_hip_pwc_level_guarded.py (cases: tests/pwc_cases.py):
+# the cost volume and its two gradients as direct sums (float64 reference, absolute sum, plain fp32 in channel / displacement
+# order), the feature warp from a numpy-float32 restatement of flow_coords and make_tap (csrc/dfe_device.h) whose weights are
+# then exact inputs of float64 sums, the bound of the fixed-point scatter, a device-side bit comparison and the three one-line
+# launch rules of csrc/ops_basic.hip.  The two tiling functions of csrc/ops_corr.hip are NOT restated: dfe_corr_fwd_plan /
+# dfe_corr_bwd_plan answer for them.
+CR_D, CR_K, CR_NK = 4, 9, 81
+FWD_PLAN = ("TH", "TXQ", "ntx", "KS", "CC", "DYG", "PF2", "threads", "lds", "chunks", "coarse", "vec")
+BWD_PLAN = ("TH", "TXQ", "ntx", "NCG", "ncr", "IS", "threads", "lds", "batches", "vec")
+FLOW_KINDS = ("smooth", "rough", "out", "zero", "collapse")
+
+
+def corr_plan(lib, shape, vec=1, sides=None):
+    """the launcher's own decision: dict of FWD_PLAN (sides None) or BWD_PLAN"""
+    import ctypes
+    names = FWD_PLAN if sides is None else BWD_PLAN
+    buf = (ctypes.c_int * len(names))()
+    rc = lib.dfe_corr_fwd_plan(*shape, int(vec), buf) if sides is None else lib.dfe_corr_bwd_plan(*shape, int(sides), int(vec), buf)
+    assert rc == 0, (shape, sides, rc)
+    return dict(zip(names, buf))
+
+
+def rule_corr_vec(W, offs, strides=()):
+    """launch_corr_fwd / launch_corr_bwd: every pointer looked at on 16 bytes, every batch stride a multiple of 4 floats"""
+    return W % 4 == 0 and all(_a16(o) for o in offs if o is not None) and all(s % 4 == 0 for s in strides)
+
+
+def rule_warp_bwd_groups(C, H, W):
+    """channel groups per block of k_warp_flow_bwd"""
+    return 16 if H * W < 2048 and C > 32 else 4
+
+
+def rule_wfg_eligible(C, HW):
+    """gx of the feature warp by the gather (otherwise by the 64-bit scatter)"""
+    return C >= 8 and 512 <= HW < 2 ** 28
+
+
+def rule_map_small(HW, forced_large=False):
+    """dfe_pwc_level_fwd_map: the map in one launch (otherwise count / scan / fill)"""
+    return HW <= 1024 and not forced_large
+
+
+def bits_equal_dev(a, b):
+    """bits_equal for two fp32 tensors of one device, compared there"""
+    return a.shape == b.shape and a.dtype == b.dtype == torch.float32 and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
+
+
+def make_flow(kind, B, H, W, gen):
+    """smooth (4x4 blocks of one vector, +-2 px), rough (+-4 px per pixel), out (sample 0 wholly out of view, the others +-30 px),
+    zero, collapse (every pixel sampled at one interior point, quarter-pixel offsets).  [B,2,H,W] fp32"""
+    if kind == "smooth":
+        c = torch.randn(B, 2, (H + 3) // 4, (W + 3) // 4, generator=gen) * 2.0
+        return c.repeat_interleave(4, 2).repeat_interleave(4, 3)[:, :, :H, :W].contiguous()
+    if kind == "rough":
+        return torch.randn(B, 2, H, W, generator=gen) * 4.0
+    if kind == "out":
+        f = torch.randn(B, 2, H, W, generator=gen) * 30.0
+        f[0, 0] += W + 40.0
+        return f
+    if kind == "zero":
+        return torch.zeros(B, 2, H, W)
+    assert kind == "collapse"
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    return torch.stack([W // 2 + 0.25 - xs, H // 2 + 0.25 - ys])[None].repeat(B, 1, 1, 1).contiguous()
+
+
+# --------------------------------------------------------------------------------------------------------- cost volume
+def corr_ref(f1, f2, dtype, absolute=False):
+    """out[b, i*9+j, y, x] = 1/C sum_c f1[b,c,y,x] f2[b,c,y+i-4,x+j-4]; float32: products and additions rounded one by one in
+    channel order, then one division; absolute: 1/C sum |f1||f2| in float64"""
+    B, C, H, W = f1.shape
+    a, b = (f1.double().abs(), f2.double().abs()) if absolute else (f1.to(dtype), f2.to(dtype))
+    dt = torch.float64 if absolute else dtype
+    bp = F.pad(b, (CR_D,) * 4)
+    out = torch.empty(B, CR_NK, H, W, dtype=dt)
+    for i in range(CR_K):
+        for j in range(CR_K):
+            win = bp[:, :, i:i + H, j:j + W]
+            if dt == torch.float64:
+                out[:, i * CR_K + j] = (a * win).sum(1)
+            else:
+                acc = torch.zeros(B, H, W, dtype=dt)
+                for c in range(C):
+                    acc += a[:, c] * win[:, c]
+                out[:, i * CR_K + j] = acc
+    return out / C
+
+
+def corr_bwd_ref(f1, f2, gout, dtype, absolute=False):
+    """(g1, g2): g1[b,c,p] = 1/C sum_k gout[b,k,p] f2[b,c,p+d_k]; g2[b,c,q] = 1/C sum_k gout[b,k,q-d_k] f1[b,c,q-d_k]; the sums run
+    in displacement order, every operation rounded in ``dtype``"""
+    B, C, H, W = f1.shape
+    if absolute:
+        f1, f2, gout, dtype = f1.abs(), f2.abs(), gout.abs(), torch.float64
+    a, g = f1.to(dtype), gout.to(dtype)
+    bp = F.pad(f2.to(dtype), (CR_D,) * 4)
+    g1, g2p = torch.zeros(B, C, H, W, dtype=dtype), torch.zeros(B, C, H + 2 * CR_D, W + 2 * CR_D, dtype=dtype)
+    for i in range(CR_K):
+        for j in range(CR_K):
+            gk = g[:, i * CR_K + j, None]
+            g1 += gk * bp[:, :, i:i + H, j:j + W]
+            g2p[:, :, i:i + H, j:j + W] += gk * a
+    return g1 / C, g2p[:, :, CR_D:CR_D + H, CR_D:CR_D + W] / C
+
+
+# --------------------------------------------------------------------------------------------------------- feature warp
+def warp_taps(flow, ac):
+    """flow_coords + make_tap (csrc/dfe_device.h) in numpy float32, operation by operation; the one FMA of unnormalize is
+    evaluated in float64 and rounded once.  flow [B,2,H,W] (torch fp32).  dict of numpy arrays [B,H*W] (lists: nw, ne, sw, se)"""
+    f32 = np.float32
+    fl = flow.numpy().astype(f32)
+    B, _, H, W = fl.shape
+
+    def coord(p, u, size):
+        g = (f32(2.0) * (p + u)) / f32(size - 1 if size > 1 else 1) - f32(1.0)
+        g1 = g + f32(1.0)
+        if ac:
+            return g1 * (f32(size - 1) / f32(2.0))
+        return (g1.astype(np.float64) * (size / 2.0) - 0.5).astype(f32)
+    ix = coord(np.arange(W, dtype=f32)[None, None, :], fl[:, 0], W).reshape(B, H * W)
+    iy = coord(np.arange(H, dtype=f32)[None, :, None], fl[:, 1], H).reshape(B, H * W)
+    assert ix.dtype == f32 and iy.dtype == f32
+    xw, yn = np.floor(ix), np.floor(iy)
+    w, n = ix - xw, iy - yn
+    e, s = f32(1.0) - w, f32(1.0) - n
+    wts = [s * e, s * w, n * e, n * w]
+    xin0, xin1 = (xw > -1) & (xw < W), (xw + 1 > -1) & (xw + 1 < W)
+    yin0, yin1 = (yn > -1) & (yn < H), (yn + 1 > -1) & (yn + 1 < H)
+    inb = [xin0 & yin0, xin1 & yin0, xin0 & yin1, xin1 & yin1]
+    x0, y0 = np.clip(xw, -2, W + 1).astype(np.int64), np.clip(yn, -2, H + 1).astype(np.int64)
+    cover = np.where(inb[0], wts[0], f32(0))
+    for k in (1, 2, 3):
+        cover = cover + np.where(inb[k], wts[k], f32(0))
+    assert cover.dtype == f32 and all(t.dtype == f32 for t in wts)
+    idx = [np.where(inb[k], (y0 + k // 2) * W + x0 + k % 2, 0) for k in range(4)]
+    return dict(w=wts, inb=inb, idx=idx, wx=w, wy=n, e=e, s=s, cover=cover, H=H, W=W)
+
+
+def _keep(taps, use_mask):
+    return torch.from_numpy((taps["cover"] >= np.float32(0.9999)).astype(np.float64) if use_mask else np.ones_like(taps["cover"], dtype=np.float64))
+
+
+def _corners(x, taps, dtype):
+    """the four corner values of every sample, zero outside the image: list of [B,C,HW]"""
+    B, C, H, W = x.shape
+    flat = x.to(dtype).reshape(B, C, H * W)
+    out = []
+    for k in range(4):
+        idx = torch.from_numpy(taps["idx"][k])[:, None, :].expand(B, C, H * W)
+        out.append(flat.gather(2, idx) * torch.from_numpy(taps["inb"][k])[:, None, :].to(dtype))
+    return out
+
+
+def _t(a, dtype):
+    return torch.from_numpy(a)[:, None, :].to(dtype)
+
+
+def warp_fwd_ref(x, taps, use_mask, dtype, absolute=False):
+    """sum of the four corner values times their (exact fp32) weights, in the kernel's order nw, ne, sw, se; [B,C,H,W]"""
+    dt = torch.float64 if absolute else dtype
+    v = _corners(x.abs() if absolute else x, taps, dt)
+    r = v[0] * _t(taps["w"][0], dt)
+    for k in (1, 2, 3):
+        r = r + v[k] * _t(taps["w"][k], dt)
+    return (r * _keep(taps, use_mask)[:, None, :].to(dt)).reshape(x.shape)
+
+
+def warp_gflow_ref(x, taps, gout, use_mask, ac, add, dtype, absolute=False):
+    """gflow [B,2,H,W] = (sum_c g_c d interp_c / d(ix, iy)) * d(ix, iy)/d(u, v) + add; channel order, every operation rounded in
+    ``dtype``; absolute: with |g|, |corner| + |corner| for every difference and |add|"""
+    B, C, H, W = x.shape
+    dt = torch.float64 if absolute else dtype
+    v = _corners(x.abs() if absolute else x, taps, dt)
+    g = (gout.abs() if absolute else gout).to(dt).reshape(B, C, H * W) * _keep(taps, use_mask)[:, None, :].to(dt)
+    s, e, wx, wy = (_t(taps[k], dt) for k in ("s", "e", "wx", "wy"))
+    sg = 1.0 if absolute else -1.0
+    dx = (v[1] + sg * v[0]) * s + (v[3] + sg * v[2]) * wy
+    dy = (v[2] + sg * v[0]) * e + (v[3] + sg * v[1]) * wx
+    gix, giy = torch.zeros(B, H * W, dtype=dt), torch.zeros(B, H * W, dtype=dt)
+    for c in range(C):
+        gix = gix + g[:, c] * dx[:, c]
+        giy = giy + g[:, c] * dy[:, c]
+
+    def scale(size):
+        den = np.float32(size - 1 if size > 1 else 1)
+        return float(np.float32(size - 1) / den if ac else np.float32(size) / den)
+    out = torch.stack([gix * scale(W), giy * scale(H)], 1).reshape(B, 2, H, W)
+    if add is not None:
+        out = out + (add.abs() if absolute else add).to(dt)
+    return out
+
+
+def warp_gx_ref(taps, gout, use_mask):
+    """the adjoint wrt the sampled tensor as a float64 scatter of the contributions g * w (weights exact): (ref64, mass = the same
+    with |g|, taps = contributions per target element), each [B,C,H,W] / [B,1,H,W]"""
+    B, C, H, W = gout.shape
+    g = gout.double().reshape(B, C, H * W) * _keep(taps, use_mask)[:, None, :]
+    ref, mass, cnt = torch.zeros(B, C, H * W, dtype=torch.float64), torch.zeros(B, C, H * W, dtype=torch.float64), torch.zeros(B, 1, H * W, dtype=torch.float64)
+    live = _keep(taps, use_mask)
+    for k in range(4):
+        w = torch.from_numpy(taps["w"][k]).double() * torch.from_numpy(taps["inb"][k]).double()
+        idx = torch.from_numpy(taps["idx"][k])
+        for b in range(B):
+            ref[b].index_add_(1, idx[b], g[b] * w[b])
+            mass[b].index_add_(1, idx[b], g[b].abs() * w[b])
+            cnt[b].index_add_(1, idx[b], ((w[b] != 0).double() * live[b])[None])
+    return ref.reshape(B, C, H, W), mass.reshape(B, C, H, W), cnt.reshape(B, 1, H, W)
+
+
+def check_scatter_bound(tag, out, ref64, mass, cnt, gmax):
+    """|out - ref64| <= 2^-24 mass + 1/2 quantum taps + 2^-24 |ref64| (one fp32 product per contribution, its rounding to the
+    fixed-point grid, the final conversion); quantum = 2^(k - 36) with gmax = m 2^k, m in [0.5, 1)"""
+    assert bool(torch.isfinite(out).all()), tag
+    quantum = 2.0 ** (math.frexp(float(gmax))[1] - 36) if gmax > 0 else 0.0
+    bound = U24 * mass + 0.5 * quantum * cnt + U24 * ref64.abs()
+    err = (out.double().cpu() - ref64).abs()
+    worst = float((err / bound.clamp_min(1e-300))[bound > 0].max()) if bool((bound > 0).any()) else 0.0
+    print("EBOUND %s scatter err/bound %.3f" % (tag, worst))
+    assert bool((err <= bound).all()), (tag, worst)
+    return worst

@@ -3,8 +3,11 @@ batch gap (and nothing else), and the plain-torch Winograd emulations that serve
 aten's float64 convolution / weight gradient computes."""
 import pytest
 import torch
+import torch.nn.functional as F
 
+from tests import glue_cases as GC
 from tests import guarded as G
+from tests import pwc_cases as PC
 
 CPU = torch.device("cpu")
 
@@ -100,9 +103,6 @@ def test_winograd_wgrad_emulation_in_float64_is_atens_weight_gradient(shape, fam
 # Self-tests of what test_hip_glue_guarded.py and test_hip_head_guarded.py rely on: the byte carve, the float64 references
 # against ATen's float64 operators, the restated launch rules on the shapes of the matrices (tests/glue_cases.py), that every
 # matrix reaches every branch of its launcher, and the margin of every thresholded decision.
-import torch.nn.functional as F
-
-from tests import glue_cases as GC
 
 
 @pytest.mark.parametrize("off", [0, 1, 5, 15])
@@ -370,3 +370,195 @@ def test_every_decision_of_the_matrices_keeps_its_margin():
         x = G.pool_input(*shape, torch.Generator().manual_seed(sum(shape)))
         fin = x[torch.isfinite(x)]
         assert bool((fin * 8 == torch.round(fin * 8)).all())
+
+
+# ========================================================================================================= PWC level
+# The case matrices of tests/pwc_cases.py against the library's own plan queries (host only: no device is touched) and the three
+# restated one-line rules; the float64 references of tests/guarded.py against the oracle.
+def _hip_lib():
+    from unsupervised_depth_opticalflow_egomotion_amd import _lib as L
+    return L.get_lib()
+
+
+def _has(plan, want):
+    return all(plan[k] == v for k, v in want.items())
+
+
+def test_plan_queries_agree_with_hand_computed_plans(monkeypatch):
+    """corr_fwd_config / corr_bwd_config worked by hand from csrc/ops_corr.hip (the workload's levels 2 and 3 at the batch of
+    training, and three ragged shapes)"""
+    for name in ("DFE_CORR_FWD", "DFE_CORR_BWD", "DFE_CORR_DYG"):
+        monkeypatch.delenv(name, raising=False)
+    lib = _hip_lib()
+    # level 2: 52 quads -> 4 tiles of 13; TH 4 keeps 8*16*4 = 512 tiles; NI = 4*13*9 = 468 -> 512 threads; 512 blocks * 512 = 256 K: fine;
+    # chunks of 8 channels (9 fit 36 KB); 2 * 8 * (12*15 + 4*13) * 16 bytes
+    assert G.corr_plan(lib, (8, 32, 64, 208)) == dict(TH=4, TXQ=13, ntx=4, KS=1, CC=8, DYG=9, PF2=4, threads=512, lds=59392, chunks=4, coarse=0, vec=1)
+    # its backward: 4 groups * 8 ch * 16 * 15 quads * 16 B = 120 KB; 8*8*4 blocks * 2 sides = 512; NI = 416 -> 448 threads; 7680 quads / (12*448)
+    assert G.corr_plan(lib, (8, 32, 64, 208), sides=2) == dict(TH=8, TXQ=13, ntx=4, NCG=4, ncr=1, IS=1, threads=448, lds=122880, batches=2, vec=1)
+    # level 3: 8 groups; NCG 2 is the largest that keeps 8*4*2*4 * 2 = 512 blocks: 60 KB, NI = 208 -> 256 threads
+    assert G.corr_plan(lib, (8, 64, 32, 104), sides=2) == dict(TH=8, TXQ=13, ntx=2, NCG=2, ncr=4, IS=1, threads=256, lds=61440, batches=2, vec=1)
+    # one pixel: TH 1, 3 displacement rows per block, NI = 3, the split is capped by C = 1; 2 * (3*3 + 1) * 16 bytes
+    assert G.corr_plan(lib, (1, 1, 1, 1), vec=0) == dict(TH=1, TXQ=1, ntx=1, KS=1, CC=1, DYG=3, PF2=4, threads=64, lds=320, chunks=1, coarse=1, vec=0)
+    # NI = 1*9*3 = 27 -> 18 slots, capped by C = 17: 459 work items; the reduction's 17*36*27*4 bytes exceed the staging buffers
+    assert G.corr_plan(lib, (3, 17, 9, 33), vec=0) == dict(TH=1, TXQ=9, ntx=1, KS=17, CC=17, DYG=3, PF2=4, threads=512, lds=66096, chunks=1, coarse=1, vec=0)
+    # the 16-byte kernels need W % 4 == 0 whatever the pointers are; a one-sided launch is planned on its own
+    assert G.corr_plan(lib, (8, 13, 62, 206), vec=1)["vec"] == 0 and G.corr_plan(lib, (8, 13, 64, 208), vec=0)["vec"] == 0
+    assert G.corr_plan(lib, (8, 32, 64, 208), sides=1)["NCG"] == 3
+    import ctypes
+    buf = (ctypes.c_int * 12)()
+    assert lib.dfe_corr_fwd_plan(0, 1, 1, 1, 1, buf) == -2 and lib.dfe_corr_fwd_plan(1, 1, 1, 1, 1, None) == -1
+    assert lib.dfe_corr_bwd_plan(1, 1, 1, 1, 3, 1, buf) == -2 and lib.dfe_corr_bwd_plan(1, 1, 1, 1, 1, 1, None) == -1
+
+
+def test_the_cases_reach_every_plan_of_the_cost_volume(monkeypatch):
+    for name in ("DFE_CORR_FWD", "DFE_CORR_BWD", "DFE_CORR_DYG"):
+        monkeypatch.delenv(name, raising=False)
+    lib = _hip_lib()
+    fwd = []
+    for shape, family, want in PC.CORR_FWD:
+        plan = G.corr_plan(lib, shape, vec=1)
+        assert _has(plan, want), (shape, plan, want)
+        assert family in G.FAMILIES
+        fwd.append((shape, plan))
+    assert any(p["coarse"] == 0 and p["vec"] == 1 and p["chunks"] == 2 and s[1] % p["CC"] == p["CC"] - 1 for s, p in fwd)          # fine, 16 bytes, a short last chunk
+    assert any(p["coarse"] == 0 and p["vec"] == 0 and s[2] % p["TH"] == 2 and s[3] % 4 == 2 for s, p in fwd)                          # fine, dwords, cut tile and quad
+    assert any(p["coarse"] == 1 and p["PF2"] == 10 for s, p in fwd)
+    assert any(p["KS"] > 1 and s[1] % p["CC"] and (s[1] % p["CC"]) < p["KS"] for s, p in fwd)                                        # empty slots in the last chunk
+    assert any(p["KS"] == s[1] and s[1] > 1 for s, p in fwd)
+    assert {min(p["chunks"], 3) for s, p in fwd} == {1, 2, 3} and any(p["chunks"] >= 3 and p["coarse"] == 0 for s, p in fwd)
+    assert any(p["ntx"] > 1 for s, p in fwd) and {p["PF2"] for s, p in fwd} == {4, 10} and {p["DYG"] for s, p in fwd} == {3, 9}
+    assert any(p["lds"] > 65536 for s, p in fwd)
+    assert {(1, 1, 1, 1), (2, 3, 2, 3)} <= {s for s, p in fwd}
+    # training's own forward plan at level 2 differs from these only in the channel count
+    t = G.corr_plan(lib, (8, 32, 64, 208))
+    assert any(all(p[k] == t[k] for k in ("TH", "TXQ", "ntx", "KS", "DYG", "PF2", "threads", "coarse", "vec")) for s, p in fwd)
+    both, one = [], []
+    for shape, family, want2, want1 in PC.CORR_BWD:
+        p2, p1 = G.corr_plan(lib, shape, sides=2), G.corr_plan(lib, shape, sides=1)
+        assert _has(p2, want2) and _has(p1, want1), (shape, p2, p1)
+        both.append((shape, p2))
+        one.append((shape, p1))
+    every = both + one
+    assert {p["IS"] for s, p in both} == {1, 3, 9} and {p["IS"] for s, p in one} >= {1, 9}
+    assert {p["NCG"] for s, p in every} >= {1, 2, 3}
+    assert any(p["NCG"] == 3 and p["lds"] > 65536 and s[1] % 8 for s, p in both) and any(p["NCG"] == 2 and s[1] % 8 and p["IS"] == 1 for s, p in every)
+    assert {p["vec"] for s, p in both if p["NCG"] == 2 and p["lds"] > 65536 and s[1] % 8} == {0, 1}                # NCG 2 above 64 KB, on either kernel
+    assert any(p["batches"] == 3 for s, p in one) and any(p["ncr"] * p["NCG"] > -(-s[1] // 8) for s, p in both)       # a last channel range that is not full
+    assert any(p["threads"] & (p["threads"] - 1) for s, p in both)                           # a thread count that is no power of two
+    assert any(p["ncr"] > 1 for s, p in both) and any(p["batches"] == 2 for s, p in both) and any(p["batches"] == 1 for s, p in both)
+    assert {p["vec"] for s, p in both} == {0, 1} and any(p["NCG"] == 3 and p["vec"] == v for v in (0, 1) for s, p in both)
+    assert any(p1 != p2 for (_, p1), (_, p2) in zip(one, both))                              # a one-sided launch picks another plan
+    # the alignment shapes are the two fine plans; at W % 4 == 0 one pointer off flips the launcher's rule
+    assert [s for s, _, w in PC.CORR_FWD if w.get("coarse") == 0][:2] == PC.ALIGN_SHAPES
+    for k in range(3):
+        assert not G.rule_corr_vec(208, [int(i == k) for i in range(3)]) and G.rule_corr_vec(208, [0, 0, 0], [81 * 64 * 208])
+    assert not G.rule_corr_vec(206, [0, 0, 0]) and not G.rule_corr_vec(208, [0, 0], [2])
+    assert set(PC.LEVEL_FWD_VEC_PTRS) < set(PC.LEVEL_FWD_PTRS) and set(PC.LEVEL_BWD_VEC_PTRS) < set(PC.LEVEL_BWD_PTRS)
+
+
+def test_the_cases_reach_every_branch_of_the_warp_and_the_level():
+    lib = _hip_lib()
+    assert G.rule_warp_bwd_groups(40, 6, 11) == 16 and G.rule_warp_bwd_groups(32, 6, 11) == 4 and G.rule_warp_bwd_groups(40, 32, 64) == 4 and G.rule_warp_bwd_groups(40, 31, 66) == 16
+    assert G.rule_wfg_eligible(8, 512) and not G.rule_wfg_eligible(7, 512) and not G.rule_wfg_eligible(8, 511)
+    assert G.rule_map_small(1024) and not G.rule_map_small(1025) and not G.rule_map_small(512, True)
+    warp = [s for s, _ in PC.WARP]
+    assert {s[1] for s in warp} == {5, 8, 40, 136} and dict(PC.WARP)[(2, 40, 6, 11)] in ("rough", "smooth") and any(G.rule_warp_bwd_groups(*s[1:]) == 16 and s[1] > 16 * 8 for s in warp) and {k for _, k in PC.WARP} | {k for *_, k in PC.LEVEL} == set(G.FLOW_KINDS)
+    assert any(s[2] * s[3] < 64 for s in warp) and any(s[2] * s[3] % 64 and s[2] * s[3] > 64 for s in warp) and any(s[2] * s[3] >= 2048 for s in warp)
+    assert {G.rule_warp_bwd_groups(*s[1:]) for s in warp} == {4, 16} and G.rule_warp_bwd_groups(40, 32, 65) == 4
+    assert {G.rule_wfg_eligible(s[1], s[2] * s[3]) for s in warp} == {True, False}
+    level = [s for s, _, _ in PC.LEVEL]
+    elig = {(s[1], s[2] * s[3]): G.rule_wfg_eligible(s[1], s[2] * s[3]) for s in level}
+    assert elig[(7, 510)] is False and elig[(8, 510)] is False and elig[(7, 512)] is False and elig[(8, 512)] is True
+    small = {s[2] * s[3]: G.rule_map_small(s[2] * s[3]) for s in level if s[1] >= 8}
+    assert small[1024] is True and small[1056] is False and small[13312] is False
+    assert all(G.rule_wfg_eligible(s[1], s[2] * s[3]) for s in PC.LEVEL_SCATTER_ENV) and all(G.rule_map_small(s[2] * s[3]) for s in PC.LEVEL_MAP_LARGE_ENV)
+    assert set(PC.LEVEL_SCATTER_ENV) | set(PC.LEVEL_MAP_LARGE_ENV) <= set(level) and set(PC.ALIGN_SHAPES) <= set(level)
+    assert {f for _, f, _ in PC.LEVEL} == set(G.FAMILIES)
+    assert PC.PILE_TAPS == PC.PILE[2] * PC.PILE[3] > 65536 and G.rule_wfg_eligible(PC.PILE[1], PC.PILE_TAPS)
+    # the gather lays header | counters | offsets | entries out inside the scatter's workspace: the same layout as the map's, so
+    # dfe_pwc_level_map_bytes is its end.  It fits because C >= 8.
+    for s in level + warp + [PC.PILE, (1, 8, 1, 512), (65535, 8, 16, 32), (3, 8, 511, 513)]:
+        if G.rule_wfg_eligible(s[1], s[2] * s[3]):
+            assert lib.dfe_pwc_level_map_bytes(s[0], s[2], s[3]) <= lib.dfe_scatter_ws_bytes(s[0] * s[1] * s[2] * s[3]), s
+    assert lib.dfe_pwc_level_map_bytes(2, 16, 32) > lib.dfe_scatter_ws_bytes(2 * 4 * 16 * 32)          # ... and would not at C = 4
+
+
+def test_pile_up_flow_puts_more_than_2_16_taps_on_four_targets():
+    B, C, H, W = PC.PILE
+    taps = G.warp_taps(G.make_flow("collapse", B, H, W, None), 0)
+    _, _, cnt = G.warp_gx_ref(taps, torch.ones(B, 1, H, W), 0)
+    assert sorted(cnt.flatten().tolist())[-5:] == [0.0] + [float(PC.PILE_TAPS)] * 4
+    ys, xs = divmod(int(cnt.flatten().argmax()), W)
+    assert 0 < ys < H - 2 and 0 < xs < W - 2                                                           # an interior point
+
+
+@pytest.mark.parametrize("ac", [0, 1])
+def test_warp_restatement_is_the_oracles_warp(ac):
+    """the numpy-float32 taps against oracle.warp_flow at the operator tests' tolerance (values 2e-6, the same zeros under the
+    mask); the float64 sums over them against the oracle's autograd in float64"""
+    from oracle import loss_stack_oracle as O
+    gen = torch.Generator().manual_seed(5 + ac)
+    for (B, C, H, W), kind in [((2, 5, 7, 9), "rough"), ((1, 8, 5, 26), "smooth"), ((2, 3, 6, 11), "out"), ((1, 2, 12, 20), "collapse"), ((1, 2, 4, 5), "zero")]:
+        x, flow = torch.rand(B, C, H, W, generator=gen), G.make_flow(kind, B, H, W, gen)
+        gout = torch.randn(B, C, H, W, generator=gen)
+        taps = G.warp_taps(flow, ac)
+        for um in (0, 1):
+            yo = O.warp_flow(x, flow, use_mask=bool(um), align_corners=bool(ac))
+            mine = G.warp_fwd_ref(x, taps, um, torch.float32)
+            assert float((mine - yo).abs().max()) <= 2e-6 and torch.equal(mine == 0, yo == 0), (kind, um)
+            A = G.warp_fwd_ref(x, taps, um, torch.float64, absolute=True)
+            assert bool((G.warp_fwd_ref(x, taps, um, torch.float64).abs() <= A * (1 + 1e-12)).all())
+        xd, fd = x.double().requires_grad_(True), flow.double().requires_grad_(True)
+        O.warp_flow(xd, fd, use_mask=False, align_corners=bool(ac)).backward(gout.double())
+        gf = G.warp_gflow_ref(x, taps, gout, 0, ac, None, torch.float64)
+        ref, mass, cnt = G.warp_gx_ref(taps, gout, 0)
+        # float64 coordinates differ from the fp32 ones by ~1e-6 px: the gradients by that times the image's slope
+        assert float((gf - fd.grad).abs().max()) <= 1e-4 * max(1.0, float(fd.grad.abs().max())), kind
+        assert float((ref - xd.grad).abs().max()) <= 1e-4 * max(1.0, float(xd.grad.abs().max())), kind
+        assert bool((mass >= ref.abs() * (1 - 1e-12)).all()) and float(cnt.max()) <= 4 * H * W
+
+
+def test_cost_volume_references_are_the_oracles_corr_naive():
+    from oracle import loss_stack_oracle as O
+    gen = torch.Generator().manual_seed(9)
+    for shape in [(2, 3, 2, 3), (1, 5, 6, 11), (1, 1, 1, 1)]:
+        B, C, H, W = shape
+        f1, f2 = G.make_input(shape, "randn", gen), G.make_input(shape, "randn", gen)
+        gout = torch.randn(B, 81, H, W, generator=gen)
+        a, b = f1.double().requires_grad_(True), f2.double().requires_grad_(True)
+        out = O.corr_naive(a, b)
+        out.backward(gout.double())
+        A = G.corr_ref(f1, f2, torch.float64, absolute=True)
+        assert _close64(G.corr_ref(f1, f2, torch.float64), out.detach(), A)
+        g1, g2 = G.corr_bwd_ref(f1, f2, gout, torch.float64)
+        A1, A2 = G.corr_bwd_ref(f1, f2, gout, torch.float64, absolute=True)
+        assert _close64(g1, a.grad, A1) and _close64(g2, b.grad, A2)
+        y1, y2 = G.corr_bwd_ref(f1, f2, gout, torch.float32)
+        assert y1.dtype == torch.float32 and float((y1.double() - g1).abs().max()) < 1e-5 and float((y2.double() - g2).abs().max()) < 1e-5
+        assert float((G.corr_ref(f1, f2, torch.float32).double() - out.detach()).abs().max()) < 1e-5
+
+
+def test_the_level_bounds_notice_one_dropped_term():
+    """one product missing from one cost-volume sum, one tap missing from one scattered element: both bounds refuse"""
+    gen = torch.Generator().manual_seed(4)
+    shape = (1, 13, 6, 10)
+    f1, f2 = G.make_input(shape, "act", gen), G.make_input(shape, "act", gen)
+    y32, r64, A = G.corr_ref(f1, f2, torch.float32), G.corr_ref(f1, f2, torch.float64), G.corr_ref(f1, f2, torch.float64, absolute=True)
+    G.check_bound("yardstick against itself", y32, y32, r64, A)
+    bad = y32.clone()
+    bad[0, 40, 2, 3] -= f1[0, 12, 2, 3] * f2[0, 12, 2, 3] / 13          # displacement (0, 0), the last channel
+    with pytest.raises(AssertionError):
+        G.check_bound("a dropped product", bad, y32, r64, A)
+    flow, gout = G.make_flow("rough", 1, 6, 10, gen), torch.randn(shape, generator=gen)
+    taps = G.warp_taps(flow, 0)
+    ref, mass, cnt = G.warp_gx_ref(taps, gout, 0)
+    gmax = float(gout.abs().max())
+    G.check_scatter_bound("float64 against itself", ref.float(), ref, mass, cnt, gmax)
+    g5 = gout.reshape(1, 13, 60)[0, 5]
+    p = int((torch.from_numpy(taps["inb"][0])[0] * torch.from_numpy(taps["w"][0])[0] * g5.abs()).argmax())    # the heaviest north-west tap
+    q = int(taps["idx"][0][0, p])
+    bad = ref.clone().reshape(1, 13, 60)
+    bad[0, 5, q] -= float(g5[p]) * float(taps["w"][0][0, p])
+    assert abs(float(g5[p])) * float(taps["w"][0][0, p]) > 0.1
+    with pytest.raises(AssertionError):
+        G.check_scatter_bound("a dropped tap", bad.reshape(shape).float(), ref, mass, cnt, gmax)

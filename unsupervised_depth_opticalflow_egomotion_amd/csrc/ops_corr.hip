@@ -499,7 +499,7 @@ inline void tile_width(int W, int& TXQ, int& ntx) {
   TXQ = (WQ + ntx - 1) / ntx;
 }
 
-bool corr_fwd_config(int B, int C, int H, int W, CorrFwdCfg& g, int& NT, size_t& lds, int& pf2) {
+bool corr_fwd_config(int B, int C, int H, int W, CorrFwdCfg& g, int& NT, size_t& lds, int& pf2, bool* is_coarse = nullptr) {
   int TXQ, ntx;
   tile_width(W, TXQ, ntx);
   // rows per tile: 4 where that still gives every CU a block, fewer on the small levels (measured per PWC level:
@@ -526,6 +526,7 @@ bool corr_fwd_config(int B, int C, int H, int W, CorrFwdCfg& g, int& NT, size_t&
   // 2 x 36 KB of LDS; coarse levels: as few chunks as 10 staged quads per thread and 2 x 72 KB of LDS allow -- every
   // chunk is a global-memory round trip that the little arithmetic of a small level cannot hide
   const bool coarse = blocks * NT < 256l * 1024;
+  if (is_coarse) *is_coarse = coarse;
   auto fits = [&](int cc, int pf, long cap) {
     return static_cast<long>(cc) * P2 <= static_cast<long>(pf) * NT && static_cast<long>(cc) * P1 <= static_cast<long>(CF_PF1) * NT &&
            static_cast<long>(cc) * (P2 + P1) * 16 <= cap;
@@ -596,18 +597,20 @@ bool corr_bwd_config(int B, int C, int H, int W, int sides, CorrBwdCfg& g, int& 
   return lds <= CORR_MAX_LDS;
 }
 
-// more than 64 KB of dynamic LDS has to be allowed per kernel, once per process (one device per process)
-template <typename K>
-inline bool allow_lds(K kernel, size_t lds) {
+// more than 64 KB of dynamic LDS has to be allowed per kernel, once per process (one device per process).
+// KERNEL is the kernel itself, not its type: every instantiation of a kernel template has the same function type, and a
+// flag per type would be set by whichever instantiation asked first and skip the call for the others.
+template <auto KERNEL>
+inline bool allow_lds(size_t lds) {
   if (lds <= 64 * 1024) return true;
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CORR_MAX_LDS) == hipSuccess;
+  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, CORR_MAX_LDS) == hipSuccess;
   return ok;
 }
 
 template <bool VEC, int PF2, int WPE>
 inline int run_corr_fwd(const float* f1, const float* f2, float* out, long obs, float* tail, const float* flow, int B, int C, int H, int W,
                         const CorrFwdCfg& g, int NT, size_t lds, hipStream_t st) {
-  if (!allow_lds(k_corr_fwd_lds<VEC, PF2, WPE>, lds)) return DFE_ERR_LAUNCH;
+  if (!allow_lds<k_corr_fwd_lds<VEC, PF2, WPE>>(lds)) return DFE_ERR_LAUNCH;
   const float fC = static_cast<float>(C), rC = 1.0f / fC;
   k_corr_fwd_lds<VEC, PF2, WPE><<<static_cast<unsigned>(B) * g.nty * g.ntx * g.ndyg, NT, lds, st>>>(f1, f2, out, obs, tail, flow, C, H, W, fC, rC, g);
   return DFE_OK;
@@ -645,13 +648,44 @@ int launch_corr_bwd(const float* f1, const float* f2, const float* gout, long gb
   const int mode0 = g1 ? 0 : 1;
   const dim3 grid(static_cast<unsigned>(B) * g.nty * g.ntx * g.ncr, (g1 && g2) ? 2 : 1);
   if (vec) {
-    if (!allow_lds(k_corr_bwd_lds<true>, lds)) return DFE_ERR_LAUNCH;
+    if (!allow_lds<k_corr_bwd_lds<true>>(lds)) return DFE_ERR_LAUNCH;
     k_corr_bwd_lds<true><<<grid, NT, lds, st>>>(s0, s1, mode0, gout, gbs, C, H, W, fC, rC, g);
   } else {
-    if (!allow_lds(k_corr_bwd_lds<false>, lds)) return DFE_ERR_LAUNCH;
+    if (!allow_lds<k_corr_bwd_lds<false>>(lds)) return DFE_ERR_LAUNCH;
     k_corr_bwd_lds<false><<<grid, NT, lds, st>>>(s0, s1, mode0, gout, gbs, C, H, W, fC, rC, g);
   }
   return DFE_OK;
 }
 
 }  // namespace dfe
+
+// ------------------------------------------------------------------------------------------------ plan queries (host only)
+// What launch_corr_fwd / launch_corr_bwd decide for a shape, from the same two functions and the same environment overrides;
+// nothing is launched and no device is touched.  `vec`: whether every pointer and batch stride of the call is 16-byte aligned
+// (the launchers' al16 / % 4 tests); the kernels are the VEC ones only when W % 4 == 0 as well, which the last field reports.
+extern "C" int dfe_corr_fwd_plan(int B, int C, int H, int W, int vec, int* plan) {
+  if (!plan) return DFE_ERR_NULL;
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return DFE_ERR_DIMS;
+  dfe::CorrFwdCfg g;
+  int NT, pf2;
+  size_t lds;
+  bool coarse;
+  if (!dfe::corr_fwd_config(B, C, H, W, g, NT, lds, pf2, &coarse)) return DFE_ERR_UNSUPPORTED;
+  const int v[12] = {g.TH, g.TXQ, g.ntx, g.KS, g.CC, g.DYG, pf2, NT, static_cast<int>(lds), (C + g.CC - 1) / g.CC, coarse ? 1 : 0,
+                     (vec && W % 4 == 0) ? 1 : 0};
+  for (int i = 0; i < 12; ++i) plan[i] = v[i];
+  return DFE_OK;
+}
+
+extern "C" int dfe_corr_bwd_plan(int B, int C, int H, int W, int sides, int vec, int* plan) {
+  if (!plan) return DFE_ERR_NULL;
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || sides < 1 || sides > 2) return DFE_ERR_DIMS;
+  dfe::CorrBwdCfg g;
+  int NT;
+  size_t lds;
+  if (!dfe::corr_bwd_config(B, C, H, W, sides, g, NT, lds)) return DFE_ERR_UNSUPPORTED;
+  const int per = dfe::CB_STAGE * NT;
+  const int v[10] = {g.TH, g.TXQ, g.ntx, g.NCG, g.ncr, g.IS, NT, static_cast<int>(lds), (g.tile_quads + per - 1) / per, (vec && W % 4 == 0) ? 1 : 0};
+  for (int i = 0; i < 10; ++i) plan[i] = v[i];
+  return DFE_OK;
+}
