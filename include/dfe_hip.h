@@ -522,15 +522,54 @@ typedef struct dfe_geom_args {
                                 lines of Model_depth, model_depth.py:326-327,332-333: mask = validity x texture, the
                                 consistency term unmasked).  With
                                 DFE_DEPTH_TERM_CONSIS the SOURCE disparities grad_disp[0], grad_disp[2] also receive the
-                                gradient of the projected depth (a bilinear scatter: float atomics, reproducible to
-                                rounding only); everything else stays bitwise reproducible. */
+                                gradient of the projected depth: a bilinear scatter in 64-bit fixed point (integer
+                                atomics, csrc/dfe_scatter.h), so these gradients are bitwise reproducible like all others. */
 } dfe_geom_args;
 
+/* Memory contract of dfe_geom_loss_fwd / dfe_geom_loss_bwd.  The forward reads the frames, the disparities (modes 0, 1), the
+ * flows (modes 0, 2), pose and K (modes 0, 1), K_inv (mode 0); it writes every element of losses [DFE_NUM_LOSSES][B] (all ten
+ * rows in every mode; only the rows of the mode's terms carry meaning) and the workspace, nothing else.  The backward reads the
+ * same inputs, grad_losses and the workspace; it writes every element of each gradient that is not NULL and the workspace,
+ * nothing else.  A NULL gradient is skipped -- no kernel stores through it -- and the others keep their bits.  Inputs are
+ * never written.
+ * workspace: dfe_geom_workspace_floats(args) floats (the size depends on B, H, W, num_scales, mode, depth_terms and on
+ * DFE_ADJ_MODE in the environment, not on any pointer); nothing outside them is touched; a smaller workspace_floats is
+ * DFE_ERR_WORKSPACE before any launch.  Contents are undefined on entry to the forward: every region is written before it is
+ * read, so one workspace may serve calls of other shapes, modes and depth_terms one after another.  The backward relies on
+ * what the forward of the SAME arguments left there -- cameras and epipolar blocks, pyramid levels >= 1, the mask pack
+ * (modes 0, 1; mode 2 leaves it unwritten), the masked warped images and rigid reconstructions, the soft weights of mode 2,
+ * the normalisers -- and leaves all of that unchanged: it writes its own scratch regions only, so it may run more than once on
+ * one forward and the mask pack may be decoded after it.
+ * Alignment: workspace on 16 bytes (DFE_ERR_DIMS otherwise, from both entry points, before any launch: every region starts a
+ * multiple of 16 bytes into it, the pyramid levels are stored in pairs and the depth-consistency term keeps a scatter
+ * workspace of 64-bit accumulators there, csrc/dfe_scatter.h); every other pointer needs dword alignment only.  With
+ * H % 4 == 0, W % 4 == 0, num_scales >= 3, mode 0 or 1 and all three frames on 16 bytes the pyramid levels 1 and 2 come from one
+ * kernel that reads the frames with 16-byte loads, otherwise from the per-level kernel: the same bits either way
+ * (DFE_PYRAMIDS_GENERIC in the environment, read at every call, forces the latter). */
 long dfe_geom_workspace_floats(const dfe_geom_args* args);
 /* byte offset of the mask pack inside the workspace, and its size in bytes per scale start */
 long dfe_geom_maskpack_offset_bytes(const dfe_geom_args* args, int scale);
 int dfe_geom_loss_fwd(const dfe_geom_args* args, void* stream);
 int dfe_geom_loss_bwd(const dfe_geom_args* args, void* stream);
+/* The launch plan the two entry points above pick for `args`: host only, nothing is launched, no device is needed and no
+ * pointer is followed (the three frame pointers are looked at for their alignment; every other pointer may be NULL).
+ * DFE_PYRAMIDS_GENERIC and DFE_ADJ_MODE are honoured as the launchers honour them.  Errors as dfe_geom_workspace_floats.
+ * plan receives DFE_GEOM_PLAN_INTS ints:
+ *   [0] S  [1] pyramid levels 1-2 from the two-level kernel (0 / 1)  [2] (frame, level) jobs of the per-level kernel
+ *   [3] box-mean jobs of k_geom_area_coarse  [4] adj_mode (0 separable, 1 mixed, 2 gather)  [5] adj_s0 (first level of the
+ *   two-pass adjoint; S = none)  [6] adj_nseg  [7] nblk_total, [8] fs_start[S]: the pointwise blocks and the flow-smoothness
+ *   units per sample, whose maximum sizes the flow-smoothness partials  [9] dsm_units, [10] nblk0: disparity-smoothness units
+ *   and full-resolution blocks, whose maximum sizes the disparity-smoothness partials  [11] DFE_DEPTH_TERM_* bits in effect
+ *   [12] total workspace floats, low 31 bits  [13] total >> 31  [14] rows per block of the forward rolling kernels  [15] of the
+ *   backward ones;
+ *   then DFE_GEOM_PLAN_PER_SCALE ints per scale s at DFE_GEOM_PLAN_HEAD + DFE_GEOM_PLAN_PER_SCALE * s:
+ *   H_s, W_s, forward strips (62 valid columns: SSIM, flow and disparity smoothness), valid columns of the last forward strip,
+ *   backward strips (60: SSIM and flow-smoothness backward), valid columns of the last backward strip, rows of the last row
+ *   block. */
+#define DFE_GEOM_PLAN_HEAD 16
+#define DFE_GEOM_PLAN_PER_SCALE 7
+#define DFE_GEOM_PLAN_INTS (DFE_GEOM_PLAN_HEAD + DFE_GEOM_PLAN_PER_SCALE * DFE_MAX_SCALES)
+int dfe_geom_plan(const dfe_geom_args* args, int* plan);
 
 /* Diagnostic variants used by bench.py: identical launches with a hipEvent recorded on `stream`
  * between them; they synchronise on the last event and return the per-segment durations in

@@ -1,12 +1,15 @@
 """CPU: self-tests of tests/guarded.py -- the guard bands notice a write one float before a view, one float after it and into a
 batch gap (and nothing else), and the plain-torch Winograd emulations that serve as the fp32 yardstick compute, in float64, what
 aten's float64 convolution / weight gradient computes."""
+import ctypes
+
 import pytest
 import torch
 import torch.nn.functional as F
 
 from tests import glue_cases as GC
 from tests import guarded as G
+from tests import loss_stack_cases as LC
 from tests import pwc_cases as PC
 
 CPU = torch.device("cpu")
@@ -562,3 +565,98 @@ def test_the_level_bounds_notice_one_dropped_term():
     assert abs(float(g5[p])) * float(taps["w"][0][0, p]) > 0.1
     with pytest.raises(AssertionError):
         G.check_scatter_bound("a dropped tap", bad.reshape(shape).float(), ref, mass, cnt, gmax)
+
+
+# ========================================================================================================= fused loss stack
+def test_the_cases_reach_every_strip_boundary_and_path_of_the_loss_stack(monkeypatch):
+    """dfe_geom_plan (host only) on the matrix of tests/loss_stack_cases.py: strips, row blocks, minimum sizes, pyramid paths,
+    adjoint modes, the operand that sizes each of the two shared partial-sum regions, modes and depth terms"""
+    for name in ("DFE_PYRAMIDS_GENERIC", "DFE_ADJ_MODE"):
+        monkeypatch.delenv(name, raising=False)
+    lib = _hip_lib()
+    plans = [(c, LC.plan(lib, LC.bare_args(c))) for c in LC.CASES]
+    assert all(p["fwd_rows"] == 8 and p["bwd_rows"] == 8 and p["S"] == c[3] and p["dt"] == (c[5] if c[4] != 2 else 0) for c, p in plans)
+    assert all(c[1] * c[2] < 10 ** 5 for c in LC.CASES) and len(set(LC.CASES)) == len(LC.CASES)
+    every = [(c, sc) for c, p in plans for sc in p["scales"]]
+    for c, sc in every:      # the plan's figures are the layout's: strips cover the width, the last one is never empty
+        assert sc["fwd_strips"] == -(-sc["W"] // 62) and sc["fwd_last"] == sc["W"] - 62 * (sc["fwd_strips"] - 1) and 1 <= sc["fwd_last"] <= 62
+        assert sc["bwd_strips"] == -(-sc["W"] // 60) and sc["bwd_last"] == sc["W"] - 60 * (sc["bwd_strips"] - 1) and 1 <= sc["bwd_last"] <= 60
+        assert sc["last_rows"] == sc["H"] - 8 * ((sc["H"] - 1) // 8) and 1 <= sc["last_rows"] <= 8
+    # forward strips of 62, backward strips of 60: an exact multiple (more than one strip), a last strip of 1, of 2, a narrow scale
+    for strips, last, cols in (("fwd_strips", "fwd_last", 62), ("bwd_strips", "bwd_last", 60)):
+        assert any(sc[strips] > 1 and sc[last] == cols for _, sc in every), cols
+        assert any(sc[strips] == 1 and sc[last] == cols for _, sc in every), cols
+        assert any(sc[strips] > 1 and sc[last] == 1 for _, sc in every), cols
+        assert any(sc[strips] > 1 and sc[last] == 2 for _, sc in every), cols
+        assert any(sc[strips] == 1 and sc[last] < cols for _, sc in every), cols
+    # rows: last blocks of 1, 2, 3 and 8; 1 and 2 where the flow-smoothness backward runs (modes 0 and 2), which walks 3 rows a step
+    assert {sc["last_rows"] for _, sc in every} >= {1, 2, 3, 8}
+    assert {sc["last_rows"] for c, sc in every if c[4] != 1} >= {1, 2, 3, 8}
+    assert any(sc["H"] == 3 for _, sc in every) and any(sc["W"] == 3 for _, sc in every)
+    assert any(sc["H"] * sc["W"] < 256 for _, sc in every) and any(sc["H"] * sc["W"] % 256 and sc["H"] * sc["W"] > 256 for _, sc in every)
+    # pyramids
+    assert any(p["two_level"] == 1 and p["generic_jobs"] == 3 * (c[3] - 3) for c, p in plans)
+    assert any(p["two_level"] == 0 and c[3] >= 3 and c[4] != 2 and c[2] % 4 for c, p in plans)                    # W % 4 != 0
+    assert any(p["two_level"] == 0 and c[3] < 3 and c[4] != 2 for c, p in plans)                                  # S < 3
+    assert any(p["coarse_jobs"] >= 1 and c[3] >= 5 for c, p in plans)
+    for c, p in plans:
+        assert p["two_level"] == int(c[3] >= 3 and c[4] != 2 and c[1] % 4 == 0 and c[2] % 4 == 0), c
+        if p["two_level"]:       # one frame pointer off 16 bytes, in turn: the per-level kernel takes every level
+            for f in range(3):
+                q = LC.plan(lib, LC.bare_args(c, tuple(4096 + (4 if k == f else 0) for k in range(3))))
+                assert q["two_level"] == 0 and q["generic_jobs"] == 3 * (c[3] - 1) and q["total"] == p["total"], (c, f)
+            assert LC.plan(lib, LC.bare_args(c, (4096, 8192, 4112)))["two_level"] == 1
+    # adjoint of the up-sampling
+    assert any(p["adj_mode"] == 1 and p["adj_s0"] == p["S"] and p["S"] > 1 for _, p in plans)                    # mixed, no coarse level
+    assert any(p["adj_mode"] == 1 and p["adj_s0"] < p["S"] for _, p in plans)                                    # mixed with one
+    assert dict((c[:4], p["adj_s0"]) for c, p in plans)[(2, 24, 124, 4)] == 3
+    assert any(p["adj_mode"] == 0 and p["adj_s0"] == 1 and p["adj_nseg"] > 1 and p["S"] > 1 for _, p in plans)    # separable
+    # the two regions sized by a maximum: each operand the larger one at least once (modes that run the kernels behind them)
+    assert any(p["nblk_total"] > p["fs_units"] for c, p in plans if c[4] != 1) and any(p["nblk_total"] < p["fs_units"] for c, p in plans if c[4] != 1)
+    assert any(p["dsm_units"] > p["nblk0"] for c, p in plans if c[4] != 2) and any(p["dsm_units"] < p["nblk0"] for c, p in plans if c[4] != 2)
+    assert any(p["nblk_total"] == p["fs_units"] and p["dsm_units"] == p["nblk0"] and c[4] == 0 for c, p in plans)  # ... and neither: no slack
+    # modes and depth terms
+    assert {c[5] for c in LC.CASES if c[4] == 0} == {0, 1, 2, 3} and {c[5] for c in LC.CASES if c[4] == 1} == {0, 3} and {c[4] for c in LC.CASES} == {0, 1, 2}
+    assert any(c[0] == 3 for c in LC.CASES)
+    for c, p in plans:
+        assert p["total"] == lib.dfe_geom_workspace_floats(ctypes.byref(LC.bare_args(c))), c
+    # the environment is honoured as the launchers honour it
+    two = next(c for c, p in plans if p["two_level"])
+    monkeypatch.setenv("DFE_PYRAMIDS_GENERIC", "1")
+    assert LC.plan(lib, LC.bare_args(two))["two_level"] == 0
+    monkeypatch.delenv("DFE_PYRAMIDS_GENERIC")
+    monkeypatch.setenv("DFE_ADJ_MODE", "separable")
+    assert LC.plan(lib, LC.bare_args(two))["adj_mode"] == 0 and LC.plan(lib, LC.bare_args(two))["total"] != dict(plans)[two]["total"]
+    monkeypatch.delenv("DFE_ADJ_MODE")
+    # errors: as dfe_geom_workspace_floats
+    bad = LC.bare_args((1, 8, 24, 3, 0, 0))
+    buf = (ctypes.c_int * LC.PLAN_INTS)()
+    assert lib.dfe_geom_plan(ctypes.byref(bad), buf) == -2 and lib.dfe_geom_plan(ctypes.byref(bad), None) == -1 and lib.dfe_geom_plan(None, buf) == -1
+
+
+@pytest.mark.parametrize("shape", sorted(LC.SEEDS))
+def test_the_loss_stack_cases_are_margin_checked_and_no_mask_is_constant(shape):
+    """what ``strict`` in test_hip_loss_stack.py rests on (as test_api_cpu.py does for STRICT): on the oracle alone, no pixel of
+    any scale inside a mask family's noise floor, for both align_corners settings; and each of the eight masks strictly between
+    2 % and 98 % set at scale 0"""
+    import numpy as np
+    from oracle import loss_stack_oracle as O
+    from tests import _margins as M
+    from tests.golden import make_golden as MG
+    B, H, W, S = shape
+    assert shape in {c[:4] for c in LC.CASES}
+    inp = LC.inputs(shape + (0, 0))
+    ang = inp.pose[..., 3:].astype(np.float64)
+    for fn in (np.cos, np.sin):      # conditioned poses: the exact value within 0.3 ulp of its nearest float32
+        v = fn(ang)
+        r = v.astype(np.float32)
+        assert (np.abs(v - r.astype(np.float64)) / np.spacing(np.abs(r)).astype(np.float64) < 0.3).all()
+    for ac in (False, True):
+        within = M.within_counts(M.geom_margins(inp, ac, S))
+        assert sum(within.values()) == 0, (shape, ac, within)
+        disps, pose, fb, ff = MG.lists_to_t(inp, False)
+        _, masks = O.GeomLossOracle(num_scales=S, align_corners=ac).geom_losses(*[MG.T(a) for a in inp.imgs], disps[0], disps[1], disps[2], pose, fb, ff,
+                                                                               MG.T(inp.K), MG.T(inp.K_inv))
+        for k in ("valid_bwd", "valid_fwd", "occ_bwd", "occ_fwd", "dyna_bwd", "dyna_fwd", "texture_bwd", "texture_fwd"):
+            frac = float(masks[k][0].mean())
+            assert 0.02 < frac < 0.98, (shape, ac, k, frac)

@@ -21,6 +21,7 @@ import torch
 
 from oracle import loss_stack_oracle as O
 from tests import _margins as M
+from tests import loss_stack_cases as LC
 from tests.golden import make_golden as MG
 from unsupervised_depth_opticalflow_egomotion_amd import synthetic
 
@@ -46,13 +47,21 @@ def to_dev(inp, grad=True):
     return disps, G(inp.pose, grad), [G(a, grad) for a in inp.flows_bwd], [G(a, grad) for a in inp.flows_fwd]
 
 
+def term_flags(depth_terms):
+    """(depth SSIM, depth consistency) of ``depth_terms``: a bool switches both, an int is the DFE_DEPTH_TERM_* bits"""
+    if isinstance(depth_terms, bool):
+        return depth_terms, depth_terms
+    return bool(depth_terms & 1), bool(depth_terms & 2)
+
+
 def run_hip(inp, ac, S, weights=None, depth_terms=False):
     from unsupervised_depth_opticalflow_egomotion_amd.loss_stack import geom_loss_stack
     disps, pose, fb, ff = to_dev(inp)
     il, it, ir = [G(a) for a in inp.imgs]
+    ssim, consis = term_flags(depth_terms)
     lp, masks = geom_loss_stack(il, it, ir, disps[0], disps[1], disps[2], pose, fb, ff, G(inp.K), G(inp.K_inv),
-                                num_scales=S, align_corners=ac, return_masks=True, enable_depth_ssim=depth_terms,
-                                enable_depth_consis=depth_terms)
+                                num_scales=S, align_corners=ac, return_masks=True, enable_depth_ssim=ssim,
+                                enable_depth_consis=consis)
     w = weights or MG.GEOM_WEIGHTS
     total = sum(w[k] * v.mean() for k, v in lp.items())
     total.backward()
@@ -63,8 +72,9 @@ def run_oracle(inp, ac, S, weights=None, depth_terms=False):
     m = O.GeomLossOracle(num_scales=S, align_corners=ac)
     disps, pose, fb, ff = MG.lists_to_t(inp, True)
     il, it, ir = [T(a) for a in inp.imgs]
+    ssim, consis = term_flags(depth_terms)
     lp, masks = m.geom_losses(il, it, ir, disps[0], disps[1], disps[2], pose, fb, ff, T(inp.K), T(inp.K_inv),
-                              enable_depth_ssim=depth_terms, enable_depth_consis=depth_terms)
+                              enable_depth_ssim=ssim, enable_depth_consis=consis)
     w = weights or MG.GEOM_WEIGHTS
     total = sum(w[k] * v.mean() for k, v in lp.items())
     total.backward()
@@ -95,11 +105,21 @@ def check_masks(mk_h, mk_o, margins, S, strict, names=MASKS):
     return nflip, npx, within
 
 
+def _worst_rel(lp_h, lp_o):
+    """largest |hip - oracle| / |oracle| over the loss rows (rows that are 0 in both: 0)"""
+    out = 0.0
+    for k in lp_h:
+        a, b = N(lp_h[k]).astype(np.float64), N(lp_o[k]).astype(np.float64)
+        out = max(out, float((np.abs(a - b) / np.maximum(np.abs(b), 1e-30))[np.abs(b) > 0].max(initial=0.0)))
+    return out
+
+
 def compare(inp, ac, S, weights=None, strict=False, depth_terms=False):
     lp_h, mk_h, tot_h, (dh, ph, fbh, ffh) = run_hip(inp, ac, S, weights, depth_terms)
     lp_o, mk_o, tot_o, (do, po, fbo, ffo) = run_oracle(inp, ac, S, weights, depth_terms)
-    assert ("loss_depth_ssim" in lp_h) == depth_terms and ("loss_depth_consis" in lp_h) == depth_terms
+    assert (("loss_depth_ssim" in lp_h), ("loss_depth_consis" in lp_h)) == term_flags(depth_terms)
     nflip, npx, _ = check_masks(mk_h, mk_o, M.geom_margins(inp, ac, S), S, strict)
+    worst = dict(loss=_worst_rel(lp_h, lp_o), grad=0.0)
     for k in lp_h:
         np.testing.assert_allclose(N(lp_h[k]), N(lp_o[k]), rtol=5e-6 + 4.0 * nflip / npx, atol=1e-7, err_msg=k)
     np.testing.assert_allclose(N(tot_h), N(tot_o), rtol=5e-6 + 4.0 * nflip / npx)
@@ -109,6 +129,7 @@ def compare(inp, ac, S, weights=None, strict=False, depth_terms=False):
         a, b = N(a.grad), N(b.grad)
         scale = max(np.abs(b).max(), 1e-12)
         bad = int((np.abs(a - b) > rel * scale + 1e-9).sum())
+        worst["grad"] = max(worst["grad"], float(np.abs(a - b).max() / scale))
         assert bad <= per_flip * nflip + extra, "%s: %d bad elements (nflip=%d) max diff %g scale %g" % (
             name, bad, nflip, np.abs(a - b).max(), scale)
     for f in range(3):
@@ -119,6 +140,8 @@ def compare(inp, ac, S, weights=None, strict=False, depth_terms=False):
         gcmp(ffh[s], ffo[s], "gflow_f_%d" % s)
     gp_h, gp_o = N(ph.grad), N(po.grad)
     tol = 2e-5 if nflip == 0 else 2e-2
+    print("DEVIATION mode 0: loss %.3g (5e-6) gradient %.3g (1e-4) pose gradient %.3g (%g)"
+          % (worst["loss"], worst["grad"], np.abs(gp_h - gp_o).max() / max(np.abs(gp_o).max(), 1e-12), tol))
     assert np.abs(gp_h - gp_o).max() <= tol * max(np.abs(gp_o).max(), 1e-12) + 1e-7, (gp_h, gp_o, nflip)
     return nflip, npx
 
@@ -354,9 +377,13 @@ def _grad_close(a, b, name, rel=2e-4, budget=0):
 def test_flow_mode_vs_oracle(shape, S, ac):
     """mode 2 (Model_flow stack, model_flow.py:209-255): no hard masks on this path -- the occlusion weights are
     smooth Gaussians -- losses agree to 5e-6 and flow gradients to 1e-4 of their scale, element-wise."""
-    from unsupervised_depth_opticalflow_egomotion_amd.loss_stack import flow_loss_stack
     b, h, w = shape
-    inp = synthetic.make_loss_stack_inputs(b, h, w, S, seed=1300 + h)
+    compare_flow_mode(synthetic.make_loss_stack_inputs(b, h, w, S, seed=1300 + h), ac, S)
+
+
+def compare_flow_mode(inp, ac, S):
+    """mode 2 against the oracle: losses 5e-6, flow gradients 1e-4 of their scale element-wise, no outliers"""
+    from unsupervised_depth_opticalflow_egomotion_amd.loss_stack import flow_loss_stack
     wts = dict(loss_flow_pixel=0.15, loss_flow_ssim=0.85, loss_flow_smooth=10.0, loss_flow_consis=0.01)
     fbh, ffh = [G(a, True) for a in inp.flows_bwd], [G(a, True) for a in inp.flows_fwd]
     lp_h = flow_loss_stack(*[G(a) for a in inp.imgs], fbh, ffh, num_scales=S, align_corners=ac)
@@ -367,6 +394,11 @@ def test_flow_mode_vs_oracle(shape, S, ac):
     assert set(lp_h) == set(lp_o)
     for k in lp_h:
         np.testing.assert_allclose(N(lp_h[k]), N(lp_o[k]), rtol=5e-6, atol=1e-7, err_msg=k)
+    worst = 0.0
+    for s in range(S):
+        for h_, o_ in ((fbh[s], fbo[s]), (ffh[s], ffo[s])):
+            worst = max(worst, float(np.abs(N(h_.grad) - N(o_.grad)).max() / max(np.abs(N(o_.grad)).max(), 1e-12)))
+    print("DEVIATION mode 2: loss %.3g (5e-6) gradient %.3g (1e-4)" % (_worst_rel(lp_h, lp_o), worst))
     for s in range(S):
         _grad_close(fbh[s], fbo[s], "gflow_b_%d" % s, rel=1e-4)
         _grad_close(ffh[s], ffo[s], "gflow_f_%d" % s, rel=1e-4)
@@ -379,11 +411,16 @@ def test_depth_mode_vs_oracle(shape, S, ac, depth_terms):
     """mode 1 (Model_depth stack, model_depth.py:272-337): the inverse_warp2 validity and texture masks are exact IEEE
     arithmetic on identical inputs -> they must EQUAL the oracle's (no noise floor on this path: no transcendental
     feeds a decision); losses 5e-6, gradients 1e-4 of their scale element-wise, pose gradient 2e-5."""
-    from unsupervised_depth_opticalflow_egomotion_amd.loss_stack import depth_loss_stack
     b, h, w = shape
     if b == 4 and (ac or depth_terms):
         pytest.skip("BASELINE configs[1] (B=4, 256x832, S=3) is compared once, in the default convention")
-    inp = synthetic.make_loss_stack_inputs(b, h, w, S, seed=1700 + h + (b if b == 4 else 0))
+    compare_depth_mode(synthetic.make_loss_stack_inputs(b, h, w, S, seed=1700 + h + (b if b == 4 else 0)), ac, S, depth_terms)
+
+
+def compare_depth_mode(inp, ac, S, depth_terms):
+    """mode 1 against the oracle: the four masks EQUAL, losses 5e-6, gradients 1e-4 of their scale element-wise with no
+    outliers, pose gradient 2e-5"""
+    from unsupervised_depth_opticalflow_egomotion_amd.loss_stack import depth_loss_stack
     wts = dict(loss_depth_pixel=1.0, loss_depth_smooth=0.1)
     if depth_terms:   # the terms the reference keeps commented (model_depth.py:326-327,332-333), config weights
         wts.update(loss_depth_ssim=0.85, loss_depth_consis=0.1)
@@ -405,12 +442,16 @@ def test_depth_mode_vs_oracle(shape, S, ac, depth_terms):
             assert np.array_equal(N(mk_h[k][s]), N(mk_o[k][s])), (k, s)
     for k in lp_h:
         np.testing.assert_allclose(N(lp_h[k]), N(lp_o[k]), rtol=5e-6, atol=1e-7, err_msg=k)
+    gp_h, gp_o = N(ph.grad), N(po.grad)
+    print("DEVIATION mode 1: loss %.3g (5e-6) gradient %.3g (1e-4) pose gradient %.3g (2e-5)"
+          % (_worst_rel(lp_h, lp_o), max(float(np.abs(N(dh[f][s].grad) - N(do[f][s].grad)).max() / max(np.abs(N(do[f][s].grad)).max(), 1e-12))
+                                         for f in range(3) for s in range(S)),
+             np.abs(gp_h - gp_o).max() / max(np.abs(gp_o).max(), 1e-12)))
     for f in range(3):
         for s in range(S):
             a, c = N(dh[f][s].grad), N(do[f][s].grad)
             bad = int((np.abs(a - c) > 1e-4 * max(np.abs(c).max(), 1e-12) + 1e-9).sum())
             assert bad == 0, ("gdisp_%d_%d" % (f, s), bad, np.abs(a - c).max(), np.abs(c).max())
-    gp_h, gp_o = N(ph.grad), N(po.grad)
     assert np.abs(gp_h - gp_o).max() <= 2e-5 * max(np.abs(gp_o).max(), 1e-12) + 1e-7, (gp_h, gp_o)
 
 
@@ -492,3 +533,23 @@ def test_fused_two_level_pyramid_kernel_is_the_generic_one_bit_for_bit(shape):
     a, b = run(False), run(True)
     for x, y in zip(a[0] + a[1] + a[2] + [a[3]] + a[4], b[0] + b[1] + b[2] + [b[3]] + b[4]):
         assert np.array_equal(x, y)
+
+
+@pytest.mark.parametrize("ac", [False, True])
+@pytest.mark.parametrize("case", LC.CASES, ids=LC.case_id)
+def test_fused_stack_at_the_strip_boundaries(case, ac):
+    """The matrix of tests/loss_stack_cases.py -- scale widths that are multiples of the 62- and 60-column strips or leave a
+    last strip of 1 or 2 columns, last row blocks of 1, 2, 3 and 8 rows, 3-row and 3-column scales, every pyramid and adjoint
+    path (test_guarded_cpu.py asserts the coverage through dfe_geom_plan) -- against the oracle under the tolerances stated
+    at the top of this file.  Mode 0 is strict: the seeds are margin-checked (re-derived on the host in test_guarded_cpu.py
+    and again inside compare), so every mask must EQUAL the oracle's and no gradient element may differ by more than 1e-4
+    of its tensor's scale; modes 1 and 2 run the bodies of test_depth_mode_vs_oracle / test_flow_mode_vs_oracle."""
+    B, H, W, S, mode, dt = case
+    inp = LC.inputs(case)
+    if mode == 0:
+        compare(inp, ac, S, strict=True, depth_terms=int(dt))
+    elif mode == 1:
+        assert dt in (0, 3)
+        compare_depth_mode(inp, ac, S, dt == 3)
+    else:
+        compare_flow_mode(inp, ac, S)

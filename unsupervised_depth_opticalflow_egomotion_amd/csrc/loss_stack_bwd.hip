@@ -1074,6 +1074,7 @@ static int geom_bwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
   int rc = geom_layout(a, &L);
   if (rc != DFE_OK) return rc;
   if (!a->workspace || !a->grad_losses || (a->mode != 2 && !a->pose)) return DFE_ERR_NULL;
+  if (!aligned16(a->workspace)) return DFE_ERR_DIMS;   // as the forward: include/dfe_hip.h
   if (a->workspace_floats < L.total) return DFE_ERR_WORKSPACE;
   for (int f = 0; f < 3; ++f) { if (!a->img[f]) return DFE_ERR_NULL; if (a->mode != 2) for (int s = 0; s < L.S; ++s) if (!a->disp[f][s]) return DFE_ERR_NULL; }
   if (a->mode != 1) for (int d = 0; d < 2; ++d) for (int s = 0; s < L.S; ++s) if (!a->flow[d][s]) return DFE_ERR_NULL;

@@ -1093,6 +1093,7 @@ using namespace dfe;
 
 static int check_args(const dfe_geom_args* a, const GeomLayout& L, bool bwd) {
   if (!a->workspace) return DFE_ERR_NULL;
+  if (!aligned16(a->workspace)) return DFE_ERR_DIMS;   // the memory contract of include/dfe_hip.h
   if (a->mode != 2 && (!a->pose || !a->K)) return DFE_ERR_NULL;
   if (a->mode == 0 && !a->K_inv) return DFE_ERR_NULL;
   if (a->workspace_floats < L.total) return DFE_ERR_WORKSPACE;
@@ -1108,7 +1109,51 @@ static int check_args(const dfe_geom_args* a, const GeomLayout& L, bool bwd) {
 }
 
 
+// The two pyramid decisions of the forward, stated once: geom_fwd_impl launches by them and dfe_geom_plan reports them.
+// levels 1 and 2 in one pass over the frames (k_geom_pyramids12: 16-byte loads of the frames) when the pyramid is an exact
+// power-of-two one of the geom / depth models and all three frames sit on 16 bytes
+static bool pyramids_two_level(const dfe_geom_args* a, const GeomLayout& L) {
+  return L.S >= 3 && a->mode != 2 && a->H % 4 == 0 && a->W % 4 == 0 && getenv("DFE_PYRAMIDS_GENERIC") == nullptr &&
+         aligned16(a->img[0]) && aligned16(a->img[1]) && aligned16(a->img[2]);
+}
+// a box mean whose window exceeds AREA_COARSE_MIN inputs moves to the wave-per-output kernel (k_geom_area_coarse)
+static bool area_window_is_coarse(const dfe_geom_args* a, int outH, int outW) {
+  const long kh = (a->H + outH - 1) / outH + 1, kw = (a->W + outW - 1) / outW + 1;
+  return kh * kw > AREA_COARSE_MIN;
+}
+
 extern "C" {
+
+int dfe_geom_plan(const dfe_geom_args* args, int* plan) {
+  if (!plan) return DFE_ERR_NULL;
+  GeomLayout L;
+  const int rc = geom_layout(args, &L);
+  if (rc != DFE_OK) return rc;
+  for (int i = 0; i < DFE_GEOM_PLAN_INTS; ++i) plan[i] = 0;
+  const bool two = pyramids_two_level(args, L);
+  int generic = 0, coarse = 0;
+  for (int s = two ? 3 : 1; s < L.S; ++s)
+    for (int f = 0; f < 3; ++f) {     // the jobs geom_fwd_impl forms: bilinear + box mean (source frames); mode 2: box mean only
+      const bool bil = args->mode != 2, area = args->mode == 2 || f != 1;
+      const bool wave = area && area_window_is_coarse(args, L.H[s], L.W[s]);
+      coarse += wave ? 1 : 0;
+      generic += (bil || (area && !wave)) ? 1 : 0;
+    }
+  plan[0] = L.S; plan[1] = two ? 1 : 0; plan[2] = generic; plan[3] = coarse;
+  plan[4] = L.adj_mode; plan[5] = L.adj_s0; plan[6] = L.adj_nseg;
+  plan[7] = L.blk_start[L.S]; plan[8] = L.fs_start[L.S]; plan[9] = L.dsm_units; plan[10] = L.nblk0;
+  plan[11] = L.dt;
+  plan[12] = static_cast<int>(L.total & 0x7fffffffL); plan[13] = static_cast<int>(L.total >> 31);
+  plan[14] = RS_ROWS; plan[15] = RSB_ROWS;
+  for (int s = 0; s < L.S; ++s) {
+    int* p = plan + DFE_GEOM_PLAN_HEAD + DFE_GEOM_PLAN_PER_SCALE * s;
+    p[0] = L.H[s]; p[1] = L.W[s];
+    p[2] = L.roll_strips[s]; p[3] = L.W[s] - (L.roll_strips[s] - 1) * RS_COLS;
+    p[4] = L.rollb_strips[s]; p[5] = L.W[s] - (L.rollb_strips[s] - 1) * RSB_COLS;
+    p[6] = L.H[s] - (L.H[s] - 1) / RSB_ROWS * RSB_ROWS;
+  }
+  return DFE_OK;
+}
 
 long dfe_geom_workspace_floats(const dfe_geom_args* args) {
   GeomLayout L;
@@ -1151,9 +1196,7 @@ static int geom_fwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
   DFE_MARK();
   // levels 1 and 2 in one pass over the frames when the pyramid is an exact power-of-two one (geom / depth models)
   int first_generic = 1;
-  if (L.S >= 3 && a->mode != 2 && a->H % 4 == 0 && a->W % 4 == 0 && getenv("DFE_PYRAMIDS_GENERIC") == nullptr &&
-      (reinterpret_cast<uintptr_t>(a->img[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(a->img[1]) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(a->img[2]) & 15) == 0) {
+  if (pyramids_two_level(a, L)) {
     Pyr12Job jb;
     jb.planes = L.B * 3; jb.H = a->H; jb.W = a->W;
     for (int f = 0; f < 3; ++f) {
@@ -1187,8 +1230,7 @@ static int geom_fwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
     int max_coarse = 0, kept = 0;
     for (int k = 0; k < jobs.n; ++k) {
       PyrJob& jb = jobs.j[k];
-      const long kh = (a->H + jb.outH - 1) / jb.outH + 1, kw = (a->W + jb.outW - 1) / jb.outW + 1;
-      if (jb.out_area && kh * kw > AREA_COARSE_MIN) {
+      if (jb.out_area && area_window_is_coarse(a, jb.outH, jb.outW)) {
         coarse.j[coarse.n++] = PyrJob{jb.in, nullptr, jb.out_area, jb.outH, jb.outW};
         if (jb.outH * jb.outW > max_coarse) max_coarse = jb.outH * jb.outW;
         jb.out_area = nullptr;
