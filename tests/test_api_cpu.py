@@ -930,8 +930,8 @@ def test_miopen_db_status_reports_tuned_only_for_a_matching_key(monkeypatch, tmp
 
 
 def test_winograd_dispatch_rule_is_shape_logic_only(monkeypatch):
-    """convs._wino_eligible (which 3x3 layers take dfe_wino_conv3x3) is pure shape logic: CPU tensors never qualify, and on a
-    fake device tensor the thresholds, the paddings and the dilation rule decide."""
+    """convs.plan's forward field (which 3x3 layers take dfe_wino_conv3x3) is pure shape logic: CPU tensors never qualify, and on
+    a fake device tensor the thresholds, the paddings and the dilation rule decide."""
     from unsupervised_depth_opticalflow_egomotion_amd import convs
 
     class FakeCuda:
@@ -948,7 +948,9 @@ def test_winograd_dispatch_rule_is_shape_logic_only(monkeypatch):
             for s in self.shape:
                 n *= s
             return n
-    el = convs._wino_eligible
+
+    def el(x, w_shape, cin, stride, padding, dilation, groups=1):      # (the plan reads the channel count off the filter's shape)
+        return convs.plan(x, w_shape, stride, padding, dilation, groups).fwd == "wino"
     assert not el(torch.zeros(8, 64, 64, 208), (64, 64, 3, 3), 64, (1, 1), (1, 1), (1, 1))          # CPU tensor
     x = FakeCuda(8, 128, 64, 208)
     assert el(x, (128, 128, 3, 3), 128, (1, 1), (1, 1), (1, 1)) and el(x, (96, 128, 3, 3), 128, (1, 1), (0, 0), (1, 1))
@@ -964,6 +966,68 @@ def test_winograd_dispatch_rule_is_shape_logic_only(monkeypatch):
     assert not el(FakeCuda(64, 512, 128, 416), (64, 512, 3, 3), 512, (1, 1), (1, 1), (1, 1))          # > 2^30 elements: 32-bit offsets
     monkeypatch.setattr(convs, "WINO_MIN_TILES", 0)
     assert not el(x, (128, 128, 3, 3), 128, (1, 1), (1, 1), (1, 1))                                   # switched off
+
+
+def test_conv_routes_match_the_recorded_table(monkeypatch):
+    """convs.plan against tests/golden/conv_routes.json: the forward / data-gradient / weight-gradient kernel of every convolution
+    the three models issue in one training step at 256x832, 3 scales (modes geom, depth, flow at per-GPU batches 1, 4, 8), as the
+    call sites of the commit named in the fixture chose them -- under the default switches and with each switch flipped alone.  A
+    changed threshold or a reordered rule moves layers between MIOpen and this build's kernels without failing any value test;
+    it fails here.  No entry is left out."""
+    import json
+    from unsupervised_depth_opticalflow_egomotion_amd import convs
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_routes.json")) as fh:
+        doc = json.load(fh)
+    entries, default = doc["entries"], doc["routes"]["default"]
+    assert len(default) == len(entries) and sorted(set(i for ids in doc["modes"].values() for i in ids)) == list(range(len(entries)))
+    assert sorted(doc["modes"]) == sorted("%s/%d" % (m, b) for m in ("geom", "depth", "flow") for b in (1, 4, 8))
+
+    def route(e):
+        kw = {"plane": route(entries[e["first"]]).fwd == "plane"} if "first" in e else {}     # a dense block decides once
+        return convs.plan((True, torch.float32, tuple(e["x"])), e["w"], e["stride"], e["padding"], e["dilation"], e["groups"], e["bias"],
+                          e["act"], e["ctx"], tuple(e.get("fuse", ())), **kw)
+    assert set(doc["routes"]) == {"default", "WINO_MIN_TILES=0", "WINO_DILATED=0", "WINO_WGRAD=0", "SCONV=0", "PLANECONV_MAX_HW=0",
+                                  "WINO_EPILOGUE=0", "FLOW_HEAD=0", "PHASE_MIN_DILATION=2"}
+    checked = 0
+    for setting, diff in doc["routes"].items():
+        want = list(default)
+        with monkeypatch.context() as mp:
+            if setting != "default":
+                for i, v in diff.items():
+                    want[int(i)] = v
+                name, value = setting.split("=")
+                mp.setattr(convs, name, type(getattr(convs, name))(int(value)))
+            got = ["/".join(route(e)) for e in entries]
+        wrong = [(setting, i, entries[i], got[i], want[i]) for i in range(len(entries)) if got[i] != want[i]]
+        assert not wrong, wrong[:5]
+        checked += len(got)
+    assert checked == 9 * len(entries)
+    # the table is not trivially MIOpen: under the default switches every kernel of this build has a layer -- except the
+    # phase-image path, which the default DFE_WINO_DILATED=1 leaves empty at these shapes (the Winograd kernel takes all four
+    # dilated layers first); it is seen with that switch off
+    fwd, dgrad, wgrad = (set(r.split("/")[k] for r in default) for k in range(3))
+    assert {"miopen", "wino", "wino_act", "plane", "conv1x1", "flow_head"} <= fwd and "wino" in dgrad
+    assert {"wino_wgrad", "sconv_wgrad", "wgrad3x3"} <= wgrad
+    assert "phase" not in fwd and any(v.startswith("phase/") for v in doc["routes"]["WINO_DILATED=0"].values())
+    # host tensors never reach the library or a kernel of this build, whatever the door
+    for ctx in ("conv2d", "module", "conv_act", "raw", "dense", "dense_head", "prepadded"):
+        assert convs.plan(torch.zeros(1, 16, 8, 8), (16, 16, 3, 3), 1, 1, bias=True, act=True, ctx=ctx, fuse=("plane", "wino_act", "conv1x1")) == convs.MIOPEN
+
+
+def test_ops_is_the_leaf_and_nothing_imports_it_inside_a_function():
+    """ops.py knows nothing of convs; no module of the package imports ops or convs inside a function (the package's own lazy
+    ``set_align_corners`` attribute aside, which must not pull torch in when the package is imported)."""
+    import re
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "unsupervised_depth_opticalflow_egomotion_amd")
+    with open(os.path.join(root, "ops.py")) as fh:
+        assert "convs" not in fh.read()
+    late = []
+    for d, _, files in os.walk(root):
+        for f in files:
+            if f.endswith(".py") and (d, f) != (root, "__init__.py"):
+                with open(os.path.join(d, f)) as fh:
+                    late += [(f, line.strip()) for line in fh if re.match(r"\s+(from \.+ import .*\b(ops|convs)\b|from \.+(ops|convs) import)", line)]
+    assert not late, late
 
 
 def test_wino_weight_cache_host_logic_without_a_gpu():

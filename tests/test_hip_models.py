@@ -60,7 +60,7 @@ def test_g7_full_model_vs_reference(golden_dir):
 
 @pytest.mark.parametrize("lvl,hw,B", [(6, (4, 13), 8), (5, (8, 26), 8), (4, (16, 52), 3), (2, (64, 208), 2)])
 def test_pwc_dense_block_matches_composition(lvl, hw, B):
-    """PWC_tf._decode as one operator (ops.dense_decode: epilogues writing into the concatenated buffers, manual
+    """PWC_tf._decode as one operator (convs.dense_decode: epilogues writing into the concatenated buffers, manual
     convolution backward) against the plain module composition of the same level on the same device: outputs and
     every gradient (input, five conv weights / biases, flow head) to 1e-6 of their scale (same MIOpen calls; only the
     order of the two-term gradient sums can differ).  Levels 6 and 5 run this build's small-plane convolutions

@@ -625,7 +625,7 @@ def test_flow_head_matches_miopen(shape):
     convolution: forward 1e-5 of the output scale, the three gradients 1e-4 of theirs (fp32 sums of C*9 / H*W*B terms in a
     different order); ragged sizes, one row, strips that end mid-wave."""
     import torch.nn.functional as F
-    from unsupervised_depth_opticalflow_egomotion_amd import ops
+    from unsupervised_depth_opticalflow_egomotion_amd import convs, ops
     b, c, h, w = shape
     r = MG.rng(500 + c + h)
     x = r.standard_normal(shape).astype(np.float32)
@@ -633,7 +633,7 @@ def test_flow_head_matches_miopen(shape):
     bs = r.standard_normal(2).astype(np.float32)
     gy = r.standard_normal((b, 2, h, w)).astype(np.float32)
     xt, wtt, bt = G(x, True), G(wt, True), G(bs, True)
-    assert ops.flow_head_eligible(xt, wtt, bt)
+    assert convs.flow_head_eligible(xt, wtt, bt)
     y = ops.FlowHeadFn.apply(xt, wtt, bt)
     y.backward(G(gy))
     xr, wr, br = G(x, True), G(wt, True), G(bs, True)
@@ -942,19 +942,19 @@ def test_wgrad3x3_mfma(shape):
 
 
 def test_thin_conv_function_and_eligibility():
-    """ops.conv3x3_valid: the MFMA weight gradient is used for the thin full-resolution layers only; values and both
+    """convs.conv3x3_valid: the MFMA weight gradient is used for the thin full-resolution layers only; values and both
     gradients agree with F.conv2d on the same device (MIOpen) to 1e-5 / 2e-4 of the gradient scale."""
     import torch.nn.functional as F
-    from unsupervised_depth_opticalflow_egomotion_amd import ops
+    from unsupervised_depth_opticalflow_egomotion_amd import convs
     torch.manual_seed(2)
     p = torch.randn(2, 32, 130, 418, device=dev())
     w = torch.randn(16, 32, 3, 3, device=dev()) * 0.1
-    assert ops.thin_conv3x3_eligible(p, w)
-    assert not ops.thin_conv3x3_eligible(torch.zeros(2, 64, 34, 106, device=dev()), torch.zeros(32, 64, 3, 3, device=dev()))
-    assert not ops.thin_conv3x3_eligible(p, torch.zeros(64, 32, 3, 3, device=dev()))
+    assert convs.thin_conv3x3_eligible(p, w)
+    assert not convs.thin_conv3x3_eligible(torch.zeros(2, 64, 34, 106, device=dev()), torch.zeros(32, 64, 3, 3, device=dev()))
+    assert not convs.thin_conv3x3_eligible(p, torch.zeros(64, 32, 3, 3, device=dev()))
     for pp, ww in ((p, w), (torch.randn(2, 16, 66, 210, device=dev()), torch.randn(16, 16, 3, 3, device=dev()) * 0.1)):
         res = []                      # 32 -> 16: MFMA weight gradient only; 16 -> 16: all three passes on the matrix cores
-        for fn in (ops.conv3x3_valid, F.conv2d):
+        for fn in (convs.conv3x3_valid, F.conv2d):
             pi, wi = pp.clone().requires_grad_(True), ww.clone().requires_grad_(True)
             y = fn(pi, wi)
             (y * y).mean().backward()

@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from unsupervised_depth_opticalflow_egomotion_amd import ops
+from unsupervised_depth_opticalflow_egomotion_amd import convs, ops
 from unsupervised_depth_opticalflow_egomotion_amd._lib import get_lib
 
 pytestmark = pytest.mark.gpu
@@ -61,7 +61,7 @@ def test_planeconv_rejects_large_planes_and_null():
     assert lib.dfe_planeconv_supported(8, 64, 64, 64, 208) == 0 and lib.dfe_planeconv_ws_floats(8, 64, 64, 64, 208) == 0
     x = torch.zeros(1, 4, 64, 208, device=dev())
     w = torch.zeros(4, 4, 3, 3, device=dev())
-    assert not ops.planeconv_eligible(x, w)
+    assert not convs.planeconv_eligible(x, w)
     assert lib.dfe_planeconv_fwd(None, None, None, 1.0, None, 0, None, 0, None, 1, 1, 1, 1, 1, None) != 0
 
 
@@ -101,7 +101,7 @@ def test_conv1x1_small_autograd_matches_aten(shape, slope):
     conv = nn.Conv2d(Ci, Co, 1).to(dev())
     x = torch.randn(B, Ci, H, W, device=dev())
     gy = torch.randn(B, Co, H, W, device=dev())
-    assert ops.conv1x1_small_eligible(x, conv)
+    assert convs.conv1x1_small_eligible(x, conv)
     outs = []
     for fused in (True, False):
         conv.zero_grad()
@@ -112,4 +112,4 @@ def test_conv1x1_small_autograd_matches_aten(shape, slope):
     for u, v in zip(*outs):
         assert float((u - v).abs().max()) <= 1e-5 * float(v.abs().max()) + 1e-9
     big = torch.zeros(1, 4, 64, 208, device=dev())
-    assert not ops.conv1x1_small_eligible(big, nn.Conv2d(4, 4, 1).to(dev()))
+    assert not convs.conv1x1_small_eligible(big, nn.Conv2d(4, 4, 1).to(dev()))

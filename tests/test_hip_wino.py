@@ -147,15 +147,15 @@ def test_wino_fused_epilogue_is_the_separate_pass_bit_for_bit(shape):
 
 
 def test_conv_bias_act_function_matches_the_two_node_graph():
-    """ops.ConvBiasActFn (net_utils.conv on the Winograd kernel: one launch forward, one autograd node) against
+    """convs.conv_bias_act (net_utils.conv on the Winograd kernel: one launch forward, one autograd node) against
     bias_act(conv2d(...)): outputs and the input / bias gradients equal bit for bit (same kernels underneath)."""
     from unsupervised_depth_opticalflow_egomotion_amd import convs
     torch.manual_seed(21)
     for (B, Ci, Co, H, W, d) in [(2, 32, 48, 32, 104, 1), (1, 64, 64, 32, 64, 2)]:
         conv = torch.nn.Conv2d(Ci, Co, 3, 1, d, d).to(dev())
         x = torch.randn(B, Ci, H, W, device=dev(), requires_grad=True)
-        assert ops.conv_bias_act_eligible(x, conv)
-        y = ops.conv_bias_act(x, conv, 0.1)
+        assert convs.conv_bias_act_eligible(x, conv)
+        y = convs.conv_bias_act(x, conv, 0.1)
         g = torch.randn_like(y)
         gx, gw, gb = torch.autograd.grad(y, [x, conv.weight, conv.bias], g)
         y2 = ops.bias_act(convs.conv2d(x, conv.weight, None, 1, d, d), conv.bias, 0.1)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer timing of the small-plane 3x3 convolutions (csrc/ops_planeconv.hip) against the MIOpen calls they replace in
-ops.DenseDecodeFn, on the decoder layers of PWC levels 6 / 5 / 4 of a 256x832 frame (B = 8 pairs).  HIP-event time per call,
+convs.DenseDecodeFn, on the decoder layers of PWC levels 6 / 5 / 4 of a 256x832 frame (B = 8 pairs).  HIP-event time per call,
 median of --reps bursts of --iters calls.  MIOpen forward = convolution + dfe_bias_act_fwd2 (what the decoder runs);
 planeconv forward = k_planeconv + k_planeconv_finish (bias and activation inside).
 

@@ -12,6 +12,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import ops
+
 
 def env_world():
     return int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
@@ -136,7 +138,6 @@ class FlatAllReduce(torch.nn.Module):
         if tensors and self.world > 1:
             dist._broadcast_coalesced(dist.group.WORLD, tensors, 250 * 1024 * 1024, 0)
             if tensors[0].is_cuda:
-                from . import ops
                 ops.wino_weights.invalidate()       # written through .data: no version bump for the cached filters to miss on
 
     def forward(self, *args, **kwargs):

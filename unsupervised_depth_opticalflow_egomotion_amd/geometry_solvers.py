@@ -27,6 +27,7 @@ exist so that those lines can be switched on as written."""
 import torch
 import torch.nn.functional as F
 
+from . import ops          # the reference leaves align_corners to the installed torch (ops.set_align_corners)
 from .structures import compute_essential_matrix, compute_projection_matrix
 
 
@@ -124,7 +125,6 @@ class GeometrySolvers:
         bsz, _, h, w = depth_pred.shape
         n = depth_tri.shape[1]
         grid = torch.stack([2.0 * coord_tri[:, :, 0] / (w - 1.0) - 1.0, 2.0 * coord_tri[:, :, 1] / (h - 1.0) - 1.0], -1)
-        from . import ops                   # the reference leaves align_corners to the installed torch (ops.set_align_corners)
         inter = F.grid_sample(depth_pred, grid.view(bsz, n, 1, 2), padding_mode="reflection",
                               align_corners=ops.get_align_corners()).squeeze(-1).transpose(1, 2)
         scale = (torch.median(inter, 1)[0] / (torch.median(depth_tri, 1)[0] + 1e-12)).detach()

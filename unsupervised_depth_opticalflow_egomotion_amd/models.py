@@ -10,6 +10,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import ops
 from .loss_stack import LossRows, geom_loss_stack, depth_loss_stack, flow_loss_stack, decode_mask
 from .geometry_solvers import GeometrySolvers
 from .loss_terms import LossTerms
@@ -398,7 +399,6 @@ class Model_flow(LossTerms, nn.Module):
     def get_occlusion_mask_from_flow(self, tensor_size, flow):
         """model_flow.py:33-39 -- dead in the reference (it calls an undefined ``transformerFwd``); here the bilinear
         forward splat of a ones image by ``flow``, clamped to [0,1], broadcast to ``tensor_size`` [B,C,H,W]."""
-        from . import ops
         b, c, h, w = tensor_size
         if tuple(flow.shape) != (b, 2, h, w):
             raise ValueError("flow must be [B,2,H,W] matching tensor_size")

@@ -6,6 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import resnet
+from .. import convs, ops
 
 
 class ResnetEncoder(nn.Module):
@@ -89,14 +90,13 @@ class DepthDecoder(nn.Module):
         """Same graph on the GPU: the bias / ELU / bilinear x2 / cat / reflection-pad glue between the MIOpen
         convolutions runs as two fused HIP passes (ops.elu_pad, ops.elu_up2_cat_pad); the convolutions are applied
         bias-free to the padded tensors.  ``a`` / ``c`` hold convolution outputs *before* bias and ELU."""
-        from .. import ops
         out = {}
         p = ops.elu_pad(feats[-1], None, apply_elu=False)        # encoder output: already activated
         for scale in range(4, -1, -1):
             c0, c1 = self.upconvs[4 - scale][0].conv.conv, self.upconvs[4 - scale][1].conv.conv
-            a = ops.conv3x3_valid(p, c0.weight)
+            a = convs.conv3x3_valid(p, c0.weight)
             q = ops.elu_up2_cat_pad(a, c0.bias, feats[scale - 1] if scale > 0 else None)
-            c = ops.conv3x3_valid(q, c1.weight)
+            c = convs.conv3x3_valid(q, c1.weight)
             if scale in self.scales or scale > 0:
                 p = ops.elu_pad(c, c1.bias, apply_elu=True)      # shared by the disparity head and the next stage
             if scale in self.scales:

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import convs, ops
+from .. import convs
 from ..convs import Conv2d
 
 
@@ -31,23 +31,15 @@ class PoseCNN(nn.Module):
 
     def conv_relu(self, conv, x):
         """``self.relu(conv(x))`` (pose_cnn.py:68-69, 84-85).  On the GPU the convolution runs without its bias and the bias +
-        ReLU epilogue is one in-place HIP pass whose backward also yields the bias gradient (ops.bias_act, slope 0)."""
-        if x.is_cuda:
-            if (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-                    and conv.groups == 1 and ops.planeconv_eligible(x, conv.weight)):
-                return ops.planeconv_act(x, conv.weight, conv.bias, 0.0)     # the 2x7 refinement planes: this build's MFMA kernels
-            if ops.conv1x1_small_eligible(x, conv):
-                return ops.conv1x1_small(x, conv, 0.0)
-            return ops.bias_act(convs.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups),
-                                conv.bias, 0.0)
+        ReLU epilogue is one in-place HIP pass whose backward also yields the bias gradient (convs.conv_act, slope 0)."""
+        if x.is_cuda:      # the 2x7 refinement planes: this build's MFMA kernels; never the fused Winograd epilogue
+            return convs.conv_act(x, conv, 0.0, ("plane", "conv1x1"))
         return self.relu(conv(x))
 
     @staticmethod
     def _conv1x1(conv, x):
         """A 1x1 convolution without activation (pose_conv, refine_pose_conv: pose_cnn.py:32,48,88,72) on the tiny-plane kernel."""
-        if x.is_cuda and ops.conv1x1_small_eligible(x, conv):
-            return ops.conv1x1_small(x, conv, 1.0)
-        return conv(x)
+        return convs.conv_act(x, conv, 1.0, ("conv1x1",)) if x.is_cuda else conv(x)
 
     def atten_refine(self, x):
         B, C, H, W = x.size()

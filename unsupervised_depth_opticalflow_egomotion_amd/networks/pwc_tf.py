@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import convs, ops
 from ..convs import Conv2d
 from ..structures.net_utils import ConvAct, conv, warp_flow
 
@@ -79,12 +79,12 @@ class PWC_tf(nn.Module):
 
     def _decode(self, lvl, x):
         """pwc_tf.py:113-118 (level 6) and the same six lines of every other level -> (flow, x4).  On the GPU the block is
-        one operator around its six MIOpen convolutions (ops.dense_decode): no torch.cat copies, no slice copies or
+        one operator around its six convolutions (convs.dense_decode): no torch.cat copies, no slice copies or
         gradient-accumulation adds in the backward pass."""
         if x.is_cuda and self._dense_block_is_standard(lvl):
-            convs = [getattr(self, "conv%d_%d" % (lvl, k))[0] for k in range(5)]
-            return ops.dense_decode(x, convs, getattr(self, "predict_flow%d" % lvl),
-                                    getattr(self, "conv%d_0" % lvl)[1].negative_slope)
+            layers = [getattr(self, "conv%d_%d" % (lvl, k))[0] for k in range(5)]
+            return convs.dense_decode(x, layers, getattr(self, "predict_flow%d" % lvl),
+                                      getattr(self, "conv%d_0" % lvl)[1].negative_slope)
         x0 = getattr(self, "conv%d_0" % lvl)(x)
         x1 = getattr(self, "conv%d_1" % lvl)(x0)
         x2 = getattr(self, "conv%d_2" % lvl)(torch.cat((x0, x1), 1))

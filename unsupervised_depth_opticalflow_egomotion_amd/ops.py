@@ -12,7 +12,7 @@ import threading
 
 import torch
 
-from . import _lib, convs
+from . import _lib
 from ._lib import DfeError, check, f32c, get_lib, ptr, stream_ptr
 
 _ALIGN_CORNERS = False
@@ -303,6 +303,9 @@ def maxpool3x3s2(x):
     if x.shape[0] * x.shape[1] > 65535:
         raise _lib.DfeError("maxpool3x3s2: more than 65535 planes")
     return MaxPool3x3s2Fn.apply(x)
+
+
+PWC_LEVEL_MAP = os.environ.get("DFE_PWC_LEVEL_MAP", "1") != "0"      # the PWC level's inverse map built in its forward pass (PwcLevelInputFn)
 
 
 class PwcLevelInputFn(torch.autograd.Function):
@@ -775,22 +778,6 @@ def bias_act(z, bias, slope):
 
 
 # --------------------------------------------------------------------------- small-plane 3x3 convolutions (fp32 MFMA)
-# Planes of at most this many pixels per sample take the dfe_planeconv_* kernels inside DenseDecodeFn (PWC levels 6 and 5 of
-# a 256x832 frame: 52 and 208 pixels); 0 = every layer stays on MIOpen.
-PLANECONV_MAX_HW = int(os.environ.get("DFE_PLANECONV_MAX_HW", "208"))
-WINO_EPILOGUE = os.environ.get("DFE_WINO_EPILOGUE", "1") != "0"      # switches read once at import (246 environment reads per step before)
-FLOW_HEAD = os.environ.get("DFE_FLOW_HEAD", "1") != "0"
-PWC_LEVEL_MAP = os.environ.get("DFE_PWC_LEVEL_MAP", "1") != "0"      # the PWC level's inverse map built in its forward pass (PwcLevelInputFn)
-
-
-def planeconv_eligible(x, w):
-    if PLANECONV_MAX_HW <= 0 or not x.is_cuda or x.dim() != 4:
-        return False
-    B, Ci, H, W = x.shape
-    return (x.dtype == torch.float32 and w.dtype == torch.float32 and tuple(w.shape[1:]) == (Ci, 3, 3)
-            and H * W <= PLANECONV_MAX_HW and get_lib().dfe_planeconv_supported(B, Ci, int(w.shape[0]), H, W) == 1)
-
-
 def _planeconv_ws(B, Ci, Co, H, W, dev):
     return torch.empty(get_lib().dfe_planeconv_ws_floats(B, Ci, Co, H, W), device=dev, dtype=torch.float32)
 
@@ -1013,41 +1000,6 @@ def wino_conv3x3(x, w, padding=1, transposed=False, dilation=1, bias=None, slope
     return y
 
 
-class ConvBiasActFn(torch.autograd.Function):
-    """``act(conv2d(x, w, stride 1, padding = dilation) + bias)`` for a 3x3 layer the Winograd kernel takes -- net_utils.conv()
-    = Conv2d + LeakyReLU(0.1) (net_utils.py:7-11: FeaturePyramid's stride-1 layers, PWC's context network) -- as ONE launch
-    forward (the epilogue inside the output transform) and one autograd node: backward = dfe_bias_act_bwd (gz = gy act'(y),
-    bias gradient) + the convolution's data / weight gradients (convs.raw_backward)."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, slope, padding, dilation):
-        y = wino_conv3x3(x, w, padding, dilation=dilation, bias=bias, slope=slope)
-        ctx.save_for_backward(x, w, y)
-        ctx.cfg = (float(slope), int(padding), int(dilation), bias is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
-        slope, P, d, has_bias = ctx.cfg
-        gz, gb = _bias_act_bwd(y, gy if _dense_chw(gy) else f32c(gy), slope, has_bias and ctx.needs_input_grad[2])
-        pad = (d, d) if d > 1 else (P, P)
-        gx, gw, _ = convs.raw_backward(gz, x, w, (1, 1), pad, (d, d), ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return gx, gw, gb, None, None, None
-
-
-def conv_bias_act_eligible(x, conv):
-    """A Conv2d whose forward the Winograd kernel runs (convs._wino_eligible: 3x3, stride 1, padding 1 or dilated with
-    padding = dilation, enough tiles and channels, fp32)."""
-    return (WINO_EPILOGUE and conv.bias is not None and conv.groups == 1
-            and convs._wino_eligible(x, conv.weight.shape, conv.in_channels, conv.stride, conv.padding, conv.dilation, conv.groups)
-            and conv.padding == ((1, 1) if conv.dilation == (1, 1) else conv.dilation))
-
-
-def conv_bias_act(x, conv, slope):
-    return ConvBiasActFn.apply(x, conv.weight, conv.bias, float(slope), int(conv.padding[0]), int(conv.dilation[0]))
-
-
 def phase_images(t, d):
     """[B,C,H,W] -> [B d^2, C, H/d, W/d]: the d x d phase images x[:, :, p::d, q::d] stacked along the batch (one strided copy).
     A dilation-d 3x3 convolution with padding d is a dense 3x3 convolution with padding 1 on them."""
@@ -1162,152 +1114,9 @@ class Conv1x1SmallFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
-def conv1x1_small_eligible(x, conv):
-    return (PLANECONV_MAX_HW > 0 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
-            and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
-            and get_lib().dfe_conv1x1_small_supported(x.shape[0], x.shape[1], conv.out_channels, x.shape[2], x.shape[3]) == 1)
-
-
 def conv1x1_small(x, conv, slope):
     """``act(conv(x))`` for an nn.Conv2d with a 1x1 kernel on a tiny plane; slope 1 = no activation."""
     return Conv1x1SmallFn.apply(x, conv.weight, conv.bias, float(slope))
-
-
-class DenseDecodeFn(torch.autograd.Function):
-    """One PWC decoder level's DenseNet-style block (pwc_tf.py:113-118 and the same six lines per level)::
-
-        x0 = conv_0(x); x1 = conv_1(x0); x2 = conv_2(cat(x0, x1)); x3 = conv_3(cat(x1, x2)); x4 = conv_4(cat(x2, x3))
-        flow = predict_flow(cat(x3, x4))                                      -> (flow, x4)
-
-    with every ``conv_k`` = Conv2d(3x3, pad 1, bias) + LeakyReLU(slope).  The convolutions stay MIOpen calls (bias-free);
-    the bias + activation epilogue writes each layer output straight into the channel slices of the two concatenated
-    buffers that consume it (``dfe_bias_act_fwd2``), so no ``torch.cat`` copies exist; the backward pass calls
-    ``aten::convolution_backward`` layer by layer and the epilogue's backward sums the two consumers' gradient slices in
-    place (``dfe_bias_act_bwd2``): no slice copies, no gradient-accumulation adds.  Same arithmetic as the composition."""
-
-    @staticmethod
-    def forward(ctx, slope, x, *wb):
-        import torch.nn.functional as F
-        lib = get_lib()
-        x = f32c(x)
-        w, b = list(wb[0:12:2]), list(wb[1:12:2])          # conv_0..conv_4, predict_flow
-        B, _, H, W = x.shape
-        co = [int(t.shape[0]) for t in w[:5]]              # 128, 128, 96, 64, 32
-        dev = x.device
-        cat = [torch.empty(B, co[k] + co[k + 1], H, W, device=dev, dtype=torch.float32) for k in range(4)]   # [x_k | x_k+1]
-        st = stream_ptr()
-
-        def epilogue(z, k, d1, d1_off, d2, d2_off):
-            c = co[k]
-            check(lib.dfe_bias_act_fwd2(ptr(z), ptr(b[k]), _chan_ptr(d1, d1_off), d1.stride(0), _chan_ptr(d2, d2_off),
-                                        d2.stride(0) if d2 is not None else 0, B, c, H, W, slope, st), "dfe_bias_act_fwd2")
-
-        plane = planeconv_eligible(x, w[0])      # levels 6 / 5: the convolution and its epilogue are this build's kernels
-        if plane:
-            z0 = torch.empty(B, co[0], H, W, device=dev, dtype=torch.float32)
-            x4 = torch.empty(B, co[4], H, W, device=dev, dtype=torch.float32)
-            planeconv_fwd_into(x, w[0], b[0], slope, z0, 0, cat[0], 0)          # x0
-            planeconv_fwd_into(z0, w[1], b[1], slope, cat[0], co[0], cat[1], 0)  # x1
-            planeconv_fwd_into(cat[0], w[2], b[2], slope, cat[1], co[1], cat[2], 0)
-            planeconv_fwd_into(cat[1], w[3], b[3], slope, cat[2], co[2], cat[3], 0)
-            planeconv_fwd_into(cat[2], w[4], b[4], slope, x4, 0, cat[3], co[3])
-        else:
-            fuse = WINO_EPILOGUE
-
-            def layer(inp, k, d1, d1_off, d2, d2_off):
-                """act(conv_k(inp) + b_k) into channels d1_off.. of d1 (None: a fresh tensor, returned) and d2_off.. of d2"""
-                if fuse and convs._wino_eligible(inp, w[k].shape, w[k].shape[1], (1, 1), (1, 1), (1, 1)):
-                    # round 5: the epilogue inside the Winograd kernel's output transform (one launch, no pass over z)
-                    return wino_conv3x3(inp, w[k], 1, bias=b[k], slope=slope, out=d1, out_off=d1_off, out2=d2, out2_off=d2_off)
-                z = convs.raw_forward(inp, w[k], 1, 1)
-                epilogue(z, k, z if d1 is None else d1, d1_off, d2, d2_off)
-                return z
-            z0 = layer(x, 0, None, 0, cat[0], 0)                                # x0: conv_1's input + cat0[:, :128]
-            layer(z0, 1, cat[0], co[0], cat[1], 0)                              # x1
-            layer(cat[0], 2, cat[1], co[1], cat[2], 0)                          # x2
-            layer(cat[1], 3, cat[2], co[2], cat[3], 0)                          # x3
-            x4 = layer(cat[2], 4, None, 0, cat[3], co[3])                       # x4: returned + cat3[:, 64:]
-        if flow_head_eligible(cat[3], w[5], b[5]):
-            flow = flow_head_fwd_raw(cat[3], f32c(w[5]), f32c(b[5]))
-        else:
-            flow = F.conv2d(cat[3], w[5], b[5], 1, 1)
-        ctx.save_for_backward(x, z0, *cat, *w)
-        ctx.slope, ctx.co, ctx.plane = slope, co, plane
-        ctx.set_materialize_grads(False)
-        return flow, x4
-
-    @staticmethod
-    def backward(ctx, g_flow, g_x4):
-        lib = get_lib()
-        saved = ctx.saved_tensors
-        x, x0, cat, w = saved[0], saved[1], list(saved[2:6]), list(saved[6:12])
-        co, slope = ctx.co, ctx.slope
-        B, _, H, W = x.shape
-        dev = x.device
-        st = stream_ptr()
-        need = ctx.needs_input_grad          # (slope, x, w0, b0, ..., wp, bp)
-        nw = lambda k: bool(need[2 + 2 * k])
-        nb = lambda k: bool(need[3 + 2 * k])
-        def cb(g, inp, wt, want_in, want_w, bias_sizes=None, want_b=False):
-            if ctx.plane and not want_b:
-                return planeconv_backward(g, inp, wt, want_in, want_w) + (None,)
-            return convs.raw_backward(g, inp, wt, 1, 1, 1, want_in, want_w, want_b)
-
-        def epilogue_bwd(k, ysrc, y_off, g1, g1_off, g2, g2_off):
-            c = co[k]
-            gz = torch.empty(B, c, H, W, device=dev, dtype=torch.float32)
-            gb = part = None
-            if nb(k):       # only the per-block partial sums now; the level's bias gradients are finished by ONE launch below
-                gb = torch.empty(c, device=dev, dtype=torch.float32)
-                part = torch.empty(lib.dfe_bias_act_partials_floats(B, c, H, W), device=dev, dtype=torch.float32)
-                pending.append((part, gb, c))
-            check(lib.dfe_bias_act_bwd2(_chan_ptr(ysrc, y_off), ysrc.stride(0), _chan_ptr(g1, g1_off), g1.stride(0),
-                                        _chan_ptr(g2, g2_off), g2.stride(0) if g2 is not None else 0,
-                                        ptr(gz), None, ptr(part), B, c, H, W, slope, st), "dfe_bias_act_bwd2")
-            return gz, gb
-
-        pending = []
-
-        gw, gbias = [None] * 6, [None] * 6
-        if g_flow is not None:
-            g_flow = f32c(g_flow)
-            if flow_head_eligible(cat[3], w[5], True):
-                g3, gw[5], gbias[5] = flow_head_bwd_raw(cat[3], f32c(w[5]), g_flow, nw(5), nb(5))
-            else:
-                g3, gw[5], gbias[5] = cb(g_flow, cat[3], w[5], True, nw(5), [2], nb(5))       # d/d cat(x3, x4)
-        else:
-            g3 = torch.zeros_like(cat[3])
-        if g_x4 is not None:     # usually a channel slice of the gradient of torch.cat([flow, x4]): read in place
-            if not _dense_chw(g_x4):
-                g_x4 = f32c(g_x4)
-        gz, gbias[4] = epilogue_bwd(4, cat[3], co[3], g3, co[3], g_x4, 0)                 # x4: cat3 slice + the returned copy
-        g2, gw[4], _ = cb(gz, cat[2], w[4], True, nw(4))                                  # d/d cat(x2, x3)
-        gz, gbias[3] = epilogue_bwd(3, cat[3], 0, g3, 0, g2, co[2])                       # x3
-        g1, gw[3], _ = cb(gz, cat[1], w[3], True, nw(3))                                  # d/d cat(x1, x2)
-        gz, gbias[2] = epilogue_bwd(2, cat[2], 0, g2, 0, g1, co[1])                       # x2
-        g0, gw[2], _ = cb(gz, cat[0], w[2], True, nw(2))                                  # d/d cat(x0, x1)
-        gz, gbias[1] = epilogue_bwd(1, cat[1], 0, g1, 0, g0, co[0])                       # x1
-        gx0, gw[1], _ = cb(gz, x0, w[1], True, nw(1))                                     # d/d x0 through conv_1
-        gz, gbias[0] = epilogue_bwd(0, cat[0], 0, g0, 0, gx0, 0)                          # x0
-        if pending:
-            n = len(pending)
-            parts = (ctypes.c_void_p * n)(*[t[0].data_ptr() for t in pending])
-            outs = (ctypes.c_void_p * n)(*[t[1].data_ptr() for t in pending])
-            chans = (ctypes.c_int * n)(*[t[2] for t in pending])
-            check(lib.dfe_bias_grad_final_multi(parts, outs, chans, n, B, H, W, st), "dfe_bias_grad_final_multi")
-        gx, gw[0], _ = cb(gz, x, w[0], bool(need[1]), nw(0))
-        out = [None, gx]
-        for k in range(6):
-            out += [gw[k], gbias[k]]
-        return tuple(out)
-
-
-def dense_decode(x, convs, predict_flow, slope=0.1):
-    """(flow, x4) of one PWC decoder level; ``convs``: the five Conv2d modules, ``predict_flow``: the 3x3 flow head."""
-    wb = []
-    for c in list(convs) + [predict_flow]:
-        wb += [c.weight, c.bias]
-    return DenseDecodeFn.apply(float(slope), x, *wb)
 
 
 # --------------------------------------------------------------------------- grouped BatchNorm (+ residual + ReLU)
@@ -1431,13 +1240,6 @@ def flow_head_bwd_raw(x, weight, gout, want_w=True, want_b=True):
     return gx, gw, gb
 
 
-def flow_head_eligible(x, weight, bias=None):
-    """PWC's predict_flow layers (pwc_tf.py:39-40): two output channels, 3x3, channel count a multiple of 8."""
-    return (FLOW_HEAD and x.is_cuda
-            and x.dtype == torch.float32 and x.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and weight.shape[0] == 2
-            and weight.shape[1] == x.shape[1] and x.shape[1] % 8 == 0 and bias is not None)
-
-
 class FlowHeadFn(torch.autograd.Function):
     """``F.conv2d(x, weight, bias, 1, 1)`` with two output channels on the rolling-window head kernels
     (csrc/ops_disphead.hip)."""
@@ -1455,51 +1257,14 @@ class FlowHeadFn(torch.autograd.Function):
         return (gx if ctx.needs_input_grad[0] else None), gw, gb
 
 
-class ThinConv3x3Fn(torch.autograd.Function):
-    """Valid 3x3 convolution of a pre-padded activation, bias-free, for the decoder's thin full-resolution layers (at most 32
-    output channels at >= 64x208 pixels).  Forward and data gradient: convs.raw_forward / raw_backward (the half-tile Winograd
-    kernel since round 4; round 3's dfe_thin_conv3x3 was removed in round 5).  Weight gradient -- a (Co x 9 Ci) contraction over
-    B*H*W pixels: the Winograd-domain kernel from 32 input channels up, dfe_wgrad3x3_fwd (fp32 MFMA straight from NCHW) for 16 -> 16."""
-
-    @staticmethod
-    def forward(ctx, p, weight):
-        ctx.save_for_backward(p, weight)
-        return convs.raw_forward(p, weight)
-
-    @staticmethod
-    def backward(ctx, gy):
-        lib = get_lib()
-        p, weight = ctx.saved_tensors
-        gy = f32c(gy)
-        B, Ci, Hp, Wp = p.shape
-        Co, H, W = weight.shape[0], Hp - 2, Wp - 2
-        gp = gw = None
-        if ctx.needs_input_grad[0]:
-            gp = convs.raw_backward(gy, p, weight, 1, 0, 1, True, False)[0]
-        if ctx.needs_input_grad[1]:
-            if Ci >= 32 and convs.WINO_WGRAD:
-                # round 5: the Winograd-domain kernel is faster wherever there are >= 32 input channels (96 -> 32 at 130x418 x 12:
-                # 229 against 374 us; 64 -> 32 at 66x210: 60 against 70; 32 -> 16 at 130x418: 102 against ~124); the 16 -> 16
-                # layer at 258x834 stays here (133 against 304)
-                gw = wino_wgrad3x3(p, gy, 0)
-            else:
-                gw = torch.empty_like(weight)
-                part = torch.empty(lib.dfe_wgrad3x3_partials_floats(B, Ci, Co, H, W), device=p.device)
-                check(lib.dfe_wgrad3x3_fwd(ptr(p), ptr(gy), ptr(gw), ptr(part), B, Ci, Co, H, W, stream_ptr()), "dfe_wgrad3x3_fwd")
-        return gp, gw
-
-
-def thin_conv3x3_eligible(p, weight):
-    """Layers the MFMA weight gradient is measured to win on: <= 32 output channels at >= 64x208 pixels (the decoder's
-    last stages), channel counts multiples of 16, width a multiple of 16."""
-    Co, Ci = weight.shape[0], weight.shape[1]
-    H, W = p.shape[2] - 2, p.shape[3] - 2
-    return (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and tuple(weight.shape[2:]) == (3, 3)
-            and Co <= 32 and Co % 16 == 0 and Ci % 16 == 0 and W % 16 == 0 and H * W >= 64 * 208)
-
-
-def conv3x3_valid(p, weight):
-    """3x3 convolution without padding or bias of a pre-padded activation (the decoder's ConvBlock convolutions)."""
-    if thin_conv3x3_eligible(p, weight):
-        return ThinConv3x3Fn.apply(p, weight)
-    return convs.conv2d(p, weight)
+def wgrad3x3(p, gy):
+    """Weight gradient [Co,Ci,3,3] of a valid 3x3 convolution of the pre-padded activation p [B,Ci,H+2,W+2] for the output gradient
+    gy [B,Co,H,W], on dfe_wgrad3x3_fwd (fp32 MFMA straight from NCHW): the depth decoder's thin full-resolution layers."""
+    lib = get_lib()
+    p, gy = f32c(p), f32c(gy)
+    B, Ci, Hp, Wp = p.shape
+    Co, H, W = int(gy.shape[1]), Hp - 2, Wp - 2
+    gw = torch.empty(Co, Ci, 3, 3, device=p.device, dtype=torch.float32)
+    part = torch.empty(lib.dfe_wgrad3x3_partials_floats(B, Ci, Co, H, W), device=p.device)
+    check(lib.dfe_wgrad3x3_fwd(ptr(p), ptr(gy), ptr(gw), ptr(part), B, Ci, Co, H, W, stream_ptr()), "dfe_wgrad3x3_fwd")
+    return gw

@@ -14,6 +14,7 @@ import ctypes
 
 import torch
 
+from . import ops
 from ._lib import check, get_lib, stream_ptr
 
 
@@ -199,6 +200,5 @@ class FusedAdam(torch.optim.Optimizer):
                         self.state[p]["step"] = new
         # the parameters changed behind autograd's back (raw pointers, no version bump): the Winograd kernel's cached
         # transformed filters are rebuilt here, in one launch on this stream, right behind the update
-        from . import ops
         ops.wino_weights.refresh()
         return loss

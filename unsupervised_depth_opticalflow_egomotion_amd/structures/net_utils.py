@@ -8,20 +8,14 @@ from .. import convs, ops
 
 class ConvAct(nn.Sequential):
     """Conv2d(bias=True) + LeakyReLU(slope) with the reference's child names (``.0`` = the Conv2d).  On the GPU the
-    convolution runs on MIOpen without its bias and the bias + activation epilogue is one in-place HIP pass
-    (ops.bias_act; the backward pass yields the bias gradient from the same read)."""
+    layer goes through convs.conv_act: the small-plane kernel (FeaturePyramid's top levels, 8x26 and 4x13), the Winograd kernel
+    with the bias + LeakyReLU inside its output transform, or the routed convolution without its bias and one in-place
+    epilogue pass (ops.bias_act; the backward pass yields the bias gradient from the same read)."""
 
     def forward(self, x):
         if not x.is_cuda:
             return super().forward(x)
-        c = self[0]
-        if (c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1
-                and ops.planeconv_eligible(x, c.weight)):   # FeaturePyramid's top levels (8x26, 4x13): small-plane MFMA kernels
-            return ops.planeconv_act(x, c.weight, c.bias, self[1].negative_slope)
-        if ops.conv_bias_act_eligible(x, c):        # round 5: bias + LeakyReLU inside the Winograd kernel's output transform
-            return ops.conv_bias_act(x, c, self[1].negative_slope)
-        z = convs.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
-        return ops.bias_act(z, c.bias, self[1].negative_slope)
+        return convs.conv_act(x, self[0], self[1].negative_slope, ("plane", "wino_act"))      # never the 1x1 kernel
 
 
 def conv(in_planes, out_planes, kernel_size=3, stride=1, padding=1, dilation=1):

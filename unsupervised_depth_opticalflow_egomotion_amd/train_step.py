@@ -3,6 +3,8 @@ backward, Adam.  Used by train.py and by bench.py's ``train_step`` workload (the
 CPU-baseline leg that drives the oracle, lives in bench.py -- nothing in this package imports the oracle)."""
 import types
 
+from . import ops
+
 DEFAULT_CFG = dict(
     dataset="kitti_depth", num_scales=3, num_input_frames=3, flow_consist_alpha=0.01, flow_consist_beta=0.5,
     h_flow_consist_alpha=0.01, h_flow_consist_beta=0.5, geometric_ratio=0.3, geometric_num=6000, pose_beta=1,
@@ -136,7 +138,6 @@ class GraphedTrainStep:
         # The captured filter refresh (ops.WinoWeightCache.refresh inside optimizer.step) reads the cache's device tables of THIS
         # moment; the cache replaces them when another model registers filters.  Hold them: a replay must never read freed memory
         # (found by the eager-twin test: the twin's registration freed the table, the next replay scattered filters through it).
-        from . import ops
         self._cache_tables = (ops.wino_weights.table, ops.wino_weights.blockmap)
         self._hyper = self._hyper_now()
         self._epoch = getattr(optimizer, "capture_epoch", 0)
@@ -192,7 +193,6 @@ class GraphedTrainStep:
                             t0 = float(st["step"])
                             break
                     dc[0].fill_(t0)
-        from . import ops
         ops.wino_weights.invalidate()       # parameters written in place without a step: cached transformed filters are stale
         ops.wino_weights.refresh()
 
