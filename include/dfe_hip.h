@@ -32,10 +32,11 @@ extern "C" {
 #define DFE_MAX_SCALES 8
 /* Bumped whenever an exported signature changes, an entry point is removed or the host side starts to rely on a new one
  * (2: round 5 changed dfe_wino_wgrad3x3 and removed dfe_thin_conv3x3 / dfe_cast_*; 3: round 6 added dfe_pwc_level_map_bytes /
- * _fwd_map / _bwd_map, which ops.py calls).  _lib.py compares the library's value with this header's.  It also reads every
+ * _fwd_map / _bwd_map, which ops.py calls; 4: dfe_sconv_fwd / _dgrad and dfe_conv1x1s2_fwd / _wgrad with their host-only queries,
+ * which the deterministic mode calls).  _lib.py compares the library's value with this header's.  It also reads every
  * ctypes argument and return type from the prototypes below (a new entry point is bound by declaring it here), so a prototype
  * stays within: pointers of any kind, int, long, float, double, unsigned long long; returning int, long or const char*. */
-#define DFE_ABI_VERSION 3
+#define DFE_ABI_VERSION 4
 
 int dfe_abi_version(void);
 const char* dfe_error_string(int code);
@@ -380,6 +381,44 @@ int dfe_sconv_tune(int blocks, int rows);
 long dfe_sconv_wgrad_floats(int B, int Ci, int Co, int H, int W, int K, int stride, int P);
 int dfe_sconv_wgrad(const float* x, long x_batch_stride, const float* gy, long gy_batch_stride, float* gweight, float* ws, int B,
                     int Ci, int Co, int H, int W, int K, int stride, int P, void* stream);
+/* Forward pass and data gradient of the same layers (stride 2, padding K / 2; csrc/ops_sconv.hip), one launch each after a
+ * filter re-layout; only the deterministic mode (convs.set_deterministic) routes layers here: every sum has one fixed order,
+ * whatever the allocator hands out.  Ho = (H + 2 (K / 2) - K) / 2 + 1, Wo alike.
+ * dfe_sconv_fwd:   y [B,Co,Ho,Wo] = act(conv(x [B,Ci,H,W], weight [Co,Ci,K,K]) + bias[co]), K in {3, 5, 7}; bias may be NULL;
+ *                  act(v) = v > 0 ? v : slope * v (slope 1: none, 0: ReLU).
+ * dfe_sconv_dgrad: gx [B,Ci,H,W] = the data gradient for gy [B,Co,Ho,Wo], K in {1, 3, 5} (K = 1: the 1x1 stride-2 shortcuts;
+ *                  the odd rows and columns of gx are written with zeros).  Every element of gx is written.
+ * ws: dfe_sconv_fwd_floats / dfe_sconv_dgrad_floats floats (host-only queries): the packed filter and, for layers whose tiles
+ * cannot fill the chip, the partial outputs of the channel splits, added in split order.  0 floats / DFE_ERR_UNSUPPORTED: a
+ * shape outside the kernel family (another K; a sample of x -- for the data gradient, of gy -- of fewer than 4 floats).
+ * Memory: x, gy, weight, bias, y and gx need dword alignment only and may be batch-strided views (any batch stride >= the dense
+ * sample, DFE_ERR_DIMS below it); the staging loads' safe address is the first 16 bytes of a sample of x (of gy), hence the
+ * 4-float rule.  Reads stay inside the B samples of x / gy, weight and bias [Co]; writes inside the B samples of y / gx (the
+ * gaps of a larger batch stride are not touched) and the first *_floats() floats of ws.  ws must be 16-byte aligned
+ * (DFE_ERR_UNSUPPORTED otherwise) and needs no initialisation.  Every refusal comes before the first launch. */
+long dfe_sconv_fwd_floats(int B, int Ci, int Co, int H, int W, int K);
+int dfe_sconv_fwd(const float* x, long x_batch_stride, const float* weight, const float* bias, float slope, float* y,
+                  long y_batch_stride, float* ws, int B, int Ci, int Co, int H, int W, int K, void* stream);
+long dfe_sconv_dgrad_floats(int B, int Ci, int Co, int H, int W, int K);
+int dfe_sconv_dgrad(const float* gy, long gy_batch_stride, const float* weight, float* gx, long gx_batch_stride, float* ws, int B,
+                    int Ci, int Co, int H, int W, int K, void* stream);
+/* The 1x1 stride-2 convolutions without padding or bias (depth_model.py:31-36, the ResNet down-sampling shortcuts 64 -> 128,
+ * 128 -> 256, 256 -> 512; a BatchNorm follows) for the same mode (csrc/ops_conv1x1s2.hip; the data gradient is dfe_sconv_dgrad
+ * with K = 1).  x [B,Ci,H,W], weight [Co,Ci] (= [Co,Ci,1,1]), Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.
+ * dfe_conv1x1s2_fwd:   y [B,Co,Ho,Wo] = sum_ci weight[co][ci] x[b][ci][2 oy][2 ox].  No workspace.
+ * dfe_conv1x1s2_wgrad: gweight [Co,Ci] = sum over b and the output pixels of gy[b][co][oy][ox] x[b][ci][2 oy][2 ox]; the pixel
+ *                      range is split over one resident round of blocks and the partials (ws: dfe_conv1x1s2_wgrad_floats
+ *                      floats) are added in split order: no atomics.
+ * dfe_conv1x1s2_supported / _wgrad_floats are host-only; 0 / DFE_ERR_UNSUPPORTED: B Ho Wo, a sample or the filter >= 2^30.
+ * Memory: every pointer needs dword alignment only; x, y and gy may be batch-strided views of any size (every access is
+ * predicated on its own index: nothing outside the B samples of x -- of which only even rows and columns are read -- , gy,
+ * weight, the B samples of y, gweight and the stated floats of ws is touched); ws needs no initialisation. */
+int dfe_conv1x1s2_supported(int B, int Ci, int Co, int H, int W);
+int dfe_conv1x1s2_fwd(const float* x, long x_batch_stride, const float* weight, float* y, long y_batch_stride, int B, int Ci, int Co,
+                      int H, int W, void* stream);
+long dfe_conv1x1s2_wgrad_floats(int B, int Ci, int Co, int H, int W);
+int dfe_conv1x1s2_wgrad(const float* x, long x_batch_stride, const float* gy, long gy_batch_stride, float* gweight, float* ws, int B,
+                        int Ci, int Co, int H, int W, void* stream);
 /* the same for a DILATED 3x3 convolution with padding = dilation (pwc_tf.py:31-36 context network: dilation 2, 4, 8, 16): the
  * Winograd tiles live on the dilation x dilation phase images; H and W must be multiples of the dilation.  y has x's size. */
 int dfe_wino_conv3x3_dilated(const float* x, const float* weight, float* y, long y_batch_stride, float* wbuf, int B, int Ci, int Co,

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""The strided weight gradient of csrc/ops_sconv.hip against MIOpen (aten, its layout transposes and fills included) on the networks'
-stride-2 layers: parity against float64 aten first (odd sizes, ragged channel counts), then HIP-event time per call.
-(profiles/r05_sconv_bench_all.md was made by this tool while the forward and data-gradient kernels of the family existed.)
+"""The strided convolutions of csrc/ops_sconv.hip and the 1x1 stride-2 kernels of csrc/ops_conv1x1s2.hip against MIOpen's whole call
+(aten, its layout transposes and fills included) on the networks' stride-2 layers: parity against float64 aten first (odd
+sizes, ragged channel counts), then HIP-event time per call.  --pass picks the passes: wgrad (the default: the one pass the
+default mode routes here), fwd, dgrad -- the passes the deterministic mode adds (profiles/deterministic_mode_layers.md).
 
-    python tools/sconv_bench.py [--iters 20] [--check-only] [--blocks 512,768]
+    python tools/sconv_bench.py [--iters 20] [--check-only] [--pass fwd,dgrad,wgrad] [--blocks 512,768]
 """
 import argparse, os, sys
 import torch
@@ -51,16 +52,29 @@ def aten_bwd(x, w, gy, S, P, mask):
     return torch.ops.aten.convolution_backward(gy, x, w, None, [S, S], [P, P], [1, 1], False, [0, 0], 1, mask)
 
 
-OURS = {
-    "wgrad": lambda x, w, gy, K, S, P: ops.sconv_wgrad(x, gy, K, S, P),
+OURS = {       # a 1x1 layer: dfe_conv1x1s2_fwd / _wgrad, and dfe_sconv_dgrad's K = 1
+    "wgrad": lambda x, w, gy, K, S, P: ops.conv1x1s2_wgrad(x, gy) if K == 1 else ops.sconv_wgrad(x, gy, K, S, P),
+    "fwd": lambda x, w, gy, K, S, P: ops.conv1x1s2_fwd(x, w) if K == 1 else ops.sconv_fwd(x, w),
+    "dgrad": lambda x, w, gy, K, S, P: ops.sconv_dgrad(gy, w, x.shape),
 }
 ATEN = {
     "wgrad": lambda x, w, gy, K, S, P: aten_bwd(x, w, gy, S, P, [False, True, False])[1],
     "fwd": lambda x, w, gy, K, S, P: torch.nn.functional.conv2d(x, w, None, S, P),
     "dgrad": lambda x, w, gy, K, S, P: aten_bwd(x, w, gy, S, P, [True, False, False])[0],
 }
+def _x(shape):
+    return shape[:2] + shape[3:5]
+
+
+def _s2(shape):      # the forward / data-gradient kernels: stride 2, padding K // 2
+    return shape[6] == 2 and shape[7] == shape[5] // 2
+
+
 SUPPORTED = {
-    "wgrad": lambda shape: ops.sconv_wgrad_supported(shape[:1] + shape[1:2] + shape[3:5], shape[2], shape[5], shape[6], shape[7]),
+    "wgrad": lambda shape: (_s2(shape) and ops.conv1x1s2_supported(_x(shape), shape[2])) if shape[5] == 1 else
+    ops.sconv_wgrad_supported(_x(shape), shape[2], shape[5], shape[6], shape[7]),
+    "fwd": lambda shape: _s2(shape) and (ops.conv1x1s2_supported(_x(shape), shape[2]) if shape[5] == 1 else ops.sconv_fwd_supported(_x(shape), shape[2], shape[5])),
+    "dgrad": lambda shape: _s2(shape) and ops.sconv_dgrad_supported(_x(shape), shape[2], shape[5]),
 }
 
 

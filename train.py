@@ -21,7 +21,7 @@ import time
 import torch
 import yaml
 
-from unsupervised_depth_opticalflow_egomotion_amd import ddp, ops, prepared_data, synthetic
+from unsupervised_depth_opticalflow_egomotion_amd import convs, ddp, ops, prepared_data, synthetic
 from unsupervised_depth_opticalflow_egomotion_amd.models import get_model
 from unsupervised_depth_opticalflow_egomotion_amd.train_step import train_step, make_optimizer, GraphedTrainStep, LOSS_WEIGHT_ATTR
 
@@ -54,6 +54,10 @@ def train(cfg):
     if dev is None:
         raise RuntimeError("train.py needs a HIP device: the loss stack has no CPU fallback")
     ops.set_align_corners(bool(getattr(cfg, "align_corners", False)))
+    # --deterministic / the YAML key switch the mode on; they never switch off what DFE_DETERMINISTIC=1 asked for
+    convs.set_deterministic(convs.DETERMINISTIC or bool(getattr(cfg, "deterministic", False)))
+    if convs.DETERMINISTIC:      # the step is a pure function of weights and inputs: the initial weights come from a seed too (YAML 'seed')
+        torch.manual_seed(int(getattr(cfg, "seed", 0)))
     model = get_model(cfg.mode)(cfg)
     if cfg.mode == "geom":
         for attr, path in (("flow_pretrained_model", ("fpyramid.", "pwc_model.")),
@@ -170,6 +174,10 @@ if __name__ == "__main__":
     ap.add_argument("--profile", action="store_true",
                     help="roctx ranges around every HIP launcher (rocprofv3 --marker-trace) and the reference Profiler's forward / backward / "
                          "optimizer wall times at every log interval (synchronises the device at each mark)")
+    ap.add_argument("--deterministic", action="store_const", const=True, default=None,
+                    help="no convolution of the step reaches MIOpen: every pass on this build's fixed-order kernels, so that loss, outputs "
+                         "and gradients repeat bit for bit run after run and process after process (same build, GPU model, batch and "
+                         "inputs; slower; also the YAML key 'deterministic' and DFE_DETERMINISTIC=1)")
     ap.add_argument("--device_pipeline", action="store_true",
                     help="feed raw uint8 triplets and run resize / flip / normalise on the device (ops.prepare_triplets)")
     args = ap.parse_args()
@@ -178,7 +186,7 @@ if __name__ == "__main__":
     cfg["img_hw"] = (cfg["img_hw"][0], cfg["img_hw"][1])
     cfg["model_dir"] = os.path.join(args.model_dir or "./models", args.mode)
     for k, v in vars(args).items():        # every CLI attribute overrides / extends the YAML (train.py:272-274)
-        if k in ("model_dir",) or (k in ("num_iterations", "data_source", "prepared_base_dir") and v is None):
+        if k in ("model_dir",) or (k in ("num_iterations", "data_source", "prepared_base_dir", "deterministic") and v is None):
             continue
         cfg[k] = v
     os.makedirs(cfg["model_dir"], exist_ok=True)

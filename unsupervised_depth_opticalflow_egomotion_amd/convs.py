@@ -1,4 +1,5 @@
-"""The one door to the networks' convolutions: MIOpen's, or this build's fp32 matrix-core kernels where they win.  Everything is fp32.
+"""The one door to the networks' convolutions: MIOpen's, or this build's fp32 matrix-core kernels where they win -- or, in the
+deterministic mode (``set_deterministic``), this build's kernels for every pass and an error where there is none.  Everything is fp32.
 
 ``plan`` is the one place that decides which kernel a convolution's forward pass, data gradient and weight gradient run on;
 every door below (``conv2d``, ``Conv2d``, ``conv_act``, ``conv3x3_valid``, ``dense_decode``, ``raw_forward`` / ``raw_backward``)
@@ -16,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import miopen_tuning, ops
-from ._lib import check, f32c, get_lib, ptr, stream_ptr
+from ._lib import DfeError, check, f32c, get_lib, ptr, stream_ptr
 
 miopen_tuning.activate()      # before the first convolution: MIOpen reads MIOPEN_USER_DB_PATH when it first opens its databases
 
@@ -41,14 +42,29 @@ PHASE_MIN_DILATION = int(os.environ.get("DFE_PHASE_CONV", "8"))
 # 256x832 frame: 52 and 208 pixels; PoseCNN's 2x7 planes); 0 = every such layer stays on MIOpen
 PLANECONV_MAX_HW = int(os.environ.get("DFE_PLANECONV_MAX_HW", "208"))
 FLOW_HEAD = os.environ.get("DFE_FLOW_HEAD", "1") != "0"           # PWC's two-channel flow heads on the rolling-window head kernels
+# The deterministic mode: no convolution of a HIP tensor reaches MIOpen / ATen.  Every stride-2 layer runs on dfe_sconv_* /
+# dfe_conv1x1s2_*, every 3x3 stride-1 layer on the Winograd kernels whatever the thresholds above say (they, DFE_SCONV, DFE_WINO_WGRAD
+# and DFE_WINO_DILATED do not limit here), the small-plane / flow-head / wgrad3x3 layers stay where they are, and a layer no kernel
+# of this build takes raises DfeError.  MIOpen's weight gradients add with float atomics and its solver choice follows the workspace
+# the allocator happens to hand it; these kernels add in one fixed order.  What it promises and costs: README "Reproducible".
+DETERMINISTIC = os.environ.get("DFE_DETERMINISTIC", "0") == "1"
 
 # The kernel of each pass of one layer: "miopen", or "wino" (dfe_wino_conv3x3; as a data gradient, on the transposed filter), "wino_act"
 # (with the bias + activation epilogue), "phase" (a dense convolution on the phase images, itself planned), "wino_wgrad", "sconv_wgrad",
-# "wgrad3x3" (dfe_wgrad3x3_fwd), and "plane" / "conv1x1" / "flow_head", whose three passes are their own (dfe_planeconv_*, ...)
+# "wgrad3x3" (dfe_wgrad3x3_fwd), and "plane" / "conv1x1" / "flow_head", whose three passes are their own (dfe_planeconv_*, ...).
+# The deterministic mode adds "sconv" (dfe_sconv_fwd / dfe_sconv_dgrad), "sconv_act" (with the bias + activation epilogue),
+# "conv1x1s2" (dfe_conv1x1s2_fwd / _wgrad) and, as a data gradient only, "none": no kernel takes it, and asking for it raises
+# (the 7x7 stems, whose input is the image).
 Plan = collections.namedtuple("Plan", "fwd dgrad wgrad")
 MIOPEN = Plan("miopen", "miopen", "miopen")
 _PLANE, _CONV1X1, _HEAD = Plan("plane", "plane", "plane"), Plan("conv1x1", "conv1x1", "conv1x1"), Plan("flow_head", "flow_head", "flow_head")
 _plans = {}
+
+
+def set_deterministic(flag):
+    """Switch the deterministic mode (DFE_DETERMINISTIC) after import; plans are memoised per setting."""
+    global DETERMINISTIC
+    DETERMINISTIC = bool(flag)
 
 
 def _pair(v):
@@ -60,15 +76,15 @@ def _out_hw(shape, w, stride, padding, dilation):
             (shape[3] + 2 * padding[1] - dilation[1] * (w[3] - 1) - 1) // stride[1] + 1)
 
 
-def _wino(f32, shape, w, cin, stride, padding, dilation):
+def _wino(f32, shape, w, cin, stride, padding, dilation, det=False):
     """[B,cin,H,W] convolved 3x3 / stride 1 with ``padding`` in {0, 1} (or dilated with padding = dilation dividing H and W):
-    enough tiles and reduction channels for dfe_wino_conv3x3?"""
-    if WINO_MIN_TILES <= 0 or not f32 or w[2:] != (3, 3) or stride != (1, 1) or dilation[0] != dilation[1]:
+    enough tiles and reduction channels for dfe_wino_conv3x3?  ``det``: whether the kernel takes the layer at all."""
+    if (WINO_MIN_TILES <= 0 and not det) or not f32 or w[2:] != (3, 3) or stride != (1, 1) or dilation[0] != dilation[1]:
         return False
     B, C, H, W = shape
     d = dilation[0]
     if d > 1:
-        if padding != (d, d) or H % d or W % d or H // d < 2 or W // d < 2 or not WINO_DILATED:
+        if padding != (d, d) or H % d or W % d or H // d < 2 or W // d < 2 or not (WINO_DILATED or det):
             return False
         Ho, Wo, tiles_b = H // d, W // d, B * d * d
     else:
@@ -77,24 +93,25 @@ def _wino(f32, shape, w, cin, stride, padding, dilation):
         Ho, Wo, tiles_b = H + 2 * padding[0] - 2, W + 2 * padding[0] - 2, B
     if C != cin or Ho < 1 or Wo < 1:
         return False
-    return tiles_b * ((Ho + 1) // 2) * ((Wo + 1) // 2) >= WINO_MIN_TILES and C >= WINO_MIN_CHANNELS and B * C * H * W < (1 << 30)
+    return (det or (tiles_b * ((Ho + 1) // 2) * ((Wo + 1) // 2) >= WINO_MIN_TILES and C >= WINO_MIN_CHANNELS)) and B * C * H * W < (1 << 30)
 
 
-def _wino_wgrad(f32, shape, w, stride, padding, dilation):
-    """dfe_wino_wgrad3x3 for the filter of a 3x3 stride-1 layer on x [B,Ci,H,W]: >= 16 channels on both sides, enough work"""
+def _wino_wgrad(f32, shape, w, stride, padding, dilation, det=False):
+    """dfe_wino_wgrad3x3 for the filter of a 3x3 stride-1 layer on x [B,Ci,H,W]: >= 16 channels on both sides, enough work
+    (``det``: any channel count, any amount of work, any dilation whose phase images are whole)"""
     d = dilation[0]
-    if not WINO_WGRAD or not f32 or w[2:] != (3, 3) or stride != (1, 1) or dilation != (d, d):
+    if not (WINO_WGRAD or det) or not f32 or w[2:] != (3, 3) or stride != (1, 1) or dilation != (d, d):
         return False
-    if d > 1 and not (d <= WINO_WGRAD_MAX_DILATION and padding == (d, d) and shape[2] % d == 0 and shape[3] % d == 0):
+    if d > 1 and not ((det or d <= WINO_WGRAD_MAX_DILATION) and padding == (d, d) and shape[2] % d == 0 and shape[3] % d == 0):
         return False
     if d == 1 and padding not in ((0, 0), (1, 1)):
         return False
     Co, Ci = w[0], w[1]
     ho, wo = _out_hw(shape, w, stride, padding, dilation)
-    if Ci != shape[1] or min(Co, Ci) < 16 or ho < 1 or wo < 1:      # (16 -> 16 at 128x416 x 12: 83 against MIOpen's 129 us)
+    if Ci != shape[1] or (min(Co, Ci) < 16 and not det) or ho < 1 or wo < 1:      # (16 -> 16 at 128x416 x 12: 83 against MIOpen's 129 us)
         return False
     n_out = shape[0] * Co * ho * wo
-    return float(n_out) * Ci * 9 >= WINO_WGRAD_MIN_MACS and shape[0] * shape[1] * shape[2] * shape[3] < (1 << 30) and n_out < (1 << 30)
+    return (det or float(n_out) * Ci * 9 >= WINO_WGRAD_MIN_MACS) and shape[0] * shape[1] * shape[2] * shape[3] < (1 << 30) and n_out < (1 << 30)
 
 
 def _sconv_wgrad(f32, shape, w, stride, padding, dilation):
@@ -109,6 +126,8 @@ def _raw(f32, shape, w, stride, padding, dilation):
     """A bias-free fp32 layer inside an autograd Function: Winograd forward / data gradient where there are enough tiles (the
     data gradient is judged on the output gradient, whose channels are the filter's outputs, as a padding-1 layer -- it is
     launched with padding 2 for a valid convolution), the weight gradient in the Winograd domain or on dfe_sconv_wgrad."""
+    if DETERMINISTIC:
+        return _det_raw(f32, shape, w, stride, padding, dilation, 1)
     d = dilation[0]
     gy = (shape[0], w[0]) + _out_hw(shape, w, stride, padding, dilation)
     return Plan("wino" if _wino(f32, shape, w, w[1], stride, padding, dilation) else "miopen",
@@ -116,6 +135,27 @@ def _raw(f32, shape, w, stride, padding, dilation):
                 and _wino(f32, gy, w, w[0], stride, (d, d) if d > 1 else (1, 1), dilation) else "miopen",
                 "wino_wgrad" if _wino_wgrad(f32, shape, w, stride, padding, dilation) else
                 "sconv_wgrad" if _sconv_wgrad(f32, shape, w, stride, padding, dilation) else "miopen")
+
+
+def _det_raw(f32, shape, w, stride, padding, dilation, groups):
+    """The deterministic mode's kernels of a bias-free layer, or DfeError naming it: stride 2 on dfe_sconv_* (k in {3, 5, 7}, padding
+    k // 2; no data gradient at k = 7) or dfe_conv1x1s2_* (k = 1, padding 0; its data gradient is dfe_sconv_dgrad's k = 1), 3x3 stride 1
+    on the Winograd kernels at any size."""
+    k, d = w[2], dilation[0]
+    if f32 and groups == 1 and w[1] == shape[1] and w[3] == k and shape[0] * shape[1] * shape[2] * shape[3] < (1 << 30):
+        if stride == (2, 2) and dilation == (1, 1):
+            if (k in (3, 5, 7) and padding == (k // 2, k // 2) and ops.sconv_fwd_supported(shape, w[0], k)
+                    and ops.sconv_wgrad_supported(shape, w[0], k, 2, k // 2)):
+                return Plan("sconv", "sconv" if ops.sconv_dgrad_supported(shape, w[0], k) else "none", "sconv_wgrad")
+            if k == 1 and padding == (0, 0) and ops.conv1x1s2_supported(shape, w[0]) and ops.sconv_dgrad_supported(shape, w[0], 1):
+                return Plan("conv1x1s2", "sconv", "conv1x1s2")
+        gy = (shape[0], w[0]) + _out_hw(shape, w, stride, padding, dilation)
+        if (_wino(f32, shape, w, w[1], stride, padding, dilation, True) and _wino_wgrad(f32, shape, w, stride, padding, dilation, True)
+                and _wino(f32, gy, w, w[0], stride, (d, d) if d > 1 else (1, 1), dilation, True)):
+            return Plan("wino", "wino", "wino_wgrad")
+    raise DfeError("deterministic mode (DFE_DETERMINISTIC / convs.set_deterministic): no fixed-order kernel of this build takes the "
+                   "convolution of x %s (%s) with w %s, stride %s, padding %s, dilation %s, groups %d; MIOpen would, and is not "
+                   "reproducible" % (tuple(shape), "fp32" if f32 else "not fp32", tuple(w), stride, padding, dilation, groups))
 
 
 def _phase(shape, w, stride, padding, dilation):
@@ -127,6 +167,8 @@ def _phase(shape, w, stride, padding, dilation):
 
 def _conv2d(f32, shape, w, stride, padding, dilation, groups):
     """``conv2d``: a layer none of whose forward pass and weight gradient is ours is one ATen call (its data gradient MIOpen's too)"""
+    if DETERMINISTIC:
+        return _det_raw(f32, shape, w, stride, padding, dilation, groups)
     if groups != 1:
         return MIOPEN
     r = _raw(f32, shape, w, stride, padding, dilation)
@@ -154,7 +196,10 @@ def _thin(f32, contiguous, shape, w):
 
 
 def _route(ctx, f32, shape, w, stride, padding, dilation, groups, bias, fuse, act, plane, contiguous):
+    det = DETERMINISTIC
     if len(shape) != 4:
+        if det:
+            raise DfeError("deterministic mode: no kernel of this build takes a convolution of a %d-dimensional input %s" % (len(shape), tuple(shape)))
         return MIOPEN
     std3 = w[2:] == (3, 3) and stride == (1, 1) and padding == (1, 1) and dilation == (1, 1) and groups == 1
     if ctx == "raw":
@@ -162,9 +207,12 @@ def _route(ctx, f32, shape, w, stride, padding, dilation, groups, bias, fuse, ac
     if ctx == "conv_act":
         if "plane" in fuse and std3 and _plane(f32, shape, w):      # FeaturePyramid's top levels (8x26, 4x13), PoseCNN's 2x7 planes
             return _PLANE
-        if ("wino_act" in fuse and WINO_EPILOGUE and bias and groups == 1 and _wino(f32, shape, w, w[1] * groups, stride, padding, dilation)
+        if ("wino_act" in fuse and WINO_EPILOGUE and bias and groups == 1 and _wino(f32, shape, w, w[1] * groups, stride, padding, dilation, det)
                 and padding == ((1, 1) if dilation == (1, 1) else dilation)):
             return _raw(f32, shape, w, stride, padding, dilation)._replace(fwd="wino_act")
+        if det and "sconv_act" in fuse and bias and stride == (2, 2) and w[2] > 1:      # bias + activation inside dfe_sconv_fwd
+            r = _det_raw(f32, shape, w, stride, padding, dilation, groups)
+            return r._replace(fwd="sconv_act") if r.fwd == "sconv" else r
         if ("conv1x1" in fuse and PLANECONV_MAX_HW > 0 and f32 and w[2:] == (1, 1) and stride == (1, 1) and padding == (0, 0) and groups == 1
                 and get_lib().dfe_conv1x1_small_supported(shape[0], shape[1], w[0], shape[2], shape[3]) == 1):
             return _CONV1X1
@@ -179,12 +227,15 @@ def _route(ctx, f32, shape, w, stride, padding, dilation, groups, bias, fuse, ac
         r = _raw(f32, shape, w, stride, padding, dilation)
         return r._replace(fwd="wino_act") if WINO_EPILOGUE and r.fwd == "wino" else r
     if ctx == "dense_head":     # the block's flow head; unfused it is F.conv2d forward, raw_backward (with the bias gradient) backward
-        return _HEAD if _flow_head(f32, shape, w, bias) else _raw(f32, shape, w, stride, padding, dilation)._replace(fwd="miopen")
+        if _flow_head(f32, shape, w, bias):
+            return _HEAD
+        r = _raw(f32, shape, w, stride, padding, dilation)
+        return r if det else r._replace(fwd="miopen")
     if ctx == "prepadded":      # the depth decoder's valid 3x3 layers on a reflection-padded activation
         if _thin(f32, contiguous, shape, w):
             # the weight gradient is ours whatever its size: the Winograd-domain kernel from 32 input channels (96 -> 32 at 130x418 x 12:
             # 229 against 374 us; 32 -> 16: 102 against ~124), dfe_wgrad3x3_fwd for the 16 -> 16 layer at 258x834 (133 against 304)
-            return _raw(f32, shape, w, stride, padding, dilation)._replace(wgrad="wino_wgrad" if w[1] >= 32 and WINO_WGRAD else "wgrad3x3")
+            return _raw(f32, shape, w, stride, padding, dilation)._replace(wgrad="wino_wgrad" if w[1] >= 32 and (WINO_WGRAD or det) else "wgrad3x3")
         return _conv2d(f32, shape, w, stride, padding, dilation, groups)
     raise ValueError("convs.plan: unknown context %r" % (ctx,))
 
@@ -194,10 +245,11 @@ def plan(x, w_shape, stride=1, padding=0, dilation=1, groups=1, bias=False, act=
 
     x: the input tensor, or its (is_cuda, dtype, shape); w_shape: the filter's shape; bias / act: whether a bias and an activation
     follow.  ctx, the door the layer came through: "conv2d" (the functional), "module" (``Conv2d.forward``: the flow head first),
-    "conv_act" (``conv_act``; ``fuse`` names the fused kernels the caller admits, of "plane", "wino_act", "conv1x1"), "raw"
+    "conv_act" (``conv_act``; ``fuse`` names the fused kernels the caller admits, of "plane", "wino_act", "conv1x1", "sconv_act"), "raw"
     (``raw_forward`` / ``raw_backward``), "dense" / "dense_head" (``DenseDecodeFn``; ``plane``: the block's small-plane decision,
     None = decide it from this layer), "prepadded" (``conv3x3_valid``).  Host tensors are all MIOpen/ATen, decided before the
-    library is touched.  Memoised with the switches in the key: at batch 1 the step is bound by the host's enqueue time."""
+    library is touched.  In the deterministic mode no plan of a HIP tensor names "miopen" and a layer without a kernel raises DfeError
+    here.  Memoised with the switches in the key: at batch 1 the step is bound by the host's enqueue time."""
     is_cuda, dtype, shape = x if isinstance(x, tuple) else (x.is_cuda, x.dtype, x.shape)
     if not is_cuda:
         return MIOPEN
@@ -206,7 +258,7 @@ def plan(x, w_shape, stride=1, padding=0, dilation=1, groups=1, bias=False, act=
     key = (ctx, dtype, shape if isinstance(shape, tuple) else tuple(shape), w_shape if isinstance(w_shape, tuple) else tuple(w_shape),
            exact(stride), exact(padding), exact(dilation), groups, bool(bias), fuse, act, plane, contiguous,
            WINO_MIN_TILES, WINO_MIN_CHANNELS, WINO_DILATED, WINO_EPILOGUE, WINO_WGRAD, WINO_WGRAD_MIN_MACS, WINO_WGRAD_MAX_DILATION,
-           SCONV, SCONV_WGRAD_MAX_CI, PHASE_MIN_DILATION, PLANECONV_MAX_HW, FLOW_HEAD)
+           SCONV, SCONV_WGRAD_MAX_CI, PHASE_MIN_DILATION, PLANECONV_MAX_HW, FLOW_HEAD, DETERMINISTIC)
     p = _plans.get(key)
     if p is None:
         if len(_plans) > 4096:
@@ -245,8 +297,13 @@ def _phase_eligible(x, w, stride, padding, dilation, groups):      # the rule al
 def raw_forward(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1), route=None):
     """y = conv(x, w) without bias, fp32 in / fp32 out, no autograd of its own."""
     stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
-    if (route or plan(x, w.shape, stride, padding, dilation, ctx="raw")).fwd == "wino":
+    fwd = (route or plan(x, w.shape, stride, padding, dilation, ctx="raw")).fwd
+    if fwd == "wino":
         return ops.wino_conv3x3(x, w, padding[0], dilation=dilation[0])
+    if fwd == "sconv":
+        return ops.sconv_fwd(x, w)
+    if fwd == "conv1x1s2":
+        return ops.conv1x1s2_fwd(x, w)
     return F.conv2d(x, w, None, stride, padding, dilation)
 
 
@@ -260,6 +317,12 @@ def raw_backward(gy, x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1), want_
     if want_w and route.wgrad == "sconv_wgrad":
         gw = ops.sconv_wgrad(x, gy, int(w.shape[2]), 2, int(w.shape[2]) // 2)
         want_w = False
+    if want_w and route.wgrad == "conv1x1s2":
+        gw = ops.conv1x1s2_wgrad(x, gy)
+        want_w = False
+    if want_x and route.dgrad == "sconv":
+        gx = ops.sconv_dgrad(gy, w, x.shape)
+        want_x = False
     if want_x and route.dgrad == "wino":
         # the data gradient = the same kernel on the transposed filter (full correlation, padding 2, for a valid convolution)
         gx = ops.wino_conv3x3(gy, w, 1 if padding != (0, 0) else 2, transposed=True, dilation=d)
@@ -267,6 +330,14 @@ def raw_backward(gy, x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1), want_
     if want_w and route.wgrad in ("wino_wgrad", "wgrad3x3"):
         gw = ops.wino_wgrad3x3(x, gy, padding[0] if d == 1 else 1, d) if route.wgrad == "wino_wgrad" else ops.wgrad3x3(x, gy)
         want_w = False
+    if DETERMINISTIC and x.is_cuda:
+        if want_b:      # a bias gradient alone never goes through aten::convolution_backward: the epilogue's fixed-order reduction
+            gb = ops._bias_act_bwd(gy, gy, 1.0, True)[1]
+            want_b = False
+        if want_x or want_w:
+            raise DfeError("deterministic mode: no kernel of this build takes the %s of the convolution of x %s with w %s, stride %s, "
+                           "padding %s, dilation %s" % ("data gradient" if want_x else "weight gradient", tuple(x.shape), tuple(w.shape),
+                                                        stride, padding, dilation))
     if want_x or want_w or want_b:
         r = _cb(gy, x, w, bias_sizes, list(stride), list(padding), list(dilation), False, [0, 0], 1, [want_x, want_w, want_b])
         gx = r[0] if want_x else gx
@@ -284,10 +355,13 @@ class _RawConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, stride, padding, dilation, route, bias=None, slope=1.0):
         ctx.cfg = (stride, padding, dilation, route, float(slope), bias is not None)
-        if route.fwd != "wino_act":
+        if route.fwd not in ("wino_act", "sconv_act"):
             ctx.save_for_backward(x, w)
             return raw_forward(x, w, stride, padding, dilation, route)
-        y = ops.wino_conv3x3(x, w, padding[0], dilation=dilation[0], bias=bias, slope=slope)
+        if route.fwd == "sconv_act":
+            y = ops.sconv_fwd(x, w, bias, slope)
+        else:
+            y = ops.wino_conv3x3(x, w, padding[0], dilation=dilation[0], bias=bias, slope=slope)
         ctx.save_for_backward(x, w, y)
         return y
 
@@ -296,7 +370,7 @@ class _RawConvFn(torch.autograd.Function):
         x, w = ctx.saved_tensors[:2]
         stride, padding, dilation, route, slope, has_bias = ctx.cfg
         gb = None
-        if route.fwd == "wino_act":
+        if route.fwd in ("wino_act", "sconv_act"):
             gy, gb = ops._bias_act_bwd(ctx.saved_tensors[2], gy if ops._dense_chw(gy) else f32c(gy), slope, has_bias and ctx.needs_input_grad[6])
         gx, gw, _ = raw_backward(gy.contiguous(), x, w, stride, padding, dilation, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                  route=route)
@@ -345,7 +419,7 @@ def conv_bias_act(x, conv, slope):
     return conv_act(x, conv, slope, ("wino_act",))      # the fused epilogue where ``conv_bias_act_eligible``
 
 
-def conv_act(x, conv, slope, fuse=("plane", "wino_act", "conv1x1")):
+def conv_act(x, conv, slope, fuse=("plane", "wino_act", "conv1x1", "sconv_act")):
     """``act(conv(x))`` of an nn.Conv2d on the GPU, act(v) = v > 0 ? v : slope v (slope 1: no activation): one fused kernel where
     the plan names one of ``fuse``; otherwise the convolution runs without its bias and the bias + activation epilogue is one
     in-place HIP pass whose backward also yields the bias gradient (ops.bias_act) -- or, with no activation to apply, the
@@ -354,7 +428,7 @@ def conv_act(x, conv, slope, fuse=("plane", "wino_act", "conv1x1")):
     route = plan(x, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias is not None, act, "conv_act", fuse)
     if route.fwd == "plane":
         return ops.planeconv_act(x, conv.weight, conv.bias, slope)
-    if route.fwd == "wino_act":
+    if route.fwd in ("wino_act", "sconv_act"):
         return _RawConvFn.apply(x, conv.weight, conv.stride, conv.padding, conv.dilation, route, conv.bias, float(slope))
     if route.fwd == "conv1x1":
         return ops.conv1x1_small(x, conv, slope)
@@ -408,8 +482,11 @@ class DenseDecodeFn(torch.autograd.Function):
         layer(cat[0], 2, cat[1], co[1], cat[2], 0)                          # x2
         layer(cat[1], 3, cat[2], co[2], cat[3], 0)                          # x3
         x4 = layer(cat[2], 4, None, 0, cat[3], co[3])                       # x4: returned + cat3[:, 64:]
-        if plan(cat[3], w[5].shape, (1, 1), (1, 1), bias=b[5] is not None, ctx="dense_head").fwd == "flow_head":
+        head = plan(cat[3], w[5].shape, (1, 1), (1, 1), bias=b[5] is not None, ctx="dense_head").fwd
+        if head == "flow_head":
             flow = ops.flow_head_fwd_raw(cat[3], f32c(w[5]), f32c(b[5]))
+        elif head == "wino":        # the deterministic mode with the head kernels switched off
+            flow = ops.wino_conv3x3(cat[3], w[5], 1, bias=b[5])
         else:
             flow = F.conv2d(cat[3], w[5], b[5], 1, 1)
         ctx.save_for_backward(x, z0, *cat, *w)

@@ -33,7 +33,7 @@ class PoseCNN(nn.Module):
         """``self.relu(conv(x))`` (pose_cnn.py:68-69, 84-85).  On the GPU the convolution runs without its bias and the bias +
         ReLU epilogue is one in-place HIP pass whose backward also yields the bias gradient (convs.conv_act, slope 0)."""
         if x.is_cuda:      # the 2x7 refinement planes: this build's MFMA kernels; never the fused Winograd epilogue
-            return convs.conv_act(x, conv, 0.0, ("plane", "conv1x1"))
+            return convs.conv_act(x, conv, 0.0, ("plane", "conv1x1", "sconv_act"))
         return self.relu(conv(x))
 
     @staticmethod

@@ -1058,6 +1058,90 @@ def sconv_wgrad(x, gy, k, stride, padding):
     return gw
 
 
+# The deterministic mode's forward / data-gradient kernels of the stride-2 layers.  The *_supported queries are host-only.
+def sconv_fwd_supported(x_shape, co, k):
+    B, Ci, H, W = (int(v) for v in x_shape)
+    return get_lib().dfe_sconv_fwd_floats(B, Ci, int(co), H, W, int(k)) > 0
+
+
+def sconv_fwd(x, w, bias=None, slope=1.0):
+    """act(conv2d(x, w, stride 2, padding k // 2) + bias) for k in {3, 5, 7} on dfe_sconv_fwd (fp32 MFMA straight from NCHW;
+    depth_model.py:60-95, feature_pyramid.py:7-36, pose_cnn.py:14-36).  slope: 1 none, 0 ReLU, 0.1 LeakyReLU."""
+    x = x if _dense_chw(x) else f32c(x)
+    w = f32c(w)
+    B, Ci, H, W = x.shape
+    Co, k = int(w.shape[0]), int(w.shape[2])
+    lib = get_lib()
+    n = lib.dfe_sconv_fwd_floats(B, Ci, Co, H, W, k)
+    if n <= 0 or w.shape[1] != Ci or w.shape[3] != k:
+        raise _lib.DfeError("dfe_sconv_fwd: unsupported layer %s * %s" % (tuple(x.shape), tuple(w.shape)))
+    P = k // 2
+    y = torch.empty(B, Co, (H + 2 * P - k) // 2 + 1, (W + 2 * P - k) // 2 + 1, device=x.device, dtype=torch.float32)
+    ws = torch.empty(n, device=x.device, dtype=torch.float32)
+    check(lib.dfe_sconv_fwd(ptr(x, strided=True), x.stride(0), ptr(w), None if bias is None else ptr(f32c(bias)), float(slope), ptr(y),
+                            y.stride(0), ptr(ws), B, Ci, Co, H, W, k, stream_ptr()), "dfe_sconv_fwd")
+    return y
+
+
+def sconv_dgrad_supported(x_shape, co, k):
+    B, Ci, H, W = (int(v) for v in x_shape)
+    return get_lib().dfe_sconv_dgrad_floats(B, Ci, int(co), H, W, int(k)) > 0
+
+
+def sconv_dgrad(gy, w, x_shape):
+    """Data gradient [B,Ci,H,W] of conv2d(x, w, stride 2, padding k // 2), k in {1, 3, 5}, for gy, on dfe_sconv_dgrad."""
+    gy = gy if _dense_chw(gy) else f32c(gy)
+    w = f32c(w)
+    B, Ci, H, W = (int(v) for v in x_shape)
+    Co, k = int(w.shape[0]), int(w.shape[2])
+    lib = get_lib()
+    n = lib.dfe_sconv_dgrad_floats(B, Ci, Co, H, W, k)
+    P = k // 2
+    if n <= 0 or w.shape[1] != Ci or w.shape[3] != k or tuple(gy.shape) != (B, Co, (H + 2 * P - k) // 2 + 1, (W + 2 * P - k) // 2 + 1):
+        raise _lib.DfeError("dfe_sconv_dgrad: unsupported layer gy %s * %s -> %s" % (tuple(gy.shape), tuple(w.shape), tuple(x_shape)))
+    gx = torch.empty(B, Ci, H, W, device=gy.device, dtype=torch.float32)
+    ws = torch.empty(n, device=gy.device, dtype=torch.float32)
+    check(lib.dfe_sconv_dgrad(ptr(gy, strided=True), gy.stride(0), ptr(w), ptr(gx), gx.stride(0), ptr(ws), B, Ci, Co, H, W, k, stream_ptr()),
+          "dfe_sconv_dgrad")
+    return gx
+
+
+def conv1x1s2_supported(x_shape, co):
+    B, Ci, H, W = (int(v) for v in x_shape)
+    return get_lib().dfe_conv1x1s2_supported(B, Ci, int(co), H, W) == 1
+
+
+def conv1x1s2_fwd(x, w):
+    """conv2d(x, w [Co,Ci,1,1], stride 2, padding 0) without bias on dfe_conv1x1s2_fwd (depth_model.py:31-36)."""
+    x = x if _dense_chw(x) else f32c(x)
+    w = f32c(w)
+    B, Ci, H, W = x.shape
+    Co = int(w.shape[0])
+    if tuple(w.shape[1:]) != (Ci, 1, 1) or not conv1x1s2_supported(x.shape, Co):
+        raise _lib.DfeError("dfe_conv1x1s2_fwd: unsupported layer %s * %s" % (tuple(x.shape), tuple(w.shape)))
+    y = torch.empty(B, Co, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, dtype=torch.float32)
+    check(get_lib().dfe_conv1x1s2_fwd(ptr(x, strided=True), x.stride(0), ptr(w), ptr(y), y.stride(0), B, Ci, Co, H, W, stream_ptr()),
+          "dfe_conv1x1s2_fwd")
+    return y
+
+
+def conv1x1s2_wgrad(x, gy):
+    """Weight gradient [Co,Ci,1,1] of the same layer for the output gradient gy, on dfe_conv1x1s2_wgrad (fixed-order split sums)."""
+    x = x if _dense_chw(x) else f32c(x)
+    gy = gy if _dense_chw(gy) else f32c(gy)
+    B, Ci, H, W = x.shape
+    Co = int(gy.shape[1])
+    lib = get_lib()
+    n = lib.dfe_conv1x1s2_wgrad_floats(B, Ci, Co, H, W)
+    if n <= 0 or tuple(gy.shape) != (B, Co, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise _lib.DfeError("dfe_conv1x1s2_wgrad: gy %s does not belong to x %s" % (tuple(gy.shape), tuple(x.shape)))
+    gw = torch.empty(Co, Ci, 1, 1, device=x.device, dtype=torch.float32)
+    ws = torch.empty(n, device=x.device, dtype=torch.float32)
+    check(lib.dfe_conv1x1s2_wgrad(ptr(x, strided=True), x.stride(0), ptr(gy, strided=True), gy.stride(0), ptr(gw), ptr(ws), B, Ci, Co, H, W,
+                                  stream_ptr()), "dfe_conv1x1s2_wgrad")
+    return gw
+
+
 class PlaneConvActFn(torch.autograd.Function):
     """act(conv3x3(x, w, pad 1) + bias) on a small plane as one operator (PoseCNN's refinement convolutions,
     pose_cnn.py:43-46, 66-69: Conv2d(12, 12, 3, 1, 1) + ReLU on 2x7 planes): dfe_planeconv_fwd with the epilogue inside;

@@ -15,7 +15,7 @@ class ConvAct(nn.Sequential):
     def forward(self, x):
         if not x.is_cuda:
             return super().forward(x)
-        return convs.conv_act(x, self[0], self[1].negative_slope, ("plane", "wino_act"))      # never the 1x1 kernel
+        return convs.conv_act(x, self[0], self[1].negative_slope, ("plane", "wino_act", "sconv_act"))      # never the 1x1 kernel
 
 
 def conv(in_planes, out_planes, kernel_size=3, stride=1, padding=1, dilation=1):
