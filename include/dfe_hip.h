@@ -69,6 +69,33 @@ int dfe_adam_step(const void* table, const int* blockmap, int nblocks, double lr
 int dfe_adam_step_dev(const void* table, const int* blockmap, int nblocks, double lr, double beta1, double beta2, double eps,
                       double* step_count, float* coef, void* stream);
 
+/* ---- gradient guard in front of the Adam update: torch.nn.utils.clip_grad_norm_(params, max_norm) and GradScaler's
+ * "skip the step whose gradients are not finite" (without the scaling), decided on the device so that a captured step can
+ * take them.  The gradients are READ once more and never written: the update multiplies by the coefficient on the fly.
+ * dfe_grad_guard: (1) one block per block-map entry sums the squares of its gradient chunk in double (fp32 x fp32 is exact
+ * in double; a gradient of 1e30 gives a large finite norm) in a fixed order and notes whether an element is NaN / +-inf
+ * (from the exponent bits) -> ws: nblocks doubles followed by nblocks int32 flags, dfe_grad_guard_ws_bytes(nblocks) bytes,
+ * 8-byte aligned, every byte written on every call; (2) one block adds the partials in a fixed order and writes record
+ * (dfe_grad_guard_record_bytes() = 32 bytes, 8-byte aligned):
+ *   double norm    = sqrt(sum g^2) over every element the block map covers
+ *   double skipped   running count of skipped steps (the caller zeroes it once)
+ *   float  c       = float(min(1, max_norm / (norm + 1e-6))) formed in double; exactly 1 when max_norm <= 0 (no clipping)
+ *   int32  finite  = no element is NaN / +-inf;  int32 skip = skip_nonfinite && !finite;  int32 0
+ * not skipping, it then does what dfe_adam_step_dev's first launch does (*step_count += 1, the two coefficients into coef);
+ * skipping, the count stays and skipped += 1.  With clipping on and skip_nonfinite off a non-finite norm goes through the
+ * formula as in torch: c = 0 for an inf norm, NaN for a NaN norm.
+ * dfe_adam_tick_guarded: the same conditional count + coefficients for one more param group that shares the record
+ * (one global norm over several groups: its table and block map cover all of them, each group steps with its own).
+ * dfe_adam_step_guarded: dfe_adam_step_dev's update with the gradient fl32(g * c) (one fp32 product; g itself when c == 1);
+ * when record says skip, no p, m or v is read or written. */
+int dfe_grad_guard_ws_bytes(int nblocks);
+int dfe_grad_guard_record_bytes(void);
+int dfe_grad_guard(const void* table, const int* blockmap, int nblocks, double max_norm, int skip_nonfinite, double lr, double beta1,
+                   double beta2, void* ws, double* step_count, float* coef, void* record, void* stream);
+int dfe_adam_tick_guarded(double lr, double beta1, double beta2, double* step_count, float* coef, const void* record, void* stream);
+int dfe_adam_step_guarded(const void* table, const int* blockmap, int nblocks, double beta1, double beta2, double eps,
+                          const float* coef, const void* record, void* stream);
+
 /* ---- order-independent scatter-add workspace (csrc/dfe_scatter.h) -----------------------------
  * Adjoint of a bilinear gather with respect to the sampled tensor: contributions are scaled by a power of two, rounded
  * once to 64-bit integers, added with integer atomics (associative: no dependence on the order the atomics retire in)

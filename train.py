@@ -42,9 +42,12 @@ def load_model(model_dir, filename, model, optimizer):
     return data["iteration"], model, optimizer
 
 
-def print_loss(iter_, loss_pack, weights, total):
+def print_loss(iter_, loss_pack, weights, total, guard=None):
+    """``guard``: FusedAdam.guard_stats() when the gradient guard is on (--clip_grad_norm / --skip_nonfinite)."""
     line = "iter {:6d} total {:.4f} | ".format(iter_, float(total))
     line += " ".join("{}:{:.4f}".format(k.replace("loss_", ""), float(v.mean()) * weights[k]) for k, v in loss_pack.items())
+    if guard is not None:
+        line += " | gnorm {:.2f} clip {:.2f} skipped {:d}".format(guard["grad_norm"], guard["clip_coef"], guard["skipped_steps"])
     print(line, flush=True)
 
 
@@ -77,7 +80,10 @@ def train(cfg):
     model.train()
     model = ddp.wrap(model, dev)
     use_graph = bool(getattr(cfg, "graph", False)) and world == 1
-    optimizer = make_optimizer(model, cfg.lr, capturable=use_graph)
+    # 0 / absent: off (then DFE_CLIP_GRAD_NORM / DFE_SKIP_NONFINITE decide, see make_optimizer)
+    optimizer = make_optimizer(model, cfg.lr, capturable=use_graph, max_grad_norm=float(getattr(cfg, "clip_grad_norm", 0) or 0) or None,
+                               skip_nonfinite=bool(getattr(cfg, "skip_nonfinite", False)))
+    guarded = getattr(optimizer, "max_grad_norm", None) is not None or getattr(optimizer, "skip_nonfinite", False)
     start = 0
     if cfg.resume:
         fn = "iter_{}.pth".format(cfg.iter_start) if cfg.iter_start > 0 else "last.pth"
@@ -127,7 +133,7 @@ def train(cfg):
         else:
             loss, loss_pack, mask_pack = train_step(model, optimizer, inputs, cfg, prof if (prof is not None and it % cfg.log_interval == 0) else None)
         if rank == 0 and it % cfg.log_interval == 0:
-            print_loss(it, loss_pack, weights, loss)
+            print_loss(it, loss_pack, weights, loss, optimizer.guard_stats() if guarded else None)
         if rank == 0 and (it + 1) % cfg.save_interval == 0:
             save_model(it + 1, cfg.model_dir, "iter_{}.pth".format(it + 1), model, optimizer)
             save_model(it + 1, cfg.model_dir, "last.pth", model, optimizer)
@@ -139,7 +145,11 @@ def train(cfg):
         torch.distributed.destroy_process_group()
 
 
-if __name__ == "__main__":
+# CLI attributes that leave the YAML's value alone when they are not given
+KEEP_YAML_WHEN_UNSET = ("num_iterations", "data_source", "prepared_base_dir", "deterministic", "clip_grad_norm", "skip_nonfinite")
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description="joint depth / flow / pose training on MI355X")
     ap.add_argument("-c", "--config_file", default="config/kitti_geom.yaml")
     ap.add_argument("-g", "--gpu", type=str, default="0", help="kept for CLI compatibility; use torchrun for >1 GPU")
@@ -180,15 +190,33 @@ if __name__ == "__main__":
                          "inputs; slower; also the YAML key 'deterministic' and DFE_DETERMINISTIC=1)")
     ap.add_argument("--device_pipeline", action="store_true",
                     help="feed raw uint8 triplets and run resize / flip / normalise on the device (ops.prepare_triplets)")
-    args = ap.parse_args()
-    with open(args.config_file) as fh:
-        cfg = yaml.safe_load(fh)
+    ap.add_argument("--clip_grad_norm", type=float, default=None,
+                    help="clip the global 2-norm of the gradients to this value inside the optimiser step "
+                         "(torch.nn.utils.clip_grad_norm_'s formula, on the device; also the YAML key 'clip_grad_norm' and "
+                         "DFE_CLIP_GRAD_NORM; 0: off)")
+    ap.add_argument("--skip_nonfinite", action="store_const", const=True, default=None,
+                    help="do not apply a step whose gradients hold a NaN or an inf: parameters, moments and Adam's step count stay "
+                         "as they are and the skip is counted (also the YAML key 'skip_nonfinite' and DFE_SKIP_NONFINITE=1)")
+    return ap
+
+
+def merge_cfg(args, cfg):
+    """The YAML's dict with the command line on top: every CLI attribute overrides / extends it (train.py:272-274), except
+    the ones of KEEP_YAML_WHEN_UNSET when they were not given."""
+    cfg = dict(cfg)
     cfg["img_hw"] = (cfg["img_hw"][0], cfg["img_hw"][1])
     cfg["model_dir"] = os.path.join(args.model_dir or "./models", args.mode)
-    for k, v in vars(args).items():        # every CLI attribute overrides / extends the YAML (train.py:272-274)
-        if k in ("model_dir",) or (k in ("num_iterations", "data_source", "prepared_base_dir", "deterministic") and v is None):
+    for k, v in vars(args).items():
+        if k in ("model_dir",) or (k in KEEP_YAML_WHEN_UNSET and v is None):
             continue
         cfg[k] = v
+    return cfg
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
+    with open(args.config_file) as fh:
+        cfg = merge_cfg(args, yaml.safe_load(fh))
     os.makedirs(cfg["model_dir"], exist_ok=True)
     if int(os.environ.get("RANK", "0")) == 0:
         shutil.copy(args.config_file, cfg["model_dir"])

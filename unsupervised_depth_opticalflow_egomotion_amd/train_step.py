@@ -26,18 +26,39 @@ def make_cfg(**over):
     return types.SimpleNamespace(**d)
 
 
-def make_optimizer(model, lr, capturable=False):
+def guard_defaults():
+    """``(max_grad_norm, skip_nonfinite)`` as the environment asks: ``DFE_CLIP_GRAD_NORM`` (a float; unset or 0: off) and
+    ``DFE_SKIP_NONFINITE`` (1: on)."""
+    import os
+    clip = float(os.environ.get("DFE_CLIP_GRAD_NORM", "0") or 0.0)
+    return (clip if clip != 0.0 else None), os.environ.get("DFE_SKIP_NONFINITE", "0") == "1"
+
+
+def make_optimizer(model, lr, capturable=False, max_grad_norm=None, skip_nonfinite=False):
     """The reference's ``torch.optim.Adam(model.parameters(), lr)`` (train.py:85-87), same hyper-parameters, state
     layout and update rule.  On a HIP device: ``optim.FusedAdam``, one launch for all parameters (ATen's fused
     multi-tensor Adam needs six for this model; ``DFE_FUSED_ADAM=0`` selects it).  ``capturable``: the step count on the
-    device, for a step replayed from a hipGraph (GraphedTrainStep)."""
+    device, for a step replayed from a hipGraph (GraphedTrainStep).  ``max_grad_norm`` / ``skip_nonfinite``: FusedAdam's
+    gradient guard (global-norm clipping, skipping a step with a non-finite gradient); where an argument is left at its
+    default, ``DFE_CLIP_GRAD_NORM`` / ``DFE_SKIP_NONFINITE`` decide.  The guard exists in FusedAdam only: asked for where
+    another optimiser is selected, this raises.  A data-parallel reducer runs as a step pre-hook, i.e. BEFORE the guard: every
+    rank guards the same reduced gradients in the same fixed order and takes the same decision, without a collective."""
     import os
     import torch
+    from ._lib import DfeError
+    env_clip, env_skip = guard_defaults()
+    if max_grad_norm is None:
+        max_grad_norm = env_clip
+    skip_nonfinite = bool(skip_nonfinite) or env_skip
+    guarded = max_grad_norm is not None or skip_nonfinite
     params = [p for p in model.parameters() if p.requires_grad]
     on_gpu = bool(params) and all(p.is_cuda and p.dtype == torch.float32 for p in params)
     if on_gpu and os.environ.get("DFE_FUSED_ADAM", "1") != "0":
         from .optim import FusedAdam
-        opt = FusedAdam(params, lr=lr, capturable=capturable)
+        opt = FusedAdam(params, lr=lr, capturable=capturable, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    elif guarded:
+        raise DfeError("make_optimizer: max_grad_norm / skip_nonfinite need optim.FusedAdam, which is not selected here (%s)"
+                       % ("DFE_FUSED_ADAM=0" if on_gpu else "the parameters are not fp32 tensors on a HIP device"))
     else:
         opt = torch.optim.Adam(params, lr=lr, fused=True, capturable=capturable) if on_gpu else torch.optim.Adam(params, lr=lr)
     if hasattr(model, "reduce_gradients"):      # ddp.FlatAllReduce: the gradient all-reduce runs in front of every step
@@ -143,7 +164,9 @@ class GraphedTrainStep:
         self._epoch = getattr(optimizer, "capture_epoch", 0)
 
     def _hyper_now(self):
-        return [(float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"])) for g in self.optimizer.param_groups]
+        opt = self.optimizer
+        guard = (getattr(opt, "max_grad_norm", None), bool(getattr(opt, "skip_nonfinite", False)))    # kernel arguments too
+        return [(float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"])) for g in opt.param_groups] + [guard]
 
     def _snapshot(self):
         """Parameters, buffers and the optimiser's state before the warm-up steps (device copies; ~3x the model)."""
@@ -155,13 +178,14 @@ class GraphedTrainStep:
                 if st:
                     state[p] = {k: (v.clone() if hasattr(v, "clone") else v) for k, v in st.items()}
         dev_count = {gi: [t.clone() for t in dc] for gi, dc in getattr(opt, "_dev_count", {}).items()}
+        rec = getattr(opt, "_guard_rec", None)             # FusedAdam's gradient guard: the running count of skipped steps
         return ([p.detach().clone() for p in self.model.parameters()], [b.detach().clone() for b in self.model.buffers()],
-                state, dev_count)
+                state, dev_count, None if rec is None else rec.clone())
 
     def _restore(self, saved):
         """Put the snapshot back IN PLACE (every address the capture is about to record stays what it is)."""
         import torch
-        params, buffers, state, dev_count = saved
+        params, buffers, state, dev_count, guard_rec = saved
         opt = self.optimizer
         with torch.no_grad():
             for p, v in zip(self.model.parameters(), params):
@@ -193,13 +217,19 @@ class GraphedTrainStep:
                             t0 = float(st["step"])
                             break
                     dc[0].fill_(t0)
+            rec = getattr(opt, "_guard_rec", None)
+            if rec is not None:         # a warm-up step may have skipped: back to the record of before, or to zero skipped steps
+                if guard_rec is not None:
+                    rec.copy_(guard_rec)
+                else:
+                    rec.zero_()
         ops.wino_weights.invalidate()       # parameters written in place without a step: cached transformed filters are stale
         ops.wino_weights.refresh()
 
     def __call__(self, inputs=None):
         if self._hyper_now() != self._hyper:
-            raise RuntimeError("GraphedTrainStep: lr / betas / eps changed since the capture (they are kernel arguments of the "
-                               "captured optimiser step): build a new GraphedTrainStep")
+            raise RuntimeError("GraphedTrainStep: lr / betas / eps or the gradient guard's settings changed since the capture (they "
+                               "are kernel arguments of the captured optimiser step): build a new GraphedTrainStep")
         if getattr(self.optimizer, "capture_epoch", 0) != self._epoch:
             raise RuntimeError("GraphedTrainStep: optimizer.load_state_dict() ran since the capture (the graph updates the "
                                "previous moment tensors): build a new GraphedTrainStep")
