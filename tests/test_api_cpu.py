@@ -1098,7 +1098,11 @@ def test_occupancy_critical_kernels_keep_their_resources():
     Winograd layer; EXPERIMENT_LOG round-6 appendix) -- nothing a parity test can see.  This reads the resource metadata of the
     built library (tools/kernel_meta.py: the code objects' AMDGPU notes, no GPU needed) and holds the matrix kernels to what
     their launch configuration assumes: no static LDS beside the dynamic buffers, at most 256 registers (two waves per SIMD),
-    no register spills to memory, no scratch; the per-sample prepare kernels are the only ones allowed scratch."""
+    no register spills to memory, no scratch; the per-sample prepare kernels are the only ones allowed scratch.
+
+    The last loop holds the deterministic mode's kernels to the same (no spills, no scratch, vgpr <= 256, agpr == 0): the twelve
+    k_sconv_fwd / k_sconv_dgrad kernels sit at 250 / 243 VGPRs at the most, and the two 1x1 stride-2 kernels carry
+    amdgpu_waves_per_eu(2) so that their MFMA accumulators stay out of the AGPRs (53 and 86 VGPRs; 76 + 24 and 104 + 20 without)."""
     import sys
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import kernel_meta
@@ -1124,6 +1128,36 @@ def test_occupancy_critical_kernels_keep_their_resources():
     # second, 16 %-full round (51 us instead of 39: profiles/r06_ssim_bwd_experiment.md)
     ssim_bwd = by("k_geom_ssim_bwd_roll")
     assert len(ssim_bwd) == 1 and ssim_bwd[0]["vgpr"] <= 96 and ssim_bwd[0]["scratch"] == 0, ssim_bwd
+    # the deterministic mode's passes on the shared staging layer (csrc/dfe_mfma_stage.h): k_sconv_fwd / _dgrad sit at the
+    # 256-register limit of two waves per SIMD
+    det = by("k_sconv_fwd") + by("k_sconv_dgrad") + by("k_conv1x1s2_fwd") + by("k_conv1x1s2_wgrad")
+    assert len(det) == 6 + 6 + 1 + 1
+    for k in det:
+        assert k["vgpr_spill"] == 0 and k["scratch"] == 0, k
+        assert k["vgpr"] <= 256 and k["agpr"] == 0, k
+
+
+def test_conv_planners_answer_as_recorded():
+    """The host-only planners of csrc/ops_sconv.hip, ops_wino_wgrad.hip and ops_conv1x1s2.hip -- workspace floats and support
+    per shape -- against tests/golden/conv_ws_floats.json, exactly: the shape lists of the kernels' GPU tests and of
+    tools/sconv_bench.py and shapes some or all planners refuse.  The file holds the answers of the library built from the commit
+    before the planners moved onto shared helpers (split_round, sc_tile_plan), never this tree's:
+        DFE_HIP_LIB=<that build>/libdfe_hip.so python tools/conv_ws_floats.py > tests/golden/conv_ws_floats.json"""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import conv_ws_floats
+    from unsupervised_depth_opticalflow_egomotion_amd._lib import get_lib
+    with open(os.path.join(REPO, "tests", "golden", "conv_ws_floats.json")) as fh:
+        rows = json.load(fh)
+    assert len(rows) >= 90
+    # the recorded shapes are still the lists' shapes, and the refused ones answer 0 wherever they did
+    assert [tuple(r["shape"]) for r in rows] == list(dict.fromkeys(s for _, s in conv_ws_floats.shapes()))
+    assert sum(1 for r in rows for k, v in r.items() if k not in ("from", "shape") and v == 0) >= 100
+    lib = get_lib()
+    for r in rows:
+        got = conv_ws_floats.answers(lib, tuple(r["shape"]))
+        assert got == {k: r[k] for k in got}, (r["from"], r["shape"], got)
 
 
 def test_bench_dump_outputs_float32_whole_or_a_fixed_sample(tmp_path):

@@ -17,6 +17,16 @@ inline int launch_status() { return hipGetLastError() == hipSuccess ? DFE_OK : D
 inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }   // an integer tuning switch; dflt when unset
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// a tensor of `per` floats per sample at batch stride bs: the stride holds a sample, and 32-bit offsets hold inside one
+inline bool sample_ok(long bs, long per) { return bs >= per && per < (1L << 30); }
+// a 256-thread launch with lds_bytes of dynamic LDS; more than 64 KB needs the opt-in attribute (attr_bytes) once per kernel:
+// the kernel is a template argument so that every instantiation has its own flag
+template <auto Kern, class... Args>
+inline void launch_dyn_lds(unsigned grid, size_t lds_bytes, int attr_bytes, hipStream_t st, Args... args) {
+  static bool attr_set = false;
+  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, attr_bytes); attr_set = true; }
+  Kern<<<grid, 256, lds_bytes, st>>>(args...);
+}
 
 // ops_corr.hip: the PWC cost volume and its gradients (LDS-staged).  out / gout: 81 planes per sample with batch stride
 // obs / gbs (the planes may be a slice of a wider tensor); add1 (batch stride abs1) is added to g1 when given.

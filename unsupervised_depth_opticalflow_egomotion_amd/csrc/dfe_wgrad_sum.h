@@ -1,6 +1,8 @@
-// The fixed-order sum of a weight gradient's split partials (ops_wino_wgrad.hip, ops_sconv.hip).
+// The split of a weight gradient's reduction over blocks and the fixed-order sum of the splits' partials (ops_wino_wgrad.hip,
+// ops_sconv.hip, ops_conv1x1s2.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 
 namespace dfe {
 
@@ -24,6 +26,21 @@ __global__ void __launch_bounds__(32 * SG) k_wgrad_sum(const float* __restrict__
     for (int j = 1; j < SG; ++j) t += sm[j][o];
     gw[idx] = t;
   }
+}
+
+inline void launch_wgrad_sum(const float* ws, float* gw, int nsplit, long n, hipStream_t st) {
+  const unsigned blocks = static_cast<unsigned>((n + 31) / 32);
+  if (nsplit > 64) k_wgrad_sum<32><<<blocks, 1024, 0, st>>>(ws, gw, nsplit, n);
+  else k_wgrad_sum<8><<<blocks, 256, 0, st>>>(ws, gw, nsplit, n);
+}
+
+// The split of a reduction of nchunks chunks over blocks: one resident round of `target` blocks, ntb of them per split.  Returns
+// the number of splits, *cps = chunks per split.
+inline int split_round(int target, long ntb, int nchunks, int* cps) {
+  long sp = (target + ntb / 2) / ntb;
+  sp = std::max(1L, std::min<long>(sp, nchunks));
+  *cps = static_cast<int>((nchunks + sp - 1) / sp);
+  return (nchunks + *cps - 1) / *cps;
 }
 
 }  // namespace dfe

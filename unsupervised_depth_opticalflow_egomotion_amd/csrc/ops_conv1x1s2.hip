@@ -11,13 +11,12 @@
 // Bound: the stride-2 reads of x (half of every 64-byte line fetched is used), not the matrix pipe (<= 0.7 GFLOP per layer).
 #include "dfe_internal.h"
 #include "dfe_device.h"
+#include "dfe_mfma_stage.h"
 #include "dfe_wgrad_sum.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
 namespace dfe {
-
-typedef float c1_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C1_T = 64;        // a block's output channels, and its pixels (forward) / input channels (weight gradient): 2 x 2 waves of 2 x 2 tiles
 constexpr int C1_KC = 16;       // forward: input channels per staged chunk
@@ -33,7 +32,10 @@ struct C1Geo {
   int nchunks, cps;             // weight gradient: pixel chunks, chunks per split
 };
 
-__global__ void __launch_bounds__(256)
+// amdgpu_waves_per_eu(2), here and below: with no blocks per CU named the compiler plans for one wave per SIMD and keeps the MFMA
+// accumulators in AGPRs (76 + 24 registers here, 104 + 20 in the weight gradient); held to the 256 VGPRs of two waves it needs 53 / 86
+// and no AGPR (tests/test_api_cpu.py holds both to that)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 k_conv1x1s2_fwd(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, const C1Geo g) {
   __shared__ float xs[C1_KC * C1_XS];
   __shared__ float wl[C1_T * C1_WS];
@@ -71,11 +73,7 @@ k_conv1x1s2_fwd(const float* __restrict__ x, const float* __restrict__ w, float*
     for (int jj = 0; jj < 4; ++jj) wl[(wro + 16 * jj) * C1_WS + wci] = wr[jj];
   };
 
-  c1_f32x4 acc[2][2];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = c1_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 acc[2][2] = {};
 
   load_chunk(0);
   store_chunk();
@@ -90,10 +88,7 @@ k_conv1x1s2_fwd(const float* __restrict__ x, const float* __restrict__ w, float*
       for (int mt = 0; mt < 2; ++mt) a[mt] = wl[((wm * 2 + mt) * 16 + i) * C1_WS + 4 * k4 + kq];
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) bv[nt] = xs[(4 * k4 + kq) * C1_XS + (wn * 2 + nt) * 16 + i];
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+      mfma_tile(acc, a, bv);
     }
     __syncthreads();
     if (more) {
@@ -118,7 +113,7 @@ k_conv1x1s2_fwd(const float* __restrict__ x, const float* __restrict__ w, float*
   }
 }
 
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 k_conv1x1s2_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ part, const C1Geo g) {
   __shared__ float gs[C1_T * C1_PS];
   __shared__ float xs[C1_T * C1_PS];
@@ -153,11 +148,7 @@ k_conv1x1s2_wgrad(const float* __restrict__ x, const float* __restrict__ gy, flo
     }
   };
 
-  c1_f32x4 acc[2][2];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = c1_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 acc[2][2] = {};
 
   if (c_beg < c_end) {
     load_chunk(c_beg);
@@ -174,10 +165,7 @@ k_conv1x1s2_wgrad(const float* __restrict__ x, const float* __restrict__ gy, flo
       for (int mt = 0; mt < 2; ++mt) a[mt] = gs[((wm * 2 + mt) * 16 + i) * C1_PS + 4 * k4 + kq];
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) bv[nt] = xs[((wn * 2 + nt) * 16 + i) * C1_PS + 4 * k4 + kq];
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+      mfma_tile(acc, a, bv);
     }
     __syncthreads();
     if (more) {
@@ -222,11 +210,7 @@ bool c1_plan(int B, int Ci, int Co, int H, int W, C1Geo* out, int* nsplit) {
   g.ntb = g.ncot * g.ncit;
   if (static_cast<long>(g.ncot) * ((n + C1_T - 1) / C1_T) >= (1L << 30) || g.ntb >= (1 << 20)) return false;
   g.nchunks = (g.N + C1_PK - 1) / C1_PK;
-  // one resident round of blocks (two per CU)
-  long sp = (512 + g.ntb / 2) / g.ntb;
-  sp = std::max(1L, std::min<long>(sp, g.nchunks));
-  g.cps = static_cast<int>((g.nchunks + sp - 1) / sp);
-  *nsplit = (g.nchunks + g.cps - 1) / g.cps;
+  *nsplit = split_round(512, g.ntb, g.nchunks, &g.cps);      // one resident round of blocks (two per CU)
   *out = g;
   return true;
 }
@@ -243,7 +227,7 @@ extern "C" int dfe_conv1x1s2_fwd(const float* x, long x_batch_stride, const floa
   if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return DFE_ERR_DIMS;
   C1Geo g; int ns;
   if (!c1_plan(B, Ci, Co, H, W, &g, &ns)) return DFE_ERR_UNSUPPORTED;
-  if (x_batch_stride < static_cast<long>(Ci) * H * W || y_batch_stride < static_cast<long>(Co) * g.HWo) return DFE_ERR_DIMS;
+  if (!sample_ok(x_batch_stride, static_cast<long>(Ci) * H * W) || !sample_ok(y_batch_stride, static_cast<long>(Co) * g.HWo)) return DFE_ERR_DIMS;
   g.xbs = x_batch_stride; g.obs = y_batch_stride;
   const unsigned blocks = static_cast<unsigned>(g.ncot) * static_cast<unsigned>((g.N + C1_T - 1) / C1_T);
   k_conv1x1s2_fwd<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(x, weight, y, g);
@@ -263,14 +247,12 @@ extern "C" int dfe_conv1x1s2_wgrad(const float* x, long x_batch_stride, const fl
   if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return DFE_ERR_DIMS;
   C1Geo g; int ns;
   if (!c1_plan(B, Ci, Co, H, W, &g, &ns)) return DFE_ERR_UNSUPPORTED;
-  if (x_batch_stride < static_cast<long>(Ci) * H * W || gy_batch_stride < static_cast<long>(Co) * g.HWo) return DFE_ERR_DIMS;
+  if (!sample_ok(x_batch_stride, static_cast<long>(Ci) * H * W) || !sample_ok(gy_batch_stride, static_cast<long>(Co) * g.HWo)) return DFE_ERR_DIMS;
   g.xbs = x_batch_stride; g.obs = gy_batch_stride;
   hipStream_t st = static_cast<hipStream_t>(stream);
   k_conv1x1s2_wgrad<<<static_cast<unsigned>(g.ntb) * ns, 256, 0, st>>>(x, gy, ws, g);
   DFE_LAUNCH_CHECK();
-  const long n = static_cast<long>(Co) * Ci;
-  if (ns > 64) k_wgrad_sum<32><<<static_cast<unsigned>((n + 31) / 32), 1024, 0, st>>>(ws, gweight, ns, n);
-  else k_wgrad_sum<8><<<static_cast<unsigned>((n + 31) / 32), 256, 0, st>>>(ws, gweight, ns, n);
+  launch_wgrad_sum(ws, gweight, ns, static_cast<long>(Co) * Ci, st);
   DFE_LAUNCH_CHECK();
   return DFE_OK;
 }

@@ -28,6 +28,7 @@
 // Displacement rows are split over IS threads per output where the level is small; partials meet in LDS in fixed order.
 #include "dfe_device.h"
 #include "dfe_internal.h"
+#include "dfe_mfma_stage.h"
 #include "loss_stack_exact.h"
 #include <cstdint>
 #include <cstdio>
@@ -47,8 +48,6 @@ constexpr int CF_PF1 = 2;          // staged f1 quads per thread and chunk (forw
 constexpr int CB_CK = 8;           // channels per thread (backward)
 constexpr int CB_STAGE = 12;       // tile quads per thread and staging batch (backward)
 constexpr int CORR_MAX_LDS = 160 * 1024;
-
-struct __attribute__((packed, aligned(4))) QuadU4 { float a, b, c, d; };     // dword-aligned 16 bytes
 
 struct MagicDiv { unsigned m, d; };   // q = e / d for e * d < 2^32
 __device__ __forceinline__ unsigned mdiv(unsigned e, MagicDiv k) { return k.d == 1 ? e : __umulhi(e, k.m); }
@@ -98,7 +97,7 @@ struct CorrBwdSide { const float* other; float* gin; const float* addend; long a
 __device__ __forceinline__ float4 load_quad_checked(const float* __restrict__ p, int gx, int W) {
   // p points at column gx of a valid row; elements outside [0, W) read as zero
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (gx >= 0 && gx + 3 < W) { const QuadU4 q = *reinterpret_cast<const QuadU4*>(p); v = make_float4(q.a, q.b, q.c, q.d); }
+  if (gx >= 0 && gx + 3 < W) { const QuadU q = *reinterpret_cast<const QuadU*>(p); v = make_float4(q.a, q.b, q.c, q.d); }
   else {
     if (gx >= 0 && gx < W) v.x = p[0];
     if (gx + 1 >= 0 && gx + 1 < W) v.y = p[1];
@@ -384,7 +383,7 @@ __device__ __forceinline__ void corr_bwd_body(float* smem, const CorrBwdSide sd,
         const int gx = x0 - CR_D + j;
         float4 v;
         if (VEC && j == CR_D) v = *reinterpret_cast<const float4*>(gp - static_cast<long>(j) * HW + j);   // the centre column is the thread's own aligned quad
-        else if (gx >= 0 && gx + 3 < W) { const QuadU4 qv = *reinterpret_cast<const QuadU4*>(gp - static_cast<long>(j) * HW + j); v = make_float4(qv.a, qv.b, qv.c, qv.d); }
+        else if (gx >= 0 && gx + 3 < W) { const QuadU qv = *reinterpret_cast<const QuadU*>(gp - static_cast<long>(j) * HW + j); v = make_float4(qv.a, qv.b, qv.c, qv.d); }
         else v = load_quad_checked(gp - static_cast<long>(j) * HW + j, gx, W);
         gq[j][0] = row_ok ? v.x : 0.0f; gq[j][1] = row_ok ? v.y : 0.0f; gq[j][2] = row_ok ? v.z : 0.0f; gq[j][3] = row_ok ? v.w : 0.0f;
       }

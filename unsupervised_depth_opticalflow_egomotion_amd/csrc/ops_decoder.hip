@@ -12,6 +12,7 @@
 // Arithmetic: elu(x) = x > 0 ? x : exp(x) - 1; elu'(x) = x > 0 ? 1 : exp(x) (ATen: expm1 / exp);
 // bilinear x2 with align_corners=False: src = max(0.5*(dst+0.5)-0.5, 0), (v0*l0 + v1*l1) horizontally first.
 #include "dfe_internal.h"
+#include "dfe_mfma_stage.h"
 #include "dfe_device.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -135,8 +136,6 @@ __global__ void __launch_bounds__(256) k_elu_pad_bwd_pair(const float* __restric
 // of the padded gradient (it sits one element to the right: offset +1); the quads that contain column 1 or W-2 and
 // the rows 1 and H-2 collect the mirrored padding entries element by element.  Round 3: the pair kernels above move
 // 8 bytes per lane and instruction and stop at 3 TB/s on the decoder's large planes.
-struct __attribute__((packed, aligned(4))) QuadU { float a, b, c, d; };     // dword-aligned 16 bytes
-
 __device__ __forceinline__ float4 pad_adjoint_quad(const float* __restrict__ g, int iy, int ix, int H, int W) {
   if (iy != 1 && iy != H - 2 && ix != 0 && ix != W - 4) {
     const QuadU q = *reinterpret_cast<const QuadU*>(g + static_cast<long>(iy + 1) * (W + 2) + ix + 1);

@@ -18,13 +18,13 @@
 //     32 x 32 channel tile); k_planeconv_finish adds the per-block partial planes in unit order.
 // Bound: launch latency and the LDS round trip of one chunk (the whole of level 6 is 0.5 GFLOP and 2.5 MB of weights).
 #include "dfe_internal.h"
+#include "dfe_mfma_stage.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
 
 namespace dfe {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PC_CC = 16;        // channels per staged chunk (4 K-steps per tap)
 constexpr int PC_MT = 64;        // pixels per block: 4 waves x one 16-pixel M tile

@@ -18,16 +18,13 @@
 // their sums have one fixed order.  The 1x1 stride-2 layers of the same mode: ops_conv1x1s2.hip.
 #include "dfe_internal.h"
 #include "dfe_device.h"
+#include "dfe_mfma_stage.h"
 #include "dfe_wgrad_sum.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
 
 namespace dfe {
-
-typedef float sc_f32x4 __attribute__((ext_vector_type(4)));
-typedef float sc_f32x2 __attribute__((ext_vector_type(2)));
-struct __attribute__((packed, aligned(4))) ScQuadU { float a, b, c, d; };     // dword-aligned 16 bytes
 
 struct ScWg {
   long xbs, gbs;
@@ -89,11 +86,10 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
   const int gr_ = gpos / GSL, gs_ = gpos - gr_ * GSL;
   const bool gact = gpos < g.TH * GSL;
   const int gl0 = XTOT + gcg * g.GCS + gr_ * g.TW + 4 * gs_;
-  sc_f32x4 xr[NXL], gr[NGL];
+  f32x4 xr[NXL], gr[NGL];
 
-  // Loads are straight-line: a 16-byte load from the slot's address -- or from the tensor's first words when the slot is outside
-  // the image, another channel than the layer has, or cut by the image's edge -- and a select; the cut slots (two per row) are
-  // then patched word by word under one branch that whole waves skip.
+  // the loads' safe address: the sample's first words (sc_wg_plan: no tensor of fewer than four)
+  const int xnch = min(g.CIB, g.Ci - cib0), gnch = min(g.COB, g.Co - cob0);
   auto load_chunk = [&](int c) {
     const int cx = c % g.cpr, ry = (c / g.cpr) % g.rpi, img = c / g.cpr / g.rpi;
     {
@@ -102,25 +98,7 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
       const bool full = rowok && ix >= 0 && ix + 3 < g.W;
       const bool cut = rowok && !full && ix + 3 >= 0 && ix < g.W;
       const float* xb = x + img * g.xbs;
-      const int off0 = (cib0 + xcg) * HW + iy * g.W + ix;
-#pragma unroll
-      for (int jj = 0; jj < NXL; ++jj) {
-          const int ch = xcg + jj * xncg;
-          const bool ok = full && ch < g.CIB && cib0 + ch < g.Ci;
-          const ScQuadU u = *reinterpret_cast<const ScQuadU*>(xb + (ok ? off0 + jj * xncg * HW : 0));
-          xr[jj] = sc_f32x4{ok ? u.a : 0.0f, ok ? u.b : 0.0f, ok ? u.c : 0.0f, ok ? u.d : 0.0f};
-        }
-      if (cut) {
-#pragma unroll
-        for (int jj = 0; jj < NXL; ++jj) {
-            const int ch = xcg + jj * xncg;
-            if (ch < g.CIB && cib0 + ch < g.Ci) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (ix + e >= 0 && ix + e < g.W) xr[jj][e] = xb[off0 + jj * xncg * HW + e];
-            }
-          }
-      }
+      load_slots(xr, xb, (cib0 + xcg) * HW + iy * g.W + ix, HW, xcg, xncg, xnch, ix, g.W, full, cut);
     }
     {
       const int oy = ry * g.TH + gr_, ox = cx * g.TW + 4 * gs_;
@@ -128,25 +106,7 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
       const bool full = rowok && ox + 3 < g.Wo;
       const bool cut = rowok && !full && ox < g.Wo;
       const float* gb = gy + img * g.gbs;
-      const int off0 = (cob0 + gcg) * gHW + oy * g.Wo + ox;
-#pragma unroll
-      for (int jj = 0; jj < NGL; ++jj) {
-          const int ch = gcg + jj * gncg;
-          const bool ok = full && ch < g.COB && cob0 + ch < g.Co;
-          const ScQuadU u = *reinterpret_cast<const ScQuadU*>(gb + (ok ? off0 + jj * gncg * gHW : 0));
-          gr[jj] = sc_f32x4{ok ? u.a : 0.0f, ok ? u.b : 0.0f, ok ? u.c : 0.0f, ok ? u.d : 0.0f};
-        }
-      if (cut) {
-#pragma unroll
-        for (int jj = 0; jj < NGL; ++jj) {
-            const int ch = gcg + jj * gncg;
-            if (ch < g.COB && cob0 + ch < g.Co) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (ox + e < g.Wo) gr[jj][e] = gb[off0 + jj * gncg * gHW + e];
-            }
-          }
-      }
+      load_slots(gr, gb, (cob0 + gcg) * gHW + oy * g.Wo + ox, gHW, gcg, gncg, gnch, ox, g.Wo, full, cut);
     }
   };
   // the LDS regions hold whole thread groups of channels (XCH / GCH >= CIB / COB): every active thread stores
@@ -154,31 +114,18 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
     if (xact) {
 #pragma unroll
       for (int jj = 0; jj < NXL; ++jj) {
-          float* d = lds + xl0 + jj * xncg * g.XCS;
-          if (g.S == 2) {
-            *reinterpret_cast<sc_f32x2*>(d) = sc_f32x2{xr[jj][0], xr[jj][2]};
-            *reinterpret_cast<sc_f32x2*>(d + g.QW) = sc_f32x2{xr[jj][1], xr[jj][3]};
-          } else {
-            *reinterpret_cast<sc_f32x2*>(d) = sc_f32x2{xr[jj][0], xr[jj][1]};
-            *reinterpret_cast<sc_f32x2*>(d + 2) = sc_f32x2{xr[jj][2], xr[jj][3]};
-          }
-        }
+        float* d = lds + xl0 + jj * xncg * g.XCS;
+        if (g.S == 2) store_slot_split(d, g.QW, xr[jj]);
+        else store_slot_pairs(d, xr[jj]);
+      }
     }
     if (gact) {
 #pragma unroll
-      for (int jj = 0; jj < NGL; ++jj) {      // two 8-byte stores: the channel stride is even, not a multiple of four
-          float* d = lds + gl0 + jj * gncg * g.GCS;
-          *reinterpret_cast<sc_f32x2*>(d) = sc_f32x2{gr[jj][0], gr[jj][1]};
-          *reinterpret_cast<sc_f32x2*>(d + 2) = sc_f32x2{gr[jj][2], gr[jj][3]};
-        }
+      for (int jj = 0; jj < NGL; ++jj) store_slot_pairs(lds + gl0 + jj * gncg * g.GCS, gr[jj]);      // the channel stride is even, not a multiple of four
     }
   };
 
-  sc_f32x4 acc[MT][NT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[mt][j] = sc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 acc[MT][NT] = {};
 
   if (c_beg < c_end) {
     load_chunk(c_beg);
@@ -213,10 +160,7 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
 #pragma unroll
           for (int j = 0; j < NT; ++j) b1[j] = lds[pb[j] + 4];
           __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[mt], b0[j], acc[mt][j], 0, 0, 0);
+          mfma_tile(acc, a0, b0);
           __builtin_amdgcn_sched_barrier(0);
           // unconditional (past the row's end in the last trip: words nobody uses, inside the allocation + its 16-word tail): a
           // branch here makes the compiler wait for ALL outstanding LDS words at the loop's head
@@ -225,22 +169,14 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
 #pragma unroll
           for (int j = 0; j < NT; ++j) b0[j] = lds[pb[j] + 8];
           __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[mt], b1[j], acc[mt][j], 0, 0, 0);
+          mfma_tile(acc, a1, b1);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) pa[mt] += 8;
 #pragma unroll
           for (int j = 0; j < NT; ++j) pb[j] += 8;
         }
-        if (s4 < n4) {
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[mt], b0[j], acc[mt][j], 0, 0, 0);
-        }
+        if (s4 < n4) mfma_tile(acc, a0, b0);
       }
     }
     __syncthreads();
@@ -272,16 +208,28 @@ k_sconv_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
 // lane's own output pixel (a per-lane LDS offset) plus the tap's uniform offset; x rows are split into even and odd columns as in the
 // weight gradient.  A block = COB output channels x a tile of TH x TW output pixels (16 NT WN pixels, numbered row-major inside the
 // tile), the input channels in chunks of CB; thin layers split the chunks over blocks and k_sconv_sum adds the partials in order.
-struct ScFw {
-  long xbs, ybs;
-  int Ci, Co, H, W, Ho, Wo;
+
+// The geometry of the forward and of the data gradient (below): "staged" is the tensor whose windows go through LDS (x / gy),
+// "written" the one the block's accumulators go to (y / gx).
+struct ScGeo {
+  long sbs, obs;                 // batch strides of the staged and of the written tensor
+  int Ci, Co, H, W, Ho, Wo;      // x and gx are [Ci][H][W], y and gy [Co][Ho][Wo]
   int TH, TW, RI, NSLOT, QW, XRS, XCS;
-  int CB, nck, cps, nsplit;      // channels per chunk, chunks, chunks per split
-  int cpr, rpi, ntile, ncot;
-  int Cop, WRS;                  // padded output channels of the packed filter; LDS row stride of the filter slab
+  int CB, nck, cps, nsplit;      // staged channels per chunk, chunks, chunks per split
+  int cpr, rpi, ntile, ncb;      // tiles per row, tile rows per image, tiles, blocks over the written channels
+  int Mp, WRS;                   // padded written channels of the packed filter; LDS row stride of the filter slab
   int wl4;                       // 16-byte words of a chunk's filter slab
-  float slope;
+  float slope;                   // forward: the activation
 };
+
+// block = (written-channel block fastest: the blocks that share a staged window are neighbours, pixel tile, split)
+struct ScBlock { int cb, cx, ry, img, split, c_beg, c_end; };
+__device__ __forceinline__ ScBlock sc_block(const ScGeo& g) {
+  const unsigned lid = xcd_swizzle(blockIdx.x, gridDim.x), ncb = static_cast<unsigned>(g.ncb), ntile = static_cast<unsigned>(g.ntile);
+  const int tile = static_cast<int>((lid / ncb) % ntile), split = static_cast<int>(lid / (ncb * ntile));
+  return ScBlock{static_cast<int>(lid % ncb), tile % g.cpr, (tile / g.cpr) % g.rpi, tile / g.cpr / g.rpi, split, split * g.cps,
+                 min(g.nck, split * g.cps + g.cps)};
+}
 
 // wp[g4][t][k][Cop] = w[co][4 g4 + k][t] (zero past Ci / Co); TRANSPOSED (data gradient): wp[g4][t][k][Cip] = w[4 g4 + k][ci][t]
 template <bool TRANSPOSED>
@@ -311,20 +259,14 @@ __global__ void k_sconv_sum(const float* __restrict__ part, float* __restrict__ 
 template <int K, int MT, int NT, int WM, int WN, int XSH, int NXL, int NWL>
 __global__ void __launch_bounds__(256, 2)
 k_sconv_fwd(const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias, float* __restrict__ y,
-            float* __restrict__ part, const ScFw g) {
+            float* __restrict__ part, const ScGeo g) {
   constexpr int KK = K * K, P = K / 2, DX = (4 - P % 4) % 4, COB = 16 * MT * WM;
   extern __shared__ float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i = lane & 15, kq = lane >> 4;
   const int wm = wv / WN, wn = wv % WN;
-  const unsigned lid = xcd_swizzle(blockIdx.x, gridDim.x);
-  // block = (co block fastest: the blocks that share an x window are neighbours, pixel tile, split)
-  const int cb_i = static_cast<int>(lid % static_cast<unsigned>(g.ncot));
-  const int tile = static_cast<int>((lid / static_cast<unsigned>(g.ncot)) % static_cast<unsigned>(g.ntile));
-  const int split = static_cast<int>(lid / (static_cast<unsigned>(g.ncot) * static_cast<unsigned>(g.ntile)));
-  const int cob0 = cb_i * COB;
-  const int cx = tile % g.cpr, ry = (tile / g.cpr) % g.rpi, img = tile / g.cpr / g.rpi;
-  const int oy0 = ry * g.TH, ox0 = cx * g.TW;
-  const int c_beg = split * g.cps, c_end = min(g.nck, c_beg + g.cps);
+  const ScBlock bk = sc_block(g);
+  const int cob0 = bk.cb * COB, img = bk.img, split = bk.split, c_beg = bk.c_beg, c_end = bk.c_end;
+  const int oy0 = bk.ry * g.TH, ox0 = bk.cx * g.TW;
   const int HW = g.H * g.W, HWo = g.Ho * g.Wo;
   const int XTOT = g.CB * g.XCS;
 
@@ -350,58 +292,23 @@ k_sconv_fwd(const float* __restrict__ x, const float* __restrict__ wp, const flo
   const bool rowok = xact && iy >= 0 && iy < g.H;
   const bool full = rowok && ix >= 0 && ix + 3 < g.W;
   const bool cut = rowok && !full && ix + 3 >= 0 && ix < g.W;
-  const float* xb = x + img * g.xbs;
+  const float* xb = x + img * g.sbs;      // the loads' safe address: the sample's first words (sc_fw_plan: no x of fewer than four)
   constexpr int WQ = COB / 4;      // 16-byte words per filter row of this block
-  sc_f32x4 xr[NXL], wr[NWL];
+  f32x4 xr[NXL], wr[NWL];
   auto load_chunk = [&](int c) {
-    const int off0 = (c * g.CB + xcg) * HW + iy * g.W + ix;
-#pragma unroll
-    for (int jj = 0; jj < NXL; ++jj) {
-      const int ch = xcg + jj * xncg;
-      const bool ok = full && ch < g.CB && c * g.CB + ch < g.Ci;
-      const ScQuadU u = *reinterpret_cast<const ScQuadU*>(xb + (ok ? off0 + jj * xncg * HW : 0));
-      xr[jj] = sc_f32x4{ok ? u.a : 0.0f, ok ? u.b : 0.0f, ok ? u.c : 0.0f, ok ? u.d : 0.0f};
-    }
-    if (cut) {
-#pragma unroll
-      for (int jj = 0; jj < NXL; ++jj) {
-        const int ch = xcg + jj * xncg;
-        if (ch < g.CB && c * g.CB + ch < g.Ci) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (ix + e >= 0 && ix + e < g.W) xr[jj][e] = xb[off0 + jj * xncg * HW + e];
-        }
-      }
-    }
-    const float* wsrc = wp + static_cast<long>(c) * g.CB * KK * g.Cop + cob0;
-#pragma unroll
-    for (int jj = 0; jj < NWL; ++jj) {
-      const int e = tid + 256 * jj, row = e / WQ, q = e - row * WQ;
-      wr[jj] = e < g.wl4 ? *reinterpret_cast<const sc_f32x4*>(wsrc + static_cast<long>(row) * g.Cop + 4 * q) : sc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
+    load_slots(xr, xb, (c * g.CB + xcg) * HW + iy * g.W + ix, HW, xcg, xncg, min(g.CB, g.Ci - c * g.CB), ix, g.W, full, cut);
+    load_slab<WQ>(wr, wp + static_cast<long>(c) * g.CB * KK * g.Mp + cob0, g.Mp, g.wl4, tid);
   };
   auto store_chunk = [&]() {
     if (xact) {
 #pragma unroll
       for (int jj = 0; jj < NXL; ++jj)
-        if (xcg + jj * xncg < g.CB) {
-          float* d = lds + xl0 + jj * xncg * g.XCS;
-          *reinterpret_cast<sc_f32x2*>(d) = sc_f32x2{xr[jj][0], xr[jj][2]};
-          *reinterpret_cast<sc_f32x2*>(d + g.QW) = sc_f32x2{xr[jj][1], xr[jj][3]};
-        }
+        if (xcg + jj * xncg < g.CB) store_slot_split(lds + xl0 + jj * xncg * g.XCS, g.QW, xr[jj]);
     }
-#pragma unroll
-    for (int jj = 0; jj < NWL; ++jj) {
-      const int e = tid + 256 * jj, row = e / WQ, q = e - row * WQ;
-      if (e < g.wl4) *reinterpret_cast<sc_f32x4*>(lds + XTOT + row * g.WRS + 4 * q) = wr[jj];
-    }
+    store_slab<WQ>(lds + XTOT, g.WRS, wr, g.wl4, tid);
   };
 
-  sc_f32x4 acc[MT][NT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[mt][j] = sc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 acc[MT][NT] = {};
 
   if (c_beg < c_end) {
     load_chunk(c_beg);
@@ -434,10 +341,7 @@ k_sconv_fwd(const float* __restrict__ x, const float* __restrict__ wp, const flo
 #pragma unroll
           for (int kk = 0; kk < KG; ++kk) {
             if (k0 + kk >= K) continue;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-              for (int j = 0; j < NT; ++j) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk][mt], b[kk][j], acc[mt][j], 0, 0, 0);
+            mfma_tile(acc, a[kk], b[kk]);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -452,7 +356,7 @@ k_sconv_fwd(const float* __restrict__ x, const float* __restrict__ wp, const flo
   // ---- epilogue: bias + activation and y, or this split's partial sums
   const bool direct = g.nsplit == 1;
   const int nimg = g.ntile / (g.cpr * g.rpi);
-  float* ob = direct ? y + img * g.ybs : part + (static_cast<long>(split) * nimg + img) * g.Co * HWo;
+  float* ob = direct ? y + img * g.obs : part + (static_cast<long>(split) * nimg + img) * g.Co * HWo;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -478,32 +382,18 @@ k_sconv_fwd(const float* __restrict__ x, const float* __restrict__ wp, const flo
 // shifted gy operands once and every tap's filter operand once: MFMA count = the forward's, no zero-stuffed work.  The filter slab
 // is k_sconv_pack<true>'s [co / 4][tap][co % 4][Ci]; gy is staged unsplit (stride 1).  1x1 (the ResNet down-sampling shortcuts,
 // depth_model.py:31-36): phase (0, 0) gets w^T gy, the three others zeros.
-struct ScDg {
-  long gbs, xbs;
-  int Ci, Co, H, W, Ho, Wo;        // gx is [Ci][H][W], gy [Co][Ho][Wo]
-  int TH, TW, RI, NSLOT, XRS, XCS;
-  int CB, nck, cps, nsplit;
-  int cpr, rpi, ntile, ncit;
-  int Cip, WRS, wl4;
-};
-
 template <int K, int MT, int NT, int WM, int WN, int XSH, int NXL, int NWL>
 __global__ void __launch_bounds__(256, 2)
-k_sconv_dgrad(const float* __restrict__ gy, const float* __restrict__ wp, float* __restrict__ gx, float* __restrict__ part, const ScDg g) {
+k_sconv_dgrad(const float* __restrict__ gy, const float* __restrict__ wp, float* __restrict__ gx, float* __restrict__ part, const ScGeo g) {
   constexpr int KK = K * K, P = K / 2, CIB = 16 * MT * WM;
   // row shift of tap ky: gy row = u + (py + P - ky) / 2 with py = (ky + P) & 1; DMIN / ND: the smallest shift, the number of shifts
   constexpr int DMIN = K == 5 ? -1 : 0, ND = K == 1 ? 1 : (K == 3 ? 2 : 3), DXA = ((DMIN % 4) + 4) % 4;
   extern __shared__ float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i = lane & 15, kq = lane >> 4;
   const int wm = wv / WN, wn = wv % WN;
-  const unsigned lid = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int cb_i = static_cast<int>(lid % static_cast<unsigned>(g.ncit));
-  const int tile = static_cast<int>((lid / static_cast<unsigned>(g.ncit)) % static_cast<unsigned>(g.ntile));
-  const int split = static_cast<int>(lid / (static_cast<unsigned>(g.ncit) * static_cast<unsigned>(g.ntile)));
-  const int cib0 = cb_i * CIB;
-  const int cx = tile % g.cpr, ry = (tile / g.cpr) % g.rpi, img = tile / g.cpr / g.rpi;
-  const int u0 = ry * g.TH, v0 = cx * g.TW;
-  const int c_beg = split * g.cps, c_end = min(g.nck, c_beg + g.cps);
+  const ScBlock bk = sc_block(g);
+  const int cib0 = bk.cb * CIB, img = bk.img, split = bk.split, c_beg = bk.c_beg, c_end = bk.c_end;
+  const int u0 = bk.ry * g.TH, v0 = bk.cx * g.TW;
   const int gHW = g.Ho * g.Wo, HW = g.H * g.W;
   const int XTOT = g.CB * g.XCS;
 
@@ -527,58 +417,23 @@ k_sconv_dgrad(const float* __restrict__ gy, const float* __restrict__ wp, float*
   const bool rowok = xact && oy >= 0 && oy < g.Ho;
   const bool full = rowok && ox >= 0 && ox + 3 < g.Wo;
   const bool cut = rowok && !full && ox + 3 >= 0 && ox < g.Wo;
-  const float* gb = gy + img * g.gbs;
+  const float* gb = gy + img * g.sbs;      // the loads' safe address: the sample's first words (sc_dg_plan: no gy of fewer than four)
   constexpr int WQ = CIB / 4;
-  sc_f32x4 xr[NXL], wr[NWL];
+  f32x4 xr[NXL], wr[NWL];
   auto load_chunk = [&](int c) {
-    const int off0 = (c * g.CB + xcg) * gHW + oy * g.Wo + ox;
-#pragma unroll
-    for (int jj = 0; jj < NXL; ++jj) {
-      const int ch = xcg + jj * xncg;
-      const bool ok = full && ch < g.CB && c * g.CB + ch < g.Co;
-      const ScQuadU u = *reinterpret_cast<const ScQuadU*>(gb + (ok ? off0 + jj * xncg * gHW : 0));
-      xr[jj] = sc_f32x4{ok ? u.a : 0.0f, ok ? u.b : 0.0f, ok ? u.c : 0.0f, ok ? u.d : 0.0f};
-    }
-    if (cut) {
-#pragma unroll
-      for (int jj = 0; jj < NXL; ++jj) {
-        const int ch = xcg + jj * xncg;
-        if (ch < g.CB && c * g.CB + ch < g.Co) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (ox + e >= 0 && ox + e < g.Wo) xr[jj][e] = gb[off0 + jj * xncg * gHW + e];
-        }
-      }
-    }
-    const float* wsrc = wp + static_cast<long>(c) * g.CB * KK * g.Cip + cib0;
-#pragma unroll
-    for (int jj = 0; jj < NWL; ++jj) {
-      const int e = tid + 256 * jj, row = e / WQ, q = e - row * WQ;
-      wr[jj] = e < g.wl4 ? *reinterpret_cast<const sc_f32x4*>(wsrc + static_cast<long>(row) * g.Cip + 4 * q) : sc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
+    load_slots(xr, gb, (c * g.CB + xcg) * gHW + oy * g.Wo + ox, gHW, xcg, xncg, min(g.CB, g.Co - c * g.CB), ox, g.Wo, full, cut);
+    load_slab<WQ>(wr, wp + static_cast<long>(c) * g.CB * KK * g.Mp + cib0, g.Mp, g.wl4, tid);
   };
   auto store_chunk = [&]() {
     if (xact) {
 #pragma unroll
       for (int jj = 0; jj < NXL; ++jj)
-        if (xcg + jj * xncg < g.CB) *reinterpret_cast<sc_f32x4*>(lds + xl0 + jj * xncg * g.XCS) = xr[jj];
+        if (xcg + jj * xncg < g.CB) *reinterpret_cast<f32x4*>(lds + xl0 + jj * xncg * g.XCS) = xr[jj];
     }
-#pragma unroll
-    for (int jj = 0; jj < NWL; ++jj) {
-      const int e = tid + 256 * jj, row = e / WQ, q = e - row * WQ;
-      if (e < g.wl4) *reinterpret_cast<sc_f32x4*>(lds + XTOT + row * g.WRS + 4 * q) = wr[jj];
-    }
+    store_slab<WQ>(lds + XTOT, g.WRS, wr, g.wl4, tid);
   };
 
-  sc_f32x4 acc[2][2][MT][NT];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[a][b][mt][j] = sc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 acc[2][2][MT][NT] = {};
 
   if (c_beg < c_end) {
     load_chunk(c_beg);
@@ -601,7 +456,6 @@ k_sconv_dgrad(const float* __restrict__ gy, const float* __restrict__ wp, float*
           for (int j = 0; j < NT; ++j) b[dy][dx][j] = lds[boff[j] + bb + dy * g.XRS + dx];
 #pragma unroll
       for (int ky = 0; ky < K; ++ky) {
-        constexpr int dummy = 0; (void)dummy;
         const int py = (ky + P) & 1, dy = (py + P - ky) / 2 - DMIN;
         float a[K][MT];
         const int ab = (c4 * KK + ky * K) * 4 * g.WRS;
@@ -613,11 +467,7 @@ k_sconv_dgrad(const float* __restrict__ gy, const float* __restrict__ wp, float*
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
           const int px = (kx + P) & 1, dx = (px + P - kx) / 2 - DMIN;
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-              acc[py][px][mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kx][mt], b[dy][dx][j], acc[py][px][mt][j], 0, 0, 0);
+          mfma_tile(acc[py][px], a[kx], b[dy][dx]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -631,7 +481,7 @@ k_sconv_dgrad(const float* __restrict__ gy, const float* __restrict__ wp, float*
 
   // ---- gx (or this split's partial sums): the two column phases of a position are neighbours
   const int nimg = g.ntile / (g.cpr * g.rpi);
-  float* ob = g.nsplit == 1 ? gx + img * g.xbs : part + (static_cast<long>(split) * nimg + img) * g.Ci * HW;
+  float* ob = g.nsplit == 1 ? gx + img * g.obs : part + (static_cast<long>(split) * nimg + img) * g.Ci * HW;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -728,22 +578,9 @@ bool sc_wg_plan(int B, int Ci, int Co, int H, int W, int K, int S, int P, ScWg* 
   g.ncit = (Ci + g.CIB - 1) / g.CIB;
   g.ntb = ncot * g.ncit;
   // one resident round of blocks: three per CU for the kernels that fit three waves per SIMD (configurations 1 and 2), else two
-  const int target = g_sc_blocks > 0 ? g_sc_blocks : ((c == 1 || c == 2) ? 768 : 512);
-  long Sp = (target + g.ntb / 2) / g.ntb;
-  Sp = std::max(1L, std::min<long>(Sp, g.nchunks));
-  g.cps = static_cast<int>((g.nchunks + Sp - 1) / Sp);
-  *nsplit = (g.nchunks + g.cps - 1) / g.cps;
+  *nsplit = split_round(g_sc_blocks > 0 ? g_sc_blocks : ((c == 1 || c == 2) ? 768 : 512), g.ntb, g.nchunks, &g.cps);
   *out = g; *cfg = c;
   return true;
-}
-
-template <int MT, int NT, int WM, int WN, int XSH, int NXL, int GSH, int NGL>
-void sc_wg_launch(const ScWg& g, int nsplit, const float* x, const float* gy, float* ws, hipStream_t st) {
-  const size_t lds_bytes = sizeof(float) * (static_cast<size_t>(g.XCH) * g.XCS + static_cast<size_t>(g.GCH) * g.GCS + 16);
-  auto kern = k_sconv_wgrad<MT, NT, WM, WN, XSH, NXL, GSH, NGL>;
-  static bool attr_set = false;      // > 64 KB of dynamic LDS needs the opt-in attribute once per kernel
-  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr_set = true; }
-  kern<<<static_cast<unsigned>(g.ntb) * nsplit, 256, lds_bytes, st>>>(x, gy, ws, g);
 }
 }  // namespace
 
@@ -765,116 +602,128 @@ extern "C" int dfe_sconv_wgrad(const float* x, long x_batch_stride, const float*
   if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return DFE_ERR_DIMS;
   ScWg g; int cfg, ns;
   if (!sc_wg_plan(B, Ci, Co, H, W, K, stride, P, &g, &cfg, &ns)) return DFE_ERR_UNSUPPORTED;
-  const long gplane = static_cast<long>(g.Ho) * g.Wo;
-  if (x_batch_stride < static_cast<long>(Ci) * H * W || gy_batch_stride < Co * gplane) return DFE_ERR_DIMS;
-  if (static_cast<long>(Ci) * H * W >= (1L << 30) || Co * gplane >= (1L << 30) || static_cast<long>(Co) * Ci * K * K >= (1L << 30)) return DFE_ERR_DIMS;
+  const long n = static_cast<long>(Co) * Ci * K * K;
+  if (!sample_ok(x_batch_stride, static_cast<long>(Ci) * H * W) || !sample_ok(gy_batch_stride, static_cast<long>(Co) * g.Ho * g.Wo) || n >= (1L << 30)) return DFE_ERR_DIMS;
   g.xbs = x_batch_stride; g.gbs = gy_batch_stride;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned grid = static_cast<unsigned>(g.ntb) * ns;
+  const size_t lds_bytes = sizeof(float) * (static_cast<size_t>(g.XCH) * g.XCS + static_cast<size_t>(g.GCH) * g.GCS + 16);
+#define SC_WG(...) launch_dyn_lds<k_sconv_wgrad<__VA_ARGS__>>(grid, lds_bytes, 80 * 1024, st, x, gy, ws, g)
   switch (cfg) {
-    case 0: sc_wg_launch<1, 9, 4, 1, 7, 8, 4, 4>(g, ns, x, gy, ws, st); break;
-    case 1: sc_wg_launch<2, 5, 2, 2, 8, 3, 4, 4>(g, ns, x, gy, ws, st); break;
-    case 2: sc_wg_launch<1, 7, 1, 4, 8, 9, 4, 1>(g, ns, x, gy, ws, st); break;
-    default: sc_wg_launch<2, 7, 1, 4, 8, 16, 4, 2>(g, ns, x, gy, ws, st); break;
+    case 0: SC_WG(1, 9, 4, 1, 7, 8, 4, 4); break;
+    case 1: SC_WG(2, 5, 2, 2, 8, 3, 4, 4); break;
+    case 2: SC_WG(1, 7, 1, 4, 8, 9, 4, 1); break;
+    default: SC_WG(2, 7, 1, 4, 8, 16, 4, 2); break;
   }
+#undef SC_WG
   DFE_LAUNCH_CHECK();
-  const long n = static_cast<long>(Co) * Ci * K * K;
-  if (ns > 64) k_wgrad_sum<32><<<static_cast<unsigned>((n + 31) / 32), 1024, 0, st>>>(ws, gweight, ns, n);
-  else k_wgrad_sum<8><<<static_cast<unsigned>((n + 31) / 32), 256, 0, st>>>(ws, gweight, ns, n);
+  launch_wgrad_sum(ws, gweight, ns, n, st);
   DFE_LAUNCH_CHECK();
   return DFE_OK;
 }
 
-// ---- forward, host side
+// ---- forward and data gradient, host side
 namespace {
 int sc_pad16(int v) { return v + ((48 - (v & 31)) & 31); }      // the next stride with stride % 32 == 16
 
-struct ScFwCfg { int k, t32, cb, nwl; };      // the instantiations: filter size, 32- or 64-channel block, channels per chunk, filter words per thread
-
-bool sc_fw_plan(int B, int Ci, int Co, int H, int W, int K, ScFw* out, int* t32) {
-  if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0 || (K != 3 && K != 5 && K != 7)) return false;
-  if (static_cast<long>(Ci) * H * W < 4) return false;
-  const int P = K / 2, DX = (4 - P % 4) % 4, KK = K * K;
-  ScFw g = {};
-  g.Ci = Ci; g.Co = Co; g.H = H; g.W = W;
-  g.Ho = (H + 2 * P - K) / 2 + 1; g.Wo = (W + 2 * P - K) / 2 + 1;
-  if (g.Ho < 1 || g.Wo < 1) return false;
-  *t32 = Co <= 32;
-  const int COB = *t32 ? 32 : 64, NPIX = 128;
-  const int cip = (Ci + 3) / 4 * 4;
-  g.CB = K == 3 ? std::min(8, cip) : 4;
-  g.nck = (cip + g.CB - 1) / g.CB;
-  g.Cop = (Co + 63) / 64 * 64;
-  g.WRS = COB + 16;
-  g.wl4 = g.CB * KK * COB / 4;
-  g.ncot = (Co + COB - 1) / COB;
-  // the pixel tile: TW (even: the staged window starts on a multiple of four columns) x TH <= 128 pixels whose window fits the 256
-  // staging positions and the LDS; the most useful pixels per tile
+// The pixel tile and the channel split of the forward and of the data gradient.  The block's tile is TH x TW of the rows x cols
+// grid it walks (TW a multiple of 4 / S: the staged window starts on a multiple of four columns), at most npix positions, whose
+// staged window -- S (TH - 1) + ext rows, S (TW - 1) + ext + dx columns -- fits maxpos staging positions and lds_kb of LDS with
+// the filter slab; the most useful positions per tile.  Before: Ci ... Wo, CB, WRS and ncb of *g.
+bool sc_tile_plan(ScGeo* g, int B, int KK, int rows, int cols, int npix, int S, int ext, int dx, int maxpos, int lds_kb) {
+  const int step = 4 / S;
   double best = 0.0;
-  for (int tw = std::min(64, (g.Wo + 1) / 2 * 2); tw >= 2; tw -= 2) {
-    const int th = std::min(NPIX / tw, g.Ho);
+  for (int tw = std::min(64, (cols + step - 1) / step * step); tw >= step; tw -= step) {
+    const int th = std::min(npix / tw, rows);
     if (th < 1) continue;
-    const int ri = 2 * (th - 1) + K, nslot = (2 * (tw - 1) + K + DX + 3) / 4;
-    if (ri * nslot > 256) continue;
-    const int qw = 2 * nslot, xrs = 2 * qw, xcs = sc_pad16(ri * xrs);
-    if (sizeof(float) * (static_cast<size_t>(g.CB) * xcs + static_cast<size_t>(g.CB) * KK * g.WRS + 64) > 80 * 1024) continue;
-    const int cpr = (g.Wo + tw - 1) / tw, rpi = (g.Ho + th - 1) / th;
-    const double eff = static_cast<double>(g.Ho) * g.Wo / (static_cast<double>(cpr) * rpi * NPIX);
-    if (eff > best + 1e-9) { best = eff; g.TW = tw; g.TH = th; g.RI = ri; g.NSLOT = nslot; g.QW = qw; g.XRS = xrs; g.XCS = xcs; g.cpr = cpr; g.rpi = rpi; }
+    const int ri = S * (th - 1) + ext, nslot = (S * (tw - 1) + ext + dx + 3) / 4;
+    if (ri * nslot > maxpos) continue;
+    const int xrs = 4 * nslot, xcs = sc_pad16(ri * xrs);
+    if (sizeof(float) * (static_cast<size_t>(g->CB) * xcs + static_cast<size_t>(g->CB) * KK * g->WRS + 64) > static_cast<size_t>(lds_kb) * 1024) continue;
+    const int cpr = (cols + tw - 1) / tw, rpi = (rows + th - 1) / th;
+    const double eff = static_cast<double>(rows) * cols / (static_cast<double>(cpr) * rpi * npix);
+    if (eff > best + 1e-9) { best = eff; g->TW = tw; g->TH = th; g->RI = ri; g->NSLOT = nslot; g->QW = 2 * nslot; g->XRS = xrs; g->XCS = xcs; g->cpr = cpr; g->rpi = rpi; }
   }
   if (best == 0.0) return false;
-  const long nt = static_cast<long>(B) * g.cpr * g.rpi;
-  if (nt * g.ncot >= (1L << 24)) return false;
-  g.ntile = static_cast<int>(nt);
+  const long nt = static_cast<long>(B) * g->cpr * g->rpi, blocks = nt * g->ncb;
+  if (blocks >= (1L << 24)) return false;
+  g->ntile = static_cast<int>(nt);
   // thin layers: the channel chunks are split over blocks until there are two blocks per CU
-  const long blocks = nt * g.ncot;
-  long sp = blocks >= 384 ? 1 : std::min<long>(g.nck, (512 + blocks - 1) / blocks);
-  g.cps = static_cast<int>((g.nck + sp - 1) / sp);
-  g.nsplit = (g.nck + g.cps - 1) / g.cps;
-  *out = g;
+  const long sp = blocks >= 384 ? 1 : std::min<long>(g->nck, (512 + blocks - 1) / blocks);
+  g->cps = static_cast<int>((g->nck + sp - 1) / sp);
+  g->nsplit = (g->nck + g->cps - 1) / g->cps;
   return true;
 }
 
-long sc_fw_packed_floats(const ScFw& g, int K) { return static_cast<long>(g.nck) * g.CB * K * K * g.Cop + 64; }
-
-template <int K, int MT, int NT, int WM, int WN, int NXL, int NWL>
-void sc_fw_launch(const ScFw& g, const float* x, const float* wp, const float* bias, float* y, float* part, hipStream_t st) {
-  const size_t lds_bytes = sizeof(float) * (static_cast<size_t>(g.CB) * g.XCS + static_cast<size_t>(g.CB) * K * K * g.WRS + 64);
-  auto kern = k_sconv_fwd<K, MT, NT, WM, WN, 8, NXL, NWL>;
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr_set = true; }
-  kern<<<static_cast<unsigned>(g.ntile) * g.ncot * g.nsplit, 256, lds_bytes, st>>>(x, wp, bias, y, part, g);
+// what both passes derive from the layer alone; *t32: the written tensor gets 32-channel blocks (else 64)
+bool sc_geo_init(ScGeo* g, int B, int Ci, int Co, int H, int W, int K, bool dgrad, int* t32) {
+  if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return false;
+  const int P = K / 2;
+  *g = ScGeo{};
+  g->Ci = Ci; g->Co = Co; g->H = H; g->W = W;
+  g->Ho = (H + 2 * P - K) / 2 + 1; g->Wo = (W + 2 * P - K) / 2 + 1;
+  // the loads' safe address: the staged tensor's first four words
+  if (g->Ho < 1 || g->Wo < 1 || (dgrad ? static_cast<long>(Co) * g->Ho * g->Wo : static_cast<long>(Ci) * H * W) < 4) return false;
+  const int staged = dgrad ? Co : Ci, written = dgrad ? Ci : Co, sp4 = (staged + 3) / 4 * 4;
+  *t32 = written <= 32;
+  const int blk = *t32 ? 32 : 64;
+  g->CB = dgrad ? std::min(K == 5 ? 8 : 16, sp4) : (K == 3 ? std::min(8, sp4) : 4);
+  g->nck = (sp4 + g->CB - 1) / g->CB;
+  g->Mp = (written + 63) / 64 * 64;
+  g->WRS = blk + 16;
+  g->wl4 = g->CB * K * K * blk / 4;
+  g->ncb = (written + blk - 1) / blk;
+  return true;
 }
+
+bool sc_fw_plan(int B, int Ci, int Co, int H, int W, int K, ScGeo* g, int* t32) {
+  if ((K != 3 && K != 5 && K != 7) || !sc_geo_init(g, B, Ci, Co, H, W, K, false, t32)) return false;
+  const int P = K / 2;
+  return sc_tile_plan(g, B, K * K, g->Ho, g->Wo, 128, 2, K, (4 - P % 4) % 4, 256, 80);
+}
+
+// the data gradient walks the positions (u, v) of the half-resolution grid whose phases the block writes: ceil(H / 2) x ceil(W / 2)
+bool sc_dg_plan(int B, int Ci, int Co, int H, int W, int K, ScGeo* g, int* t32) {
+  if ((K != 1 && K != 3 && K != 5) || !sc_geo_init(g, B, Ci, Co, H, W, K, true, t32)) return false;
+  const int dmin = K == 5 ? -1 : 0, nd = K == 1 ? 1 : (K == 3 ? 2 : 3), dxa = ((dmin % 4) + 4) % 4;
+  return sc_tile_plan(g, B, K * K, (H + 1) / 2, (W + 1) / 2, *t32 ? 128 : 64, 1, nd, dxa, 64, 76);
+}
+
+long sc_packed_floats(const ScGeo& g, int K) { return static_cast<long>(g.nck) * g.CB * K * K * g.Mp + 64; }
+size_t sc_lds_bytes(const ScGeo& g, int K) { return sizeof(float) * (static_cast<size_t>(g.CB) * g.XCS + static_cast<size_t>(g.CB) * K * K * g.WRS + 64); }
 }  // namespace
 
 extern "C" long dfe_sconv_fwd_floats(int B, int Ci, int Co, int H, int W, int K) {
-  ScFw g; int t32;
+  ScGeo g; int t32;
   if (!sc_fw_plan(B, Ci, Co, H, W, K, &g, &t32)) return 0;
-  return sc_fw_packed_floats(g, K) + (g.nsplit > 1 ? static_cast<long>(g.nsplit) * B * Co * g.Ho * g.Wo : 0);
+  return sc_packed_floats(g, K) + (g.nsplit > 1 ? static_cast<long>(g.nsplit) * B * Co * g.Ho * g.Wo : 0);
 }
 
 extern "C" int dfe_sconv_fwd(const float* x, long x_batch_stride, const float* weight, const float* bias, float slope, float* y,
                              long y_batch_stride, float* ws, int B, int Ci, int Co, int H, int W, int K, void* stream) {
   if (!x || !weight || !y || !ws) return DFE_ERR_NULL;
   if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return DFE_ERR_DIMS;
-  ScFw g; int t32;
+  ScGeo g; int t32;
   if (!sc_fw_plan(B, Ci, Co, H, W, K, &g, &t32)) return DFE_ERR_UNSUPPORTED;
   const long oplane = static_cast<long>(g.Ho) * g.Wo;
-  if (x_batch_stride < static_cast<long>(Ci) * H * W || y_batch_stride < Co * oplane) return DFE_ERR_DIMS;
-  if (static_cast<long>(Ci) * H * W >= (1L << 30) || Co * oplane >= (1L << 30)) return DFE_ERR_DIMS;
+  if (!sample_ok(x_batch_stride, static_cast<long>(Ci) * H * W) || !sample_ok(y_batch_stride, Co * oplane)) return DFE_ERR_DIMS;
   if (!aligned16(ws)) return DFE_ERR_UNSUPPORTED;      // the packed filter is read with 16-byte loads
-  g.xbs = x_batch_stride; g.ybs = y_batch_stride; g.slope = slope;
+  g.sbs = x_batch_stride; g.obs = y_batch_stride; g.slope = slope;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int rows = g.nck * g.CB * K * K;
-  const long npk = static_cast<long>(rows) * g.Cop;
-  k_sconv_pack<false><<<static_cast<unsigned>((npk + 255) / 256), 256, 0, st>>>(weight, ws, Co, Ci, K * K, g.Cop, rows);
+  const long npk = static_cast<long>(rows) * g.Mp;
+  k_sconv_pack<false><<<static_cast<unsigned>((npk + 255) / 256), 256, 0, st>>>(weight, ws, Co, Ci, K * K, g.Mp, rows);
   DFE_LAUNCH_CHECK();
-  float* part = ws + sc_fw_packed_floats(g, K);
-  if (K == 3 && !t32) sc_fw_launch<3, 2, 4, 2, 2, 8, 5>(g, x, ws, bias, y, part, st);
-  else if (K == 3) sc_fw_launch<3, 2, 2, 1, 4, 8, 3>(g, x, ws, bias, y, part, st);
-  else if (K == 5 && !t32) sc_fw_launch<5, 2, 4, 2, 2, 4, 7>(g, x, ws, bias, y, part, st);
-  else if (K == 5) sc_fw_launch<5, 2, 2, 1, 4, 4, 4>(g, x, ws, bias, y, part, st);
-  else if (!t32) sc_fw_launch<7, 2, 4, 2, 2, 4, 13>(g, x, ws, bias, y, part, st);
-  else sc_fw_launch<7, 2, 2, 1, 4, 4, 7>(g, x, ws, bias, y, part, st);
+  float* part = ws + sc_packed_floats(g, K);
+  const unsigned grid = static_cast<unsigned>(g.ntile) * g.ncb * g.nsplit;
+#define SC_FW(...) launch_dyn_lds<k_sconv_fwd<__VA_ARGS__>>(grid, sc_lds_bytes(g, K), 80 * 1024, st, x, ws, bias, y, part, g)
+  if (K == 3 && !t32) SC_FW(3, 2, 4, 2, 2, 8, 8, 5);
+  else if (K == 3) SC_FW(3, 2, 2, 1, 4, 8, 8, 3);
+  else if (K == 5 && !t32) SC_FW(5, 2, 4, 2, 2, 8, 4, 7);
+  else if (K == 5) SC_FW(5, 2, 2, 1, 4, 8, 4, 4);
+  else if (!t32) SC_FW(7, 2, 4, 2, 2, 8, 4, 13);
+  else SC_FW(7, 2, 2, 1, 4, 8, 4, 7);
+#undef SC_FW
   DFE_LAUNCH_CHECK();
   if (g.nsplit > 1) {
     const long per_img = Co * oplane, n = per_img * B;
@@ -884,92 +733,37 @@ extern "C" int dfe_sconv_fwd(const float* x, long x_batch_stride, const float* w
   return DFE_OK;
 }
 
-// ---- data gradient, host side
-namespace {
-bool sc_dg_plan(int B, int Ci, int Co, int H, int W, int K, ScDg* out, int* t32) {
-  if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0 || (K != 1 && K != 3 && K != 5)) return false;
-  const int P = K / 2, KK = K * K;
-  ScDg g = {};
-  g.Ci = Ci; g.Co = Co; g.H = H; g.W = W;
-  g.Ho = (H + 2 * P - K) / 2 + 1; g.Wo = (W + 2 * P - K) / 2 + 1;
-  if (g.Ho < 1 || g.Wo < 1 || static_cast<long>(Co) * g.Ho * g.Wo < 4) return false;
-  *t32 = Ci <= 32;
-  const int CIB = *t32 ? 32 : 64, NPIX = *t32 ? 128 : 64;
-  const int cop = (Co + 3) / 4 * 4;
-  g.CB = K == 5 ? std::min(8, cop) : std::min(16, cop);
-  g.nck = (cop + g.CB - 1) / g.CB;
-  g.Cip = (Ci + 63) / 64 * 64;
-  g.WRS = CIB + 16;
-  g.wl4 = g.CB * KK * CIB / 4;
-  g.ncit = (Ci + CIB - 1) / CIB;
-  const int dmin = K == 5 ? -1 : 0, nd = K == 1 ? 1 : (K == 3 ? 2 : 3), dxa = ((dmin % 4) + 4) % 4;
-  // positions (u, v) of the half-resolution grid whose phases the block writes: U x V = ceil(H / 2) x ceil(W / 2)
-  const int U = (H + 1) / 2, V = (W + 1) / 2;
-  double best = 0.0;
-  for (int tw = std::min(64, (V + 3) / 4 * 4); tw >= 4; tw -= 4) {
-    const int th = std::min(NPIX / tw, U);
-    if (th < 1) continue;
-    const int ri = th + nd - 1, nslot = (tw + nd - 1 + dxa + 3) / 4;
-    if (ri * nslot > 64) continue;
-    const int xrs = 4 * nslot, xcs = sc_pad16(ri * xrs);
-    if (sizeof(float) * (static_cast<size_t>(g.CB) * xcs + static_cast<size_t>(g.CB) * KK * g.WRS + 64) > 76 * 1024) continue;
-    const int cpr = (V + tw - 1) / tw, rpi = (U + th - 1) / th;
-    const double eff = static_cast<double>(U) * V / (static_cast<double>(cpr) * rpi * NPIX);
-    if (eff > best + 1e-9) { best = eff; g.TW = tw; g.TH = th; g.RI = ri; g.NSLOT = nslot; g.XRS = xrs; g.XCS = xcs; g.cpr = cpr; g.rpi = rpi; }
-  }
-  if (best == 0.0) return false;
-  const long nt = static_cast<long>(B) * g.cpr * g.rpi;
-  if (nt * g.ncit >= (1L << 24)) return false;
-  g.ntile = static_cast<int>(nt);
-  const long blocks = nt * g.ncit;
-  long sp = blocks >= 384 ? 1 : std::min<long>(g.nck, (512 + blocks - 1) / blocks);
-  g.cps = static_cast<int>((g.nck + sp - 1) / sp);
-  g.nsplit = (g.nck + g.cps - 1) / g.cps;
-  *out = g;
-  return true;
-}
-
-long sc_dg_packed_floats(const ScDg& g, int K) { return static_cast<long>(g.nck) * g.CB * K * K * g.Cip + 64; }
-
-template <int K, int MT, int NT, int WM, int WN, int NXL, int NWL>
-void sc_dg_launch(const ScDg& g, const float* gy, const float* wp, float* gx, float* part, hipStream_t st) {
-  const size_t lds_bytes = sizeof(float) * (static_cast<size_t>(g.CB) * g.XCS + static_cast<size_t>(g.CB) * K * K * g.WRS + 64);
-  auto kern = k_sconv_dgrad<K, MT, NT, WM, WN, 6, NXL, NWL>;
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr_set = true; }
-  kern<<<static_cast<unsigned>(g.ntile) * g.ncit * g.nsplit, 256, lds_bytes, st>>>(gy, wp, gx, part, g);
-}
-}  // namespace
-
 extern "C" long dfe_sconv_dgrad_floats(int B, int Ci, int Co, int H, int W, int K) {
-  ScDg g; int t32;
+  ScGeo g; int t32;
   if (!sc_dg_plan(B, Ci, Co, H, W, K, &g, &t32)) return 0;
-  return sc_dg_packed_floats(g, K) + (g.nsplit > 1 ? static_cast<long>(g.nsplit) * B * Ci * H * W : 0);
+  return sc_packed_floats(g, K) + (g.nsplit > 1 ? static_cast<long>(g.nsplit) * B * Ci * H * W : 0);
 }
 
 extern "C" int dfe_sconv_dgrad(const float* gy, long gy_batch_stride, const float* weight, float* gx, long gx_batch_stride, float* ws, int B,
                                int Ci, int Co, int H, int W, int K, void* stream) {
   if (!gy || !weight || !gx || !ws) return DFE_ERR_NULL;
   if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return DFE_ERR_DIMS;
-  ScDg g; int t32;
+  ScGeo g; int t32;
   if (!sc_dg_plan(B, Ci, Co, H, W, K, &g, &t32)) return DFE_ERR_UNSUPPORTED;
   const long oplane = static_cast<long>(g.Ho) * g.Wo, iplane = static_cast<long>(H) * W;
-  if (gx_batch_stride < Ci * iplane || gy_batch_stride < Co * oplane) return DFE_ERR_DIMS;
-  if (Ci * iplane >= (1L << 30) || Co * oplane >= (1L << 30)) return DFE_ERR_DIMS;
+  if (!sample_ok(gx_batch_stride, Ci * iplane) || !sample_ok(gy_batch_stride, Co * oplane)) return DFE_ERR_DIMS;
   if (!aligned16(ws)) return DFE_ERR_UNSUPPORTED;      // the packed filter is read with 16-byte loads
-  g.gbs = gy_batch_stride; g.xbs = gx_batch_stride;
+  g.sbs = gy_batch_stride; g.obs = gx_batch_stride;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int rows = g.nck * g.CB * K * K;
-  const long npk = static_cast<long>(rows) * g.Cip;
-  k_sconv_pack<true><<<static_cast<unsigned>((npk + 255) / 256), 256, 0, st>>>(weight, ws, Co, Ci, K * K, g.Cip, rows);
+  const long npk = static_cast<long>(rows) * g.Mp;
+  k_sconv_pack<true><<<static_cast<unsigned>((npk + 255) / 256), 256, 0, st>>>(weight, ws, Co, Ci, K * K, g.Mp, rows);
   DFE_LAUNCH_CHECK();
-  float* part = ws + sc_dg_packed_floats(g, K);
-  if (K == 3 && !t32) sc_dg_launch<3, 2, 2, 2, 2, 4, 9>(g, gy, ws, gx, part, st);
-  else if (K == 3) sc_dg_launch<3, 2, 2, 1, 4, 4, 5>(g, gy, ws, gx, part, st);
-  else if (K == 5 && !t32) sc_dg_launch<5, 2, 2, 2, 2, 2, 13>(g, gy, ws, gx, part, st);
-  else if (K == 5) sc_dg_launch<5, 2, 2, 1, 4, 2, 7>(g, gy, ws, gx, part, st);
-  else if (!t32) sc_dg_launch<1, 2, 2, 2, 2, 4, 1>(g, gy, ws, gx, part, st);
-  else sc_dg_launch<1, 2, 2, 1, 4, 4, 1>(g, gy, ws, gx, part, st);
+  float* part = ws + sc_packed_floats(g, K);
+  const unsigned grid = static_cast<unsigned>(g.ntile) * g.ncb * g.nsplit;
+#define SC_DG(...) launch_dyn_lds<k_sconv_dgrad<__VA_ARGS__>>(grid, sc_lds_bytes(g, K), 80 * 1024, st, gy, ws, gx, part, g)
+  if (K == 3 && !t32) SC_DG(3, 2, 2, 2, 2, 6, 4, 9);
+  else if (K == 3) SC_DG(3, 2, 2, 1, 4, 6, 4, 5);
+  else if (K == 5 && !t32) SC_DG(5, 2, 2, 2, 2, 6, 2, 13);
+  else if (K == 5) SC_DG(5, 2, 2, 1, 4, 6, 2, 7);
+  else if (!t32) SC_DG(1, 2, 2, 2, 2, 6, 4, 1);
+  else SC_DG(1, 2, 2, 1, 4, 6, 4, 1);
+#undef SC_DG
   DFE_LAUNCH_CHECK();
   if (g.nsplit > 1) {
     const long per_img = Ci * iplane, n = per_img * B;

@@ -11,11 +11,11 @@
 // partial sums are added in a fixed order by a second kernel (no atomics: reproducible).  fp32 MFMA is an exact fma chain.
 // Bound: MFMA (157 TFLOP/s fp32) for Ci >= 32, HBM below.
 #include "dfe_internal.h"
+#include "dfe_mfma_stage.h"
 #include <hip/hip_runtime.h>
 
 namespace dfe {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(8))) F2 { float a, b; };
 
 // grid: x = unit = (b * nrg + row group) * nseg + column segment, y = group of NCI ci tiles, z = group of NCO co tiles;

@@ -16,6 +16,7 @@
 // Same numerics class as the MIOpen kernels it replaces (fp32 Winograd F(2,3)); sums in a fixed order: reproducible.
 // Bound: MFMA (2.25 x 157 TFLOP/s effective at 100 % of the fp32 matrix pipe; measured 51 %).
 #include "dfe_internal.h"
+#include "dfe_mfma_stage.h"
 #include "dfe_device.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -23,9 +24,6 @@
 
 namespace dfe {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Optional epilogue of the output transform (round 5): y = act(conv + bias[k]) with act(v) = v > 0 ? v : slope v -- the arithmetic
 // of dfe_bias_act_fwd / _fwd2 (ops_epilogue.hip), bit for bit, written to y and (optionally) to the same channels of a second

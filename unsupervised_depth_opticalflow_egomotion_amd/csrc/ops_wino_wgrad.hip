@@ -18,16 +18,13 @@
 // Bound: MFMA (2.25 x 157 TFLOP/s effective at 100 % of the fp32 matrix pipe).
 #include "dfe_internal.h"
 #include "dfe_device.h"
+#include "dfe_mfma_stage.h"
 #include "dfe_wgrad_sum.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
 
 namespace dfe {
-
-typedef float wg_f32x4 __attribute__((ext_vector_type(4)));
-typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
-struct __attribute__((packed, aligned(4))) WgQuadU { float a, b, c, d; };     // dword-aligned 16 bytes
 
 // TWC = tiles per chunk (a multiple of 4: TWC / 4 steps per barrier): 8 or 12
 template <int MH, int NH, int WM, int WN, int TWC>
@@ -76,7 +73,7 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
   const int gl0 = Cfg::CIB * WG_XCS + gc_ * WG_GCS + gr_ * WG_GP + 4 * gq_;
   const int xg0 = (cib0 + xc_) * HW + (xr_ - PP) * W + (4 * xq_ - CS);
   const int gg0 = (cob0 + gc_) * gHW + gr_ * gW + 4 * gq_;
-  wg_f32x4 xr[Cfg::NXT], gr[Cfg::NGT];
+  f32x4 xr[Cfg::NXT], gr[Cfg::NGT];
   int cx = c_beg % cpr, ty = (c_beg / cpr) % TH, img = c_beg / cpr / TH;       // the chunk load_chunk stages next
   auto load_chunk = [&]() {
     const long xb = img * xbs + static_cast<long>(2 * ty) * W + 2 * TWC * cx;
@@ -90,12 +87,12 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
       for (int k = 0; k < Cfg::NXT; ++k) {
         const float* p = p0 + static_cast<long>(8 * k) * HW;
         const bool cok = xc_ + 8 * k < Cfg::CIB && cib0 + xc_ + 8 * k < C;
-        wg_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
         {            // straight-line: one 16-byte load from a safe address, zero unless the slot lies inside.  The safe address is the
                      // workspace's first 16 bytes (at least 9 floats, whatever they hold: the value is dropped) -- x or gy may be
                      // views of fewer than 4 floats (a 1x1 gy of one channel)
-          const WgQuadU u = *reinterpret_cast<const WgQuadU*>(full && cok ? p : part);
-          if (full && cok) v = wg_f32x4{u.a, u.b, u.c, u.d};
+          const QuadU u = *reinterpret_cast<const QuadU*>(full && cok ? p : part);
+          if (full && cok) v = f32x4{u.a, u.b, u.c, u.d};
         }
         if (!full && some && cok) {      // a slot that straddles the image's edge: element by element
 #pragma unroll
@@ -114,10 +111,10 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
       for (int k = 0; k < Cfg::NGT; ++k) {
         const float* p = p0 + static_cast<long>(Cfg::GCH * k) * gHW;
         const bool cok = gc_ + Cfg::GCH * k < Cfg::COB && cob0 + gc_ + Cfg::GCH * k < K;
-        wg_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
         {
-          const WgQuadU u = *reinterpret_cast<const WgQuadU*>(full && cok ? p : part);
-          if (full && cok) v = wg_f32x4{u.a, u.b, u.c, u.d};
+          const QuadU u = *reinterpret_cast<const QuadU*>(full && cok ? p : part);
+          if (full && cok) v = f32x4{u.a, u.b, u.c, u.d};
         }
         if (!full && some && cok) {
 #pragma unroll
@@ -133,22 +130,22 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
     if (xq_ < Cfg::XU) {
 #pragma unroll
       for (int k = 0; k < Cfg::NXT; ++k)
-        if (xc_ + 8 * k < Cfg::CIB) *reinterpret_cast<wg_f32x4*>(buf + xl0 + 8 * k * WG_XCS) = xr[k];
+        if (xc_ + 8 * k < Cfg::CIB) *reinterpret_cast<f32x4*>(buf + xl0 + 8 * k * WG_XCS) = xr[k];
     }
     if (gq_ < Cfg::GU) {
 #pragma unroll
       for (int k = 0; k < Cfg::NGT; ++k)
-        if (gc_ + Cfg::GCH * k < Cfg::COB) *reinterpret_cast<wg_f32x4*>(buf + gl0 + Cfg::GCH * k * WG_GCS) = gr[k];
+        if (gc_ + Cfg::GCH * k < Cfg::COB) *reinterpret_cast<f32x4*>(buf + gl0 + Cfg::GCH * k * WG_GCS) = gr[k];
     }
   };
 
-  wg_f32x4 acc[MH][NH][16];
+  f32x4 acc[MH][NH][16];
 #pragma unroll
   for (int a = 0; a < MH; ++a)
 #pragma unroll
     for (int b = 0; b < NH; ++b)
 #pragma unroll
-      for (int s = 0; s < 16; ++s) acc[a][b][s] = wg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      for (int s = 0; s < 16; ++s) acc[a][b][s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
   // consumer addresses: input channel (wn NH + nh) 16 + i, output channel (wm MH + mh) 16 + i, tile 4 ks + kq
   const int xoff = (wn * NH * 16 + i) * WG_XCS + 2 * kq + S;
@@ -159,7 +156,7 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
 #pragma unroll
     for (int mh = 0; mh < MH; ++mh) {
       const float* p = buf + goff + mh * 16 * WG_GCS + 8 * ks;
-      const wg_f32x2 r0 = *reinterpret_cast<const wg_f32x2*>(p), r1 = *reinterpret_cast<const wg_f32x2*>(p + WG_GP);
+      const f32x2 r0 = *reinterpret_cast<const f32x2*>(p), r1 = *reinterpret_cast<const f32x2*>(p + WG_GP);
       // dM' = A' dY A'^T with A' = diag(1, 1, 1, -1) A (no negations here; the signs are put back in the epilogue)
       const float a0[4] = {r0[0], r0[0] + r1[0], r0[0] - r1[0], r1[0]};
       const float a1[4] = {r0[1], r0[1] + r1[1], r0[1] - r1[1], r1[1]};
@@ -175,11 +172,11 @@ k_wino_wgrad2(const float* __restrict__ x, long xbs, const float* __restrict__ g
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (PP == 1) {         // patch column 0 at an odd LDS column: three aligned pairs (dword reads would meet 4 to a bank)
-          const wg_f32x2 lo = *reinterpret_cast<const wg_f32x2*>(p + r * WG_XP - 1), mid = *reinterpret_cast<const wg_f32x2*>(p + r * WG_XP + 1),
-                         hi = *reinterpret_cast<const wg_f32x2*>(p + r * WG_XP + 3);
+          const f32x2 lo = *reinterpret_cast<const f32x2*>(p + r * WG_XP - 1), mid = *reinterpret_cast<const f32x2*>(p + r * WG_XP + 1),
+                         hi = *reinterpret_cast<const f32x2*>(p + r * WG_XP + 3);
           d[4 * r] = lo[1]; d[4 * r + 1] = mid[0]; d[4 * r + 2] = mid[1]; d[4 * r + 3] = hi[0];
         } else {
-          const wg_f32x2 lo = *reinterpret_cast<const wg_f32x2*>(p + r * WG_XP), hi = *reinterpret_cast<const wg_f32x2*>(p + r * WG_XP + 2);
+          const f32x2 lo = *reinterpret_cast<const f32x2*>(p + r * WG_XP), hi = *reinterpret_cast<const f32x2*>(p + r * WG_XP + 2);
           d[4 * r] = lo[0]; d[4 * r + 1] = lo[1]; d[4 * r + 2] = hi[0]; d[4 * r + 3] = hi[1];
         }
       }
@@ -293,12 +290,7 @@ bool wg_plan(int B, int Ci, int Co, int H, int W, int P, WgPlan* pl) {
   if (nch >= (1L << 30)) return false;
   p.nchunks = static_cast<int>(nch);
   p.ncot = (Co + 32 * p.mh - 1) / (32 * p.mh); p.ncit = (Ci + 32 * p.nh - 1) / (32 * p.nh);
-  const int tgt1 = g_wg_tune[1], tgt2 = g_wg_tune[2];
-  const long ntb = static_cast<long>(p.ncot) * p.ncit;
-  long S = ((p.mh * p.nh >= 2 ? tgt2 : tgt1) + ntb / 2) / ntb;
-  S = std::max(1L, std::min<long>(S, p.nchunks));
-  p.cps = static_cast<int>((p.nchunks + S - 1) / S);
-  p.S = (p.nchunks + p.cps - 1) / p.cps;
+  p.S = split_round(g_wg_tune[p.mh * p.nh >= 2 ? 2 : 1], static_cast<long>(p.ncot) * p.ncit, p.nchunks, &p.cps);
   *pl = p;
   return true;
 }
@@ -326,11 +318,8 @@ static void wg_launch(const WgPlan& p, const float* x, long xbs, const float* gy
   typedef WgCfg<MH, NH, 2, 2, TWC> Cfg;
   const int ntb = p.ncot * p.ncit;
   const size_t lds_bytes = sizeof(float) * 2 * Cfg::BUF;
-  auto kern = k_wino_wgrad2<MH, NH, 2, 2, TWC, PP>;
-  static bool attr_set = false;      // > 64 KB of dynamic LDS needs the opt-in attribute once per kernel
-  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)); attr_set = true; }
-  kern<<<static_cast<unsigned>(ntb) * p.S, 256, lds_bytes, st>>>(x, xbs, gy, gbs, ws, Ci, Co, W, H * W, H, W, p.Ho, p.Wo, p.Wo, p.Ho * p.Wo, p.TH,
-                                                                   p.cpr, p.TWn, p.nchunks, p.cps, p.ncit, ntb);
+  launch_dyn_lds<k_wino_wgrad2<MH, NH, 2, 2, TWC, PP>>(static_cast<unsigned>(ntb) * p.S, lds_bytes, static_cast<int>(lds_bytes), st, x, xbs, gy, gbs, ws,
+                                                      Ci, Co, W, H * W, H, W, p.Ho, p.Wo, p.Wo, p.Ho * p.Wo, p.TH, p.cpr, p.TWn, p.nchunks, p.cps, p.ncit, ntb);
 }
 
 extern "C" int dfe_wino_wgrad3x3(const float* x, long x_batch_stride, const float* gy, long gy_batch_stride, float* gweight, float* ws, int B,
@@ -340,10 +329,8 @@ extern "C" int dfe_wino_wgrad3x3(const float* x, long x_batch_stride, const floa
   if (P < 0 || P > 1) return DFE_ERR_UNSUPPORTED;
   WgPlan p;
   if (!wg_plan(B, Ci, Co, H, W, P, &p)) return DFE_ERR_DIMS;
-  const long gplane = static_cast<long>(p.Ho) * p.Wo;
-  if (x_batch_stride < static_cast<long>(Ci) * H * W || gy_batch_stride < Co * gplane) return DFE_ERR_DIMS;
-  // 32-bit offsets inside one sample
-  if (static_cast<long>(Ci) * H * W >= (1L << 30) || Co * gplane >= (1L << 30) || static_cast<long>(Co) * Ci * 9 >= (1L << 30)) return DFE_ERR_DIMS;
+  const long n = static_cast<long>(Co) * Ci * 9;
+  if (!sample_ok(x_batch_stride, static_cast<long>(Ci) * H * W) || !sample_ok(gy_batch_stride, static_cast<long>(Co) * p.Ho * p.Wo) || n >= (1L << 30)) return DFE_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define WG_GO(MHV, NHV, TWV) do { \
     if (P == 1) wg_launch<MHV, NHV, TWV, 1>(p, x, x_batch_stride, gy, gy_batch_stride, ws, Ci, Co, H, W, st); \
@@ -355,9 +342,7 @@ extern "C" int dfe_wino_wgrad3x3(const float* x, long x_batch_stride, const floa
   else WG_GO(1, 1, 8);
 #undef WG_GO
   DFE_LAUNCH_CHECK();
-  const long n = static_cast<long>(Co) * Ci * 9;
-  if (p.S > 64) k_wgrad_sum<32><<<static_cast<unsigned>((n + 31) / 32), 1024, 0, st>>>(ws, gweight, p.S, n);
-  else k_wgrad_sum<8><<<static_cast<unsigned>((n + 31) / 32), 256, 0, st>>>(ws, gweight, p.S, n);
+  launch_wgrad_sum(ws, gweight, p.S, n, st);
   DFE_LAUNCH_CHECK();
   return DFE_OK;
 }
