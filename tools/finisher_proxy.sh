@@ -1,14 +1,15 @@
 #!/bin/bash
 # Upper bound of what removing the small finishing launches could buy, measured BEFORE building anything:
-# a copy of csrc/ under /tmp whose launchers skip them (DFE_PROXY_SKIP=1: k_wino_sum, k_planeconv_finish, k_bias_grad_final(_multi),
-# k_glue_bias_final, k_head_final; DFE_PROXY_SKIP_BIG=1: the weight gradients' split sums) -- results are garbage, timing is valid
+# a copy of csrc/ under /tmp whose launchers skip them (DFE_PROXY_SKIP=1: k_wino_sum, k_planeconv_finish, k_bias_grad_final (the
+# epilogue's and the decoder glue's, one launch site in launch_bias_final) and k_bias_grad_final_multi, k_head_final;
+# DFE_PROXY_SKIP_BIG=1: the weight gradients' split sums) -- results are garbage, timing is valid
 # (Adam bounds every update by lr).  Alternating runs on one box.   usage (on the GPU box): bash tools/finisher_proxy.sh
 R=$GRAFT_REPO_ROOT; export TMPDIR=/tmp
 rm -rf /tmp/pf; mkdir -p /tmp/pf/pkg /tmp/pf/include
 cp -r $R/unsupervised_depth_opticalflow_egomotion_amd/csrc /tmp/pf/pkg/csrc; cp $R/include/dfe_hip.h /tmp/pf/include/; rm -f /tmp/pf/pkg/csrc/*.o
 python3 - <<'PY'
 import re, glob
-small = [r'k_glue_bias_final<<<', r'k_head_final<\d, \w+><<<', r'k_bias_grad_final<<<', r'k_bias_grad_final_multi<<<', r'k_planeconv_finish<<<', r'k_wino_sum<<<']
+small = [r'k_head_final<\d, \w+><<<', r'k_bias_grad_final<<<', r'k_bias_grad_final_multi<<<', r'k_planeconv_finish<<<', r'k_wino_sum<<<']
 for f in glob.glob('/tmp/pf/pkg/csrc/*.hip'):
     s = open(f).read(); o = s
     for p in small:

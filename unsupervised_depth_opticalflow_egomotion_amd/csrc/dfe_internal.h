@@ -35,4 +35,8 @@ int launch_corr_fwd(const float* f1, const float* f2, float* out, long obs, floa
                     hipStream_t st);
 int launch_corr_bwd(const float* f1, const float* f2, const float* gout, long gbs, const float* add1, long abs1, float* g1,
                     float* g2, unsigned* amax2, int B, int C, int H, int W, hipStream_t st);
+
+// ops_epilogue.hip: the bias-gradient finisher of the epilogue and decoder-glue passes, in its one fixed order:
+// gbias[c] = sum over b < B, k < n of part[(b*C + c)*n + k] (n partials per plane, as many as the producing launch had blocks)
+int launch_bias_final(const float* part, float* gbias, int B, int C, int n, hipStream_t st);
 }  // namespace dfe

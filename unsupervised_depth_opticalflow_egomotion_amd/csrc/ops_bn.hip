@@ -15,13 +15,15 @@
 // a fixed order (no atomics; reproducible).  Bound: HBM.
 #include "dfe_internal.h"
 #include "dfe_device.h"
+#include "dfe_chunk.h"
 #include <hip/hip_runtime.h>
 
 namespace dfe {
 
-constexpr int BN_BLOCK = 256;
-constexpr int BN_PER_THREAD = 8;
-constexpr int BN_CHUNK = BN_BLOCK * BN_PER_THREAD;
+// the (nchunk, C, N) kernels walk their planes with load8 / store8 of dfe_chunk.h
+constexpr int BN_BLOCK = CHUNK_BLOCK;
+constexpr int BN_PER_THREAD = CHUNK_PER_THREAD;
+constexpr int BN_CHUNK = CHUNK_ELEMS;
 
 // sum over the block, returned to every thread (fixed order); smem: 4 * (BN_BLOCK / 64) floats
 __device__ __forceinline__ float block_allsum(float v, float* smem) {
@@ -34,44 +36,6 @@ __device__ __forceinline__ float block_allsum(float v, float* smem) {
   for (int k = 0; k < 4 * (BN_BLOCK / 64); ++k) s += smem[k];
   __syncthreads();
   return s;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void load8(const float* __restrict__ p, int base, int HW, float (&v)[BN_PER_THREAD], bool (&ok)[BN_PER_THREAD]) {
-  if (VEC) {
-#pragma unroll
-    for (int k = 0; k < BN_PER_THREAD / 4; ++k) {
-      const int e = base + (k * BN_BLOCK + threadIdx.x) * 4;
-      const bool in = e < HW;
-      float4 q = in ? *reinterpret_cast<const float4*>(p + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-      v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
-      ok[4 * k] = ok[4 * k + 1] = ok[4 * k + 2] = ok[4 * k + 3] = in;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < BN_PER_THREAD; ++k) {
-      const int e = base + k * BN_BLOCK + threadIdx.x;
-      ok[k] = e < HW;
-      v[k] = ok[k] ? p[e] : 0.0f;
-    }
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store8(float* __restrict__ p, int base, int HW, const float (&v)[BN_PER_THREAD]) {
-  if (VEC) {
-#pragma unroll
-    for (int k = 0; k < BN_PER_THREAD / 4; ++k) {
-      const int e = base + (k * BN_BLOCK + threadIdx.x) * 4;
-      if (e < HW) *reinterpret_cast<float4*>(p + e) = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < BN_PER_THREAD; ++k) {
-      const int e = base + k * BN_BLOCK + threadIdx.x;
-      if (e < HW) p[e] = v[k];
-    }
-  }
 }
 
 // ---- forward pass 1: per block (count, mean, M2) of its chunk of plane (n, c).  grid: (nchunk, C, N)

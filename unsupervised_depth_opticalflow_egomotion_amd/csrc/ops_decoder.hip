@@ -12,7 +12,6 @@
 // Arithmetic: elu(x) = x > 0 ? x : exp(x) - 1; elu'(x) = x > 0 ? 1 : exp(x) (ATen: expm1 / exp);
 // bilinear x2 with align_corners=False: src = max(0.5*(dst+0.5)-0.5, 0), (v0*l0 + v1*l1) horizontally first.
 #include "dfe_internal.h"
-#include "dfe_mfma_stage.h"
 #include "dfe_device.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -49,150 +48,110 @@ __device__ __forceinline__ float pad_adjoint(const float* __restrict__ gp, int y
   return s;
 }
 
-// ---------------------------------------------------------------- p = pad(elu(x))
-// grid: x over the elements of one padded plane, y = c, z = b
-__global__ void __launch_bounds__(256) k_elu_pad_fwd(const float* __restrict__ x, const float* __restrict__ bias,
-                                                     float* __restrict__ out, int C, int H, int W, int elu) {
-  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= static_cast<unsigned>((H + 2) * (W + 2))) return;
-  const int oy = e / static_cast<unsigned>(W + 2), ox = e - oy * (W + 2);
-  const long pl = plane_id();
-  const float v = x[(pl * H + reflect1(oy - 1, H)) * W + reflect1(ox - 1, W)] + (bias ? bias[plane_id() % C] : 0.0f);
-  out[(pl * (H + 2) + oy) * (W + 2) + ox] = elu ? elu1(v) : v;
+// V consecutive floats of a row.  VecA<V>: at the vector's natural alignment of 4 V bytes (x, gx, gskip, out);
+// VecU<V>: dword-aligned (the padded plane's interior sits one element to the right of the plane's: an odd offset)
+template <int V> struct __attribute__((aligned(4 * V))) VecA { float v[V]; };
+template <int V> struct __attribute__((packed, aligned(4))) VecU { float v[V]; };
+struct __attribute__((aligned(8))) AF2 { float a, b; };      // the pair, by name, of the up2 kernels below
+
+// pad_adjoint for the V columns ix ... ix + V - 1 (ix a multiple of V) of row iy.  V = 1 goes through pad_adjoint for every
+// element, which starts its sum from 0.0f: a -0.0 of the padded gradient comes out as +0.0.  V = 2 / 4 copy ONE dword-aligned
+// 8- / 16-byte load wherever nothing is mirrored onto the vector -- a -0.0 stays -0.0, each width keeps its own answer --
+// and collect the vectors that contain column 1 or W-2 and the rows 1 and H-2 element by element.
+template <int V>
+__device__ __forceinline__ void pad_adjoint_vec(const float* __restrict__ g, int iy, int ix, int H, int W, float (&r)[V]) {
+  if (V > 1 && iy != 1 && iy != H - 2 && ix != 0 && ix != W - V) {
+    const VecU<V> q = *reinterpret_cast<const VecU<V>*>(g + static_cast<long>(iy + 1) * (W + 2) + ix + 1);
+#pragma unroll
+    for (int k = 0; k < V; ++k) r[k] = q.v[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; ++k) r[k] = pad_adjoint(g, iy, ix + k, H, W);
+  }
 }
 
+// a thread's V values as its share of the block's bias-gradient partial: g0, g0 + g1, (g0 + g1) + (g2 + g3)
+template <int V>
+__device__ __forceinline__ float vec_sum(const float* g) {
+  if constexpr (V == 1) return g[0];
+  else return vec_sum<V / 2>(g) + vec_sum<V / 2>(g + V / 2);
+}
+
+// ---------------------------------------------------------------- p = pad(elu(x))
+// V elements per thread.  These passes are pure streaming, so halving the instruction count per byte is what moves them
+// towards the HBM roofline: V = 2 (even W) takes one 8-byte store (and, backward, one 8-byte load per stream in the
+// interior), V = 4 (W % 4 == 0; backward only) 16-byte loads / stores of x and gx and one 16-byte load of the padded gradient.  Round 3: the pair
+// kernels move 8 bytes per lane and instruction and stop at 3 TB/s on the decoder's large planes.
+// grid: x over the (H+2) * (W+2)/V vectors of one padded plane, y = c, z = b
+template <int V>
+__global__ void __launch_bounds__(256) k_elu_pad_fwd(const float* __restrict__ x, const float* __restrict__ bias,
+                                                     float* __restrict__ out, int C, int H, int W, int elu) {
+  const int Wv = (W + 2) / V;
+  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= static_cast<unsigned>((H + 2) * Wv)) return;
+  const int oy = e / static_cast<unsigned>(Wv), ox = V * (e - oy * Wv);
+  const long pl = plane_id();
+  const float bv = bias ? bias[plane_id() % C] : 0.0f;
+  const float* row = x + (pl * H + reflect1(oy - 1, H)) * W;
+  // V dword loads at selected columns (the source of an interior vector sits at an odd offset, ox - 1).  One 8-byte load
+  // under an interior branch was tried and lost 3 % (24.9 -> 25.65 us per launch in the training step): the loads then wait
+  // inside the divergent region (profiles/glue_epilogue_refactor.txt, D1)
+  const bool inner = V > 1 && ox >= V && ox <= W - V;      // no mirrored column among the V
+  VecA<V> o;
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    const float t = row[inner ? ox - 1 + k : reflect1(ox - 1 + k, W)] + bv;
+    o.v[k] = elu ? elu1(t) : t;
+  }
+  *reinterpret_cast<VecA<V>*>(out + (pl * (H + 2) + oy) * (W + 2) + ox) = o;
+}
+
+// grid: x over the H * W/V vectors of one plane, y = c, z = b
+template <int V>
 __global__ void __launch_bounds__(256) k_elu_pad_bwd(const float* __restrict__ x, const float* __restrict__ bias,
                                                      const float* __restrict__ gp, float* __restrict__ gx,
                                                      float* __restrict__ part, int C, int H, int W, int elu) {
   __shared__ float red[4 * 4];
+  const int Wv = W / V;
   const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
   float acc[1] = {0.0f};
-  if (e < static_cast<unsigned>(H * W)) {
-    const int iy = e / static_cast<unsigned>(W), ix = e - iy * W;
+  if (e < static_cast<unsigned>(H * Wv)) {
+    const int iy = e / static_cast<unsigned>(Wv), ix = V * (e - iy * Wv);
     const long pl = plane_id();
-    float g = pad_adjoint(gp + pl * (H + 2) * (W + 2), iy, ix, H, W);
-    const long o = (pl * H + iy) * W + ix;
-    if (elu) g *= elu1_grad(x[o] + (bias ? bias[plane_id() % C] : 0.0f));
-    gx[o] = g;
-    acc[0] = g;
-  }
-  if (part) block_sum<1>(acc, red, part + static_cast<long>(plane_id()) * gridDim.x + blockIdx.x);
-}
-
-// ---- two elements per thread (even W): these passes are pure streaming, so halving the instruction count per byte
-// is what moves them towards the HBM roofline.  Interior pairs take one 8-byte load / store per stream (the padded
-// plane's pair sits at an odd offset: a dword-aligned 8-byte load); the pairs touching a mirrored column or row
-// take the scalar path.  grid: x over H * W/2 (bwd) or (H+2) * (W+2)/2 (fwd) pairs, y = c, z = b.
-struct __attribute__((aligned(8))) AF2 { float a, b; };
-
-__global__ void __launch_bounds__(256) k_elu_pad_fwd_pair(const float* __restrict__ x, const float* __restrict__ bias,
-                                                          float* __restrict__ out, int C, int H, int W, int elu) {
-  const int Wh = (W + 2) / 2;
-  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= static_cast<unsigned>((H + 2) * Wh)) return;
-  const int oy = e / static_cast<unsigned>(Wh), ox = 2 * (e - oy * Wh);
-  const long pl = plane_id();
-  const float bv = bias ? bias[plane_id() % C] : 0.0f;
-  const float* row = x + (pl * H + reflect1(oy - 1, H)) * W;
-  float v0, v1;
-  if (ox >= 2 && ox <= W - 2) { const PairF q = *reinterpret_cast<const PairF*>(row + ox - 1); v0 = q.a; v1 = q.b; }
-  else { v0 = row[reflect1(ox - 1, W)]; v1 = row[reflect1(ox, W)]; }
-  v0 += bv; v1 += bv;
-  AF2 o;
-  o.a = elu ? elu1(v0) : v0; o.b = elu ? elu1(v1) : v1;
-  *reinterpret_cast<AF2*>(out + (pl * (H + 2) + oy) * (W + 2) + ox) = o;
-}
-
-__global__ void __launch_bounds__(256) k_elu_pad_bwd_pair(const float* __restrict__ x, const float* __restrict__ bias,
-                                                          const float* __restrict__ gp, float* __restrict__ gx,
-                                                          float* __restrict__ part, int C, int H, int W, int elu) {
-  __shared__ float red[4 * 4];
-  const int Wh = W / 2;
-  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-  float acc[1] = {0.0f};
-  if (e < static_cast<unsigned>(H * Wh)) {
-    const int iy = e / static_cast<unsigned>(Wh), ix = 2 * (e - iy * Wh);
-    const long pl = plane_id();
-    const float* g = gp + pl * (H + 2) * (W + 2);
-    float g0, g1;
-    if (iy != 1 && iy != H - 2 && ix != 0 && ix != W - 2) {
-      const PairF q = *reinterpret_cast<const PairF*>(g + static_cast<long>(iy + 1) * (W + 2) + ix + 1);
-      g0 = q.a; g1 = q.b;
-    } else { g0 = pad_adjoint(g, iy, ix, H, W); g1 = pad_adjoint(g, iy, ix + 1, H, W); }
+    float g[V];
+    pad_adjoint_vec<V>(gp + pl * (H + 2) * (W + 2), iy, ix, H, W, g);
     const long o = (pl * H + iy) * W + ix;
     if (elu) {
-      const AF2 xv = *reinterpret_cast<const AF2*>(x + o);
+      const VecA<V> xv = *reinterpret_cast<const VecA<V>*>(x + o);
       const float bv = bias ? bias[plane_id() % C] : 0.0f;
-      g0 *= elu1_grad(xv.a + bv); g1 *= elu1_grad(xv.b + bv);
+#pragma unroll
+      for (int k = 0; k < V; ++k) g[k] *= elu1_grad(xv.v[k] + bv);
     }
-    AF2 r; r.a = g0; r.b = g1;
-    *reinterpret_cast<AF2*>(gx + o) = r;
-    acc[0] = g0 + g1;
+    VecA<V> r;
+#pragma unroll
+    for (int k = 0; k < V; ++k) r.v[k] = g[k];
+    *reinterpret_cast<VecA<V>*>(gx + o) = r;
+    acc[0] = vec_sum<V>(g);
   }
   if (part) block_sum<1>(acc, red, part + static_cast<long>(plane_id()) * gridDim.x + blockIdx.x);
 }
 
-// ---- four elements per thread (W % 4 == 0): 16-byte loads / stores of x and gx, and ONE dword-aligned 16-byte load
-// of the padded gradient (it sits one element to the right: offset +1); the quads that contain column 1 or W-2 and
-// the rows 1 and H-2 collect the mirrored padding entries element by element.  Round 3: the pair kernels above move
-// 8 bytes per lane and instruction and stop at 3 TB/s on the decoder's large planes.
-__device__ __forceinline__ float4 pad_adjoint_quad(const float* __restrict__ g, int iy, int ix, int H, int W) {
-  if (iy != 1 && iy != H - 2 && ix != 0 && ix != W - 4) {
-    const QuadU q = *reinterpret_cast<const QuadU*>(g + static_cast<long>(iy + 1) * (W + 2) + ix + 1);
-    return make_float4(q.a, q.b, q.c, q.d);
-  }
-  return make_float4(pad_adjoint(g, iy, ix, H, W), pad_adjoint(g, iy, ix + 1, H, W), pad_adjoint(g, iy, ix + 2, H, W),
-                     pad_adjoint(g, iy, ix + 3, H, W));
-}
-
-__global__ void __launch_bounds__(256) k_elu_pad_bwd_quad(const float* __restrict__ x, const float* __restrict__ bias,
-                                                          const float* __restrict__ gp, float* __restrict__ gx,
-                                                          float* __restrict__ part, int C, int H, int W, int elu) {
-  __shared__ float red[4 * 4];
-  const int Wq = W / 4;
+// gradient wrt the skip of pad(cat(up2(elu(x)), skip)) below: adjoint of the pad only.
+// grid: x over the H * W/V vectors of one plane, y = c, z = b
+template <int V>
+__global__ void __launch_bounds__(256) k_cat_pad_bwd_skip(const float* __restrict__ gp, float* __restrict__ gskip,
+                                                          int C1, int C2, int H, int W) {
+  const int Wv = W / V;
   const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-  float acc[1] = {0.0f};
-  if (e < static_cast<unsigned>(H * Wq)) {
-    const int iy = e / static_cast<unsigned>(Wq), ix = 4 * (e - iy * Wq);
-    const long pl = plane_id();
-    float4 g = pad_adjoint_quad(gp + pl * (H + 2) * (W + 2), iy, ix, H, W);
-    const long o = (pl * H + iy) * W + ix;
-    if (elu) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + o);
-      const float bv = bias ? bias[plane_id() % C] : 0.0f;
-      g.x *= elu1_grad(xv.x + bv); g.y *= elu1_grad(xv.y + bv); g.z *= elu1_grad(xv.z + bv); g.w *= elu1_grad(xv.w + bv);
-    }
-    *reinterpret_cast<float4*>(gx + o) = g;
-    acc[0] = (g.x + g.y) + (g.z + g.w);
-  }
-  if (part) block_sum<1>(acc, red, part + static_cast<long>(plane_id()) * gridDim.x + blockIdx.x);
-}
-
-__global__ void __launch_bounds__(256) k_cat_pad_bwd_skip_quad(const float* __restrict__ gp, float* __restrict__ gskip,
-                                                               int C1, int C2, int H, int W) {
-  const int Wq = W / 4;
-  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= static_cast<unsigned>(H * Wq)) return;
-  const int iy = e / static_cast<unsigned>(Wq), ix = 4 * (e - iy * Wq);
+  if (e >= static_cast<unsigned>(H * Wv)) return;
+  const int iy = e / static_cast<unsigned>(Wv), ix = V * (e - iy * Wv);
   const int b = plane_id() / C2, c = plane_id() - b * C2;
-  const float* g = gp + (static_cast<long>(b) * (C1 + C2) + C1 + c) * (H + 2) * (W + 2);
-  *reinterpret_cast<float4*>(gskip + (static_cast<long>(plane_id()) * H + iy) * W + ix) = pad_adjoint_quad(g, iy, ix, H, W);
-}
-
-__global__ void __launch_bounds__(256) k_cat_pad_bwd_skip_pair(const float* __restrict__ gp, float* __restrict__ gskip,
-                                                               int C1, int C2, int H, int W) {
-  const int Wh = W / 2;
-  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= static_cast<unsigned>(H * Wh)) return;
-  const int iy = e / static_cast<unsigned>(Wh), ix = 2 * (e - iy * Wh);
-  const int b = plane_id() / C2, c = plane_id() - b * C2;
-  const float* g = gp + (static_cast<long>(b) * (C1 + C2) + C1 + c) * (H + 2) * (W + 2);
-  AF2 r;
-  if (iy != 1 && iy != H - 2 && ix != 0 && ix != W - 2) {
-    const PairF q = *reinterpret_cast<const PairF*>(g + static_cast<long>(iy + 1) * (W + 2) + ix + 1);
-    r.a = q.a; r.b = q.b;
-  } else { r.a = pad_adjoint(g, iy, ix, H, W); r.b = pad_adjoint(g, iy, ix + 1, H, W); }
-  *reinterpret_cast<AF2*>(gskip + (static_cast<long>(plane_id()) * H + iy) * W + ix) = r;
+  float g[V];
+  pad_adjoint_vec<V>(gp + (static_cast<long>(b) * (C1 + C2) + C1 + c) * (H + 2) * (W + 2), iy, ix, H, W, g);
+  VecA<V> r;
+#pragma unroll
+  for (int k = 0; k < V; ++k) r.v[k] = g[k];
+  *reinterpret_cast<VecA<V>*>(gskip + (static_cast<long>(plane_id()) * H + iy) * W + ix) = r;
 }
 
 // ---------------------------------------------------------------- p = pad(cat(up2(elu(x)), skip))
@@ -274,6 +233,19 @@ __global__ void __launch_bounds__(256) k_elu_up2_cat_pad_fwd_pair(const float* _
   *reinterpret_cast<AF2*>(out + (static_cast<long>(plane_id()) * (H + 2) + oy) * (W + 2) + ox) = o;
 }
 
+// weights with which the four full-res outputs 2i - 1 ... 2i + 2 of an axis (low-res length n_lo) tap low-res index i: the
+// clamped taps near the plane's ends, zero for an output outside the plane
+__device__ __forceinline__ void up2_adjoint_weights(int i, int n_lo, float (&wgt)[4]) {
+  const int n_hi = 2 * n_lo;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int a0, a1; float l0, l1;
+    const int y = 2 * i - 1 + k;
+    up2_tap(min(max(y, 0), n_hi - 1), n_lo, a0, a1, l0, l1);
+    wgt[k] = (y >= 0 && y < n_hi) ? ((a0 == i ? l0 : 0.0f) + (a1 == i ? l1 : 0.0f)) : 0.0f;
+  }
+}
+
 // gradient wrt x: thread per low-res element; the <= 4x4 full-res outputs whose taps touch it, each through the
 // adjoint of the reflection pad.  grid: x over the low-res plane, y = c, z = b
 __global__ void __launch_bounds__(256) k_elu_up2_cat_pad_bwd_x(const float* __restrict__ x, const float* __restrict__ bias,
@@ -301,16 +273,8 @@ __global__ void __launch_bounds__(256) k_elu_up2_cat_pad_bwd_x(const float* __re
     }
   } else {
   float wy[4], wx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int a0, a1; float l0, l1;
-    const int y = 2 * i - 1 + k;
-    up2_tap(min(max(y, 0), H - 1), h, a0, a1, l0, l1);
-    wy[k] = (y >= 0 && y < H) ? ((a0 == i ? l0 : 0.0f) + (a1 == i ? l1 : 0.0f)) : 0.0f;
-    const int xq = 2 * j - 1 + k;
-    up2_tap(min(max(xq, 0), W - 1), w, a0, a1, l0, l1);
-    wx[k] = (xq >= 0 && xq < W) ? ((a0 == j ? l0 : 0.0f) + (a1 == j ? l1 : 0.0f)) : 0.0f;
-  }
+  up2_adjoint_weights(i, h, wy);
+  up2_adjoint_weights(j, w, wx);
 #pragma unroll
   for (int ky = 0; ky < 4; ++ky) {
     if (wy[ky] == 0.0f) continue;
@@ -338,17 +302,6 @@ __global__ void __launch_bounds__(256) k_elu_up2_cat_pad_bwd_x(const float* __re
 // clamped tap weights; same products and the same summation order per element as the two kernels above -> identical gx.
 // grid: x = tiles_x * tiles_y, y = c, z = b; 256 threads = (256 / TW) row groups x TW columns.
 constexpr int UT_H = 16;
-
-__device__ __forceinline__ void up2_adjoint_weights(int i, int n_lo, float (&wgt)[4]) {
-  const int n_hi = 2 * n_lo;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int a0, a1; float l0, l1;
-    const int y = 2 * i - 1 + k;
-    up2_tap(min(max(y, 0), n_hi - 1), n_lo, a0, a1, l0, l1);
-    wgt[k] = (y >= 0 && y < n_hi) ? ((a0 == i ? l0 : 0.0f) + (a1 == i ? l1 : 0.0f)) : 0.0f;
-  }
-}
 
 template <int TW>
 __global__ void __launch_bounds__(256) k_elu_up2_cat_pad_bwd_x_tile(const float* __restrict__ x, const float* __restrict__ bias,
@@ -448,34 +401,6 @@ __global__ void __launch_bounds__(256) k_elu_up2_cat_pad_bwd_x_tile(const float*
   if (part) block_sum<1>(acc, red, part + static_cast<long>(plane_id()) * gridDim.x + blockIdx.x);
 }
 
-// gbias[c] = sum over b, blocks of part[(b*C + c)*nblk + k] in a fixed order; one wave per channel
-__global__ void __launch_bounds__(64) k_glue_bias_final(const float* __restrict__ part, float* __restrict__ gbias,
-                                                        int B, int C, int nblk) {
-  const int c = blockIdx.x, lane = threadIdx.x;
-  float s = 0.0f;
-  for (int b = 0; b < B; ++b) {
-    const float* p = part + (static_cast<long>(b) * C + c) * nblk;
-    for (int k = lane; k < nblk; k += 64) s += p[k];
-  }
-  s = dpp_add<0xB1>(s); s = dpp_add<0x4E>(s); s = dpp_add<0x141>(s); s = dpp_add<0x140>(s);
-  const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 0));
-  const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 16));
-  const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 32));
-  const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 48));
-  if (lane == 0) gbias[c] = (r0 + r1) + (r2 + r3);
-}
-
-// gradient wrt skip: adjoint of the pad only.  grid: x over the plane, y = c, z = b
-__global__ void __launch_bounds__(256) k_cat_pad_bwd_skip(const float* __restrict__ gp, float* __restrict__ gskip,
-                                                          int C1, int C2, int H, int W) {
-  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= static_cast<unsigned>(H * W)) return;
-  const int iy = e / static_cast<unsigned>(W), ix = e - iy * W;
-  const int b = plane_id() / C2, c = plane_id() - b * C2;
-  const float* g = gp + (static_cast<long>(b) * (C1 + C2) + C1 + c) * (H + 2) * (W + 2);
-  gskip[(static_cast<long>(plane_id()) * H + iy) * W + ix] = pad_adjoint(g, iy, ix, H, W);
-}
-
 }  // namespace dfe
 
 using namespace dfe;
@@ -493,8 +418,8 @@ extern "C" int dfe_elu_pad_fwd(const float* x, const float* bias, float* out, in
   if (!x || !out) return DFE_ERR_NULL;
   if (B <= 0 || C <= 0 || H < 2 || W < 2 || !grid_ok((H + 2L) * (W + 2L), B, C)) return DFE_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (W % 2 == 0 && W >= 4 && aligned8(out)) k_elu_pad_fwd_pair<<<dim3(nblk((H + 2L) * ((W + 2L) / 2)), C, B), 256, 0, st>>>(x, bias, out, C, H, W, apply_elu);
-  else k_elu_pad_fwd<<<dim3(nblk((H + 2L) * (W + 2L)), C, B), 256, 0, st>>>(x, bias, out, C, H, W, apply_elu);
+  if (W % 2 == 0 && W >= 4 && aligned8(out)) k_elu_pad_fwd<2><<<dim3(nblk((H + 2L) * ((W + 2L) / 2)), C, B), 256, 0, st>>>(x, bias, out, C, H, W, apply_elu);
+  else k_elu_pad_fwd<1><<<dim3(nblk((H + 2L) * (W + 2L)), C, B), 256, 0, st>>>(x, bias, out, C, H, W, apply_elu);
   DFE_LAUNCH_CHECK();
   return DFE_OK;
 }
@@ -507,15 +432,11 @@ extern "C" int dfe_elu_pad_bwd(const float* x, const float* bias, const float* g
   const bool pair = W % 2 == 0 && W >= 4 && aligned8(gx) && (!apply_elu || aligned8(x));
   const bool quad = W % 4 == 0 && W >= 8 && aligned16(gx) && (!apply_elu || aligned16(x));
   const unsigned nb = nblk(quad ? static_cast<long>(H) * (W / 4) : pair ? static_cast<long>(H) * (W / 2) : static_cast<long>(H) * W);   // <= the scratch size
-  if (quad) k_elu_pad_bwd_quad<<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
-  else if (pair) k_elu_pad_bwd_pair<<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
-  else k_elu_pad_bwd<<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
+  if (quad) k_elu_pad_bwd<4><<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
+  else if (pair) k_elu_pad_bwd<2><<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
+  else k_elu_pad_bwd<1><<<dim3(nb, C, B), 256, 0, st>>>(x, bias, gout, gx, gbias ? partials : nullptr, C, H, W, apply_elu);
   DFE_LAUNCH_CHECK();
-  if (gbias) {
-    k_glue_bias_final<<<C, 64, 0, st>>>(partials, gbias, B, C, static_cast<int>(nb));
-    DFE_LAUNCH_CHECK();
-  }
-  return DFE_OK;
+  return gbias ? launch_bias_final(partials, gbias, B, C, static_cast<int>(nb), st) : DFE_OK;     // nb partials per plane: the width chosen
 }
 
 extern "C" int dfe_elu_up2_cat_pad_fwd(const float* x, const float* bias, const float* skip, float* out, int B, int C1, int C2,
@@ -547,14 +468,14 @@ extern "C" int dfe_elu_up2_cat_pad_bwd(const float* x, const float* bias, const 
     }
     DFE_LAUNCH_CHECK();
     if (gbias) {
-      k_glue_bias_final<<<C1, 64, 0, st>>>(partials, gbias, B, C1, static_cast<int>(nb));
-      DFE_LAUNCH_CHECK();
+      const int rc = launch_bias_final(partials, gbias, B, C1, static_cast<int>(nb), st);
+      if (rc != DFE_OK) return rc;
     }
   }
   if (gskip && C2 > 0) {
-    if (w % 2 == 0 && w >= 4 && aligned16(gskip)) k_cat_pad_bwd_skip_quad<<<dim3(nblk(1L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
-    else if (w >= 2 && aligned8(gskip)) k_cat_pad_bwd_skip_pair<<<dim3(nblk(2L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
-    else k_cat_pad_bwd_skip<<<dim3(nblk(4L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
+    if (w % 2 == 0 && w >= 4 && aligned16(gskip)) k_cat_pad_bwd_skip<4><<<dim3(nblk(1L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
+    else if (w >= 2 && aligned8(gskip)) k_cat_pad_bwd_skip<2><<<dim3(nblk(2L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
+    else k_cat_pad_bwd_skip<1><<<dim3(nblk(4L * h * w), C2, B), 256, 0, st>>>(gout, gskip, C1, C2, 2 * h, 2 * w);
     DFE_LAUNCH_CHECK();
   }
   return DFE_OK;
