@@ -498,6 +498,20 @@ int dfe_bn_bwd(const float* x, const float* y, const float* gy, const float* wei
                const float* save_invstd, float* gx, float* gres, float* gweight, float* gbias, float* partials,
                float* scratch_means, int G, int Bg, int C, int H, int W, int relu, void* stream);
 
+/* ---- eval-mode BatchNorm2d (+ residual + ReLU) of the depth encoder, forward only (inference.py).
+ * dfe_bn_fold: one launch; per channel, in double, s = weight / sqrt((double)running_var + eps) and t = bias - running_mean * s
+ *              (the unrounded s), each rounded once to fp32 into scale / shift [C].  weight / bias may be NULL (1 / 0).
+ * dfe_bn_eval_fwd: y = act(x * scale[c] + shift[c] [+ residual]) over x [B,C,H,W], act = ReLU if relu; the product, the add and the
+ *              residual add are each rounded once, in that order (no FMA).  residual may be NULL.  y == x (in place) is allowed;
+ *              residual must not alias y.  One read of x (and residual), one write of y, no workspace; 16-byte accesses when
+ *              H*W % 4 == 0 and x, y and residual are 16-byte aligned, dword accesses otherwise; every access stays inside
+ *              [0, B*C*H*W) of its tensor.  B*C is not limited by a grid dimension; DFE_ERR_DIMS when H*W >= 2^31 or
+ *              B*C*ceil(H*W / 512) >= 2^30. */
+int dfe_bn_fold(const float* weight, const float* bias, const float* running_mean, const float* running_var, float eps,
+                float* scale, float* shift, int C, void* stream);
+int dfe_bn_eval_fwd(const float* x, const float* residual, const float* scale, const float* shift, float* y, int B, int C, int H,
+                    int W, int relu, void* stream);
+
 /* ---- convolution epilogue of the flow nets (net_utils.py conv() = Conv2d(bias) + LeakyReLU(0.1),
  * feature_pyramid.py:7-36, pwc_tf.py:16-95): the convolution itself runs on MIOpen *without* its bias, then
  * dfe_bias_act_fwd: z [B,C,H,W] <- act(z + bias[c]) in place; act(v) = v > 0 ? v : slope*v (0.1 LeakyReLU, 0 ReLU, 1 none);

@@ -400,6 +400,84 @@ __global__ void __launch_bounds__(T) k_bn_bwd_small(const float* __restrict__ x,
   }
 }
 
+// ---- eval mode (inference.py): the running statistics folded into one scale and one shift per channel, then a pure streaming
+// pass y = act(x * scale[c] + shift[c] [+ res]).  Forward only.
+__global__ void __launch_bounds__(64) k_bn_fold(const float* __restrict__ weight, const float* __restrict__ bias,
+                                                const float* __restrict__ running_mean, const float* __restrict__ running_var,
+                                                float eps, float* __restrict__ scale, float* __restrict__ shift, int C) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= C) return;
+  const double w = weight ? static_cast<double>(weight[c]) : 1.0, b = bias ? static_cast<double>(bias[c]) : 0.0;
+  const double s = w / sqrt(static_cast<double>(running_var[c]) + static_cast<double>(eps));
+  scale[c] = static_cast<float>(s);
+  shift[c] = static_cast<float>(b - static_cast<double>(running_mean[c]) * s);
+}
+
+// The unit of work is one wave on BNE_WAVE_ELEMS consecutive elements of ONE (n, c) plane: plane and channel are wave-uniform, so
+// scale[c] / shift[c] are fetched once per wave, and no access can straddle two planes.  The grid is one-dimensional over the
+// B * C * ceil(HW / BNE_WAVE_ELEMS) units (a stride loop above BNE_MAX_BLOCKS blocks): no dimension of it carries B * C.
+// VEC (HW % 4 == 0, 16-byte aligned tensors): two float4 per lane, the wave's quads interleaved; otherwise eight dwords per lane
+// at stride 64.  Every load of a lane is issued before its first store, so y may be x.  No LDS, no atomics.  The traffic is the
+// minimum (one read, one write); on the encoder's coarse planes (H*W = 52 .. 208 at 256x832) a wave has at most one float4 per lane
+// and the layer is bound by its launch, not by HBM -- the kernel alone has not been timed (inference.py's calls have: profiles/
+// inference_session.txt).
+constexpr int BNE_BLOCK = 256, BNE_WAVES = BNE_BLOCK / 64, BNE_PER_LANE = 8, BNE_WAVE_ELEMS = 64 * BNE_PER_LANE;
+constexpr int BNE_MAX_BLOCKS = 1 << 20;
+
+template <bool VEC, bool RES>
+__global__ void __launch_bounds__(BNE_BLOCK) k_bn_eval(const float* x, const float* __restrict__ res,
+                                                       const float* __restrict__ scale, const float* __restrict__ shift, float* y,
+                                                       int C, int HW, int nchunk, int units, int relu) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  for (int u = blockIdx.x * BNE_WAVES + wave; u < units; u += gridDim.x * BNE_WAVES) {      // units < 2^30, grid <= 2^20 blocks: no overflow
+    const int plane = u / nchunk, base = (u - plane * nchunk) * BNE_WAVE_ELEMS, c = plane % C;
+    const float s = scale[c], t = shift[c];
+    const long off = static_cast<long>(plane) * HW;
+    float v[BNE_PER_LANE], r[BNE_PER_LANE];
+    if (VEC) {
+#pragma unroll
+      for (int k = 0; k < BNE_PER_LANE / 4; ++k) {
+        const int e = base + (k * 64 + lane) * 4;          // e % 4 == 0 and HW % 4 == 0: e < HW implies e + 3 < HW
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f), p = q;
+        if (e < HW) {
+          q = *reinterpret_cast<const float4*>(x + off + e);
+          if (RES) p = *reinterpret_cast<const float4*>(res + off + e);
+        }
+        v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+        r[4 * k] = p.x; r[4 * k + 1] = p.y; r[4 * k + 2] = p.z; r[4 * k + 3] = p.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < BNE_PER_LANE; ++k) {
+        const int e = base + k * 64 + lane;
+        v[k] = e < HW ? x[off + e] : 0.0f;
+        r[k] = (RES && e < HW) ? res[off + e] : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < BNE_PER_LANE; ++k) {
+      float o = v[k] * s;                                  // product, add, add: one rounding each (-ffp-contract=off)
+      o = o + t;
+      if (RES) o = o + r[k];
+      v[k] = (relu && o <= 0.0f) ? 0.0f : o;
+    }
+    if (VEC) {
+#pragma unroll
+      for (int k = 0; k < BNE_PER_LANE / 4; ++k) {
+        const int e = base + (k * 64 + lane) * 4;
+        if (e < HW) *reinterpret_cast<float4*>(y + off + e) = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < BNE_PER_LANE; ++k) {
+        const int e = base + k * 64 + lane;
+        if (e < HW) y[off + e] = v[k];
+      }
+    }
+  }
+}
+
 }  // namespace dfe
 
 using namespace dfe;
@@ -476,6 +554,35 @@ extern "C" int dfe_bn_bwd(const float* x, const float* y, const float* gy, const
   DFE_LAUNCH_CHECK();
   if (vec) k_bn_bwd_apply<true><<<grid, BN_BLOCK, 0, st>>>(x, y, gy, weight, save_mean, save_invstd, gmean, gxmean, gx, gres, Bg, C, hw, relu);
   else k_bn_bwd_apply<false><<<grid, BN_BLOCK, 0, st>>>(x, y, gy, weight, save_mean, save_invstd, gmean, gxmean, gx, gres, Bg, C, hw, relu);
+  DFE_LAUNCH_CHECK();
+  return DFE_OK;
+}
+
+extern "C" int dfe_bn_fold(const float* weight, const float* bias, const float* running_mean, const float* running_var, float eps,
+                           float* scale, float* shift, int C, void* stream) {
+  if (!running_mean || !running_var || !scale || !shift) return DFE_ERR_NULL;
+  if (C <= 0) return DFE_ERR_DIMS;
+  k_bn_fold<<<(C + 63) / 64, 64, 0, static_cast<hipStream_t>(stream)>>>(weight, bias, running_mean, running_var, eps, scale, shift, C);
+  DFE_LAUNCH_CHECK();
+  return DFE_OK;
+}
+
+extern "C" int dfe_bn_eval_fwd(const float* x, const float* residual, const float* scale, const float* shift, float* y, int B, int C,
+                               int H, int W, int relu, void* stream) {
+  if (!x || !scale || !shift || !y) return DFE_ERR_NULL;
+  const long hw = static_cast<long>(H) * W;
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || hw >= (1L << 31)) return DFE_ERR_DIMS;
+  const long nchunk = (hw + BNE_WAVE_ELEMS - 1) / BNE_WAVE_ELEMS, units = static_cast<long>(B) * C * nchunk;
+  if (units >= (1L << 30)) return DFE_ERR_DIMS;
+  const long blocks = (units + BNE_WAVES - 1) / BNE_WAVES;
+  const int grid = static_cast<int>(blocks < BNE_MAX_BLOCKS ? blocks : BNE_MAX_BLOCKS);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool vec = hw % 4 == 0 && aligned16(x) && aligned16(y) && (!residual || aligned16(residual));
+#define DFE_BNE(VEC, RES) k_bn_eval<VEC, RES><<<grid, BNE_BLOCK, 0, st>>>(x, residual, scale, shift, y, C, static_cast<int>(hw), \
+                                                                          static_cast<int>(nchunk), static_cast<int>(units), relu)
+  if (vec) { if (residual) DFE_BNE(true, true); else DFE_BNE(true, false); }
+  else { if (residual) DFE_BNE(false, true); else DFE_BNE(false, false); }
+#undef DFE_BNE
   DFE_LAUNCH_CHECK();
   return DFE_OK;
 }

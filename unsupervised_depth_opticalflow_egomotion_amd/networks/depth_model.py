@@ -86,10 +86,15 @@ class DepthDecoder(nn.Module):
                 out[scale] = self.sigmoid(self.dispconvs[self.scales.index(scale)](x))
         return out
 
-    def forward_fused(self, feats):
+    def forward_fused(self, feats, scales=None):
         """Same graph on the GPU: the bias / ELU / bilinear x2 / cat / reflection-pad glue between the MIOpen
         convolutions runs as two fused HIP passes (ops.elu_pad, ops.elu_up2_cat_pad); the convolutions are applied
-        bias-free to the padded tensors.  ``a`` / ``c`` hold convolution outputs *before* bias and ELU."""
+        bias-free to the padded tensors.  ``a`` / ``c`` hold convolution outputs *before* bias and ELU.
+        ``scales``: the disparity heads to compute, a subset of the decoder's (default: all of them) -- inference reads
+        scale 0 alone."""
+        want = self.scales if scales is None else [s for s in self.scales if s in scales]
+        if scales is not None and len(want) != len(set(scales)):
+            raise ValueError("scales %s: this decoder has the heads %s" % (list(scales), self.scales))
         out = {}
         p = ops.elu_pad(feats[-1], None, apply_elu=False)        # encoder output: already activated
         for scale in range(4, -1, -1):
@@ -97,9 +102,9 @@ class DepthDecoder(nn.Module):
             a = convs.conv3x3_valid(p, c0.weight)
             q = ops.elu_up2_cat_pad(a, c0.bias, feats[scale - 1] if scale > 0 else None)
             c = convs.conv3x3_valid(q, c1.weight)
-            if scale in self.scales or scale > 0:
+            if scale in want or scale > 0:
                 p = ops.elu_pad(c, c1.bias, apply_elu=True)      # shared by the disparity head and the next stage
-            if scale in self.scales:
+            if scale in want:
                 head = self.dispconvs[self.scales.index(scale)].conv
                 out[scale] = ops.disp_head(p, head.weight, head.bias)      # Conv3x3(C -> 1) + bias + sigmoid
         return out

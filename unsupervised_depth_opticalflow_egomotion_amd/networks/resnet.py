@@ -17,11 +17,16 @@ class FrameBatchNorm2d(nn.BatchNorm2d):
     net one call at a time (model_geometry.py:786-788).  Statistics are per (group, channel) and the running statistics
     receive the ``groups`` momentum updates in group order, i.e. the result of ``groups`` sequential calls.  An optional
     residual add and ReLU are applied to the output.  On a HIP device in training mode this is one fused op
-    (ops.grouped_batch_norm); on the host, or in eval mode, the ATen graph."""
+    (ops.grouped_batch_norm); on the host, or in eval mode, the ATen graph -- except inside a call of an
+    inference.InferenceSession, which installs its folded (scale, shift) tables as ``folded`` for the call: then eval mode is one
+    streaming pass in place over the convolution's output (ops.bn_eval)."""
     groups = 1
     count_deferred = False     # Depth_Model.forward_frames bumps every layer's num_batches_tracked in one foreach call
+    folded = None              # (scale, shift) of ops.bn_fold, for the length of one InferenceSession call
 
     def forward(self, x, residual=None, relu=False):
+        if self.folded is not None and x.is_cuda and not self.training:
+            return ops.bn_eval(x, self.folded[0], self.folded[1], residual=residual, relu=relu, out=x if x.is_contiguous() else None)
         if x.is_cuda and self.training:
             if self.momentum is None or not self.track_running_stats or not self.affine:
                 raise ValueError("FrameBatchNorm2d: only affine, momentum-tracked batch norm is implemented in HIP")

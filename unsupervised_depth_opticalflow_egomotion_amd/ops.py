@@ -1262,6 +1262,54 @@ def grouped_batch_norm(x, weight, bias, running_mean, running_var, groups=1, eps
                                     float(momentum), bool(relu))
 
 
+# --------------------------------------------------------------------------- eval-mode BatchNorm (+ residual + ReLU), forward only
+def _forward_only(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise DfeError("%s is forward-only (it has no backward pass): call it under torch.no_grad(), or detach its inputs" % what)
+
+
+def bn_fold(bn, out=None):
+    """(scale, shift) [C] of an eval-mode ``nn.BatchNorm2d``: in double, scale = weight / sqrt(running_var + eps) and
+    shift = bias - running_mean * scale, each rounded once to fp32 (dfe_bn_fold, one launch).  ``out``: a (scale, shift) pair of
+    earlier tables to fold into in place -- whatever holds their addresses (a captured graph) reads the new values."""
+    if bn.running_mean is None or bn.running_var is None:
+        raise DfeError("bn_fold: the layer tracks no running statistics")
+    _forward_only("bn_fold", bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    C = int(bn.running_mean.numel())
+    scale, shift = out if out is not None else (torch.empty(C, device=bn.running_mean.device, dtype=torch.float32) for _ in range(2))
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.numel() != C:
+            raise DfeError("bn_fold: out must be two fp32 tensors of %d elements" % C)
+    w, b = (None if t is None else f32c(t.detach()) for t in (bn.weight, bn.bias))
+    check(get_lib().dfe_bn_fold(ptr(w), ptr(b), ptr(f32c(bn.running_mean)), ptr(f32c(bn.running_var)), float(bn.eps), ptr(scale),
+                                ptr(shift), C, stream_ptr()), "dfe_bn_fold")
+    return scale, shift
+
+
+def bn_eval(x, scale, shift, residual=None, relu=False, out=None):
+    """act(x * scale[c] + shift[c] [+ residual]) over x [B,C,H,W] with the tables of ``bn_fold``: one streaming pass
+    (dfe_bn_eval_fwd), the product and the adds rounded once each.  ``out``: the destination (default: a fresh tensor); ``out is x``
+    runs in place.  ``residual`` must not share memory with ``out``."""
+    _forward_only("bn_eval", x, scale, shift, residual)
+    if x.dim() != 4:
+        raise DfeError("bn_eval: x must be [B,C,H,W], got %s" % (tuple(x.shape),))
+    x = x if out is x else f32c(x)
+    B, C, H, W = x.shape
+    residual = f32c(residual) if residual is not None else None
+    if residual is not None and residual.shape != x.shape:
+        raise DfeError("bn_eval: residual must have the shape of x")
+    if any(t.dtype != torch.float32 or t.numel() != C for t in (scale, shift)):
+        raise DfeError("bn_eval: scale / shift must be fp32 tensors of %d channels (ops.bn_fold's)" % C)
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape or y.dtype != torch.float32 or x.dtype != torch.float32:
+        raise DfeError("bn_eval: out must be an fp32 tensor of the shape of x")
+    if residual is not None and residual.data_ptr() == y.data_ptr():
+        raise DfeError("bn_eval: residual must not alias out")
+    check(get_lib().dfe_bn_eval_fwd(ptr(x), ptr(residual), ptr(scale), ptr(shift), ptr(y), B, C, H, W, int(bool(relu)), stream_ptr()),
+          "dfe_bn_eval_fwd")
+    return y
+
+
 # --------------------------------------------------------------------------- disparity head (Conv3x3(C -> 1) + sigmoid)
 class DispHeadFn(torch.autograd.Function):
     """sigmoid(conv3x3(p) + bias) on a reflection-padded activation p [B,C,H+2,W+2] -> [B,1,H,W]."""
