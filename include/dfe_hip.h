@@ -46,13 +46,20 @@ const char* dfe_error_string(int code);
  * (model_geometry.py:92-93,696-697), K_s^-1, A = K_s R, b = K_s t with R = Rx Ry Rz
  * (inverse_warp.py:110-145,172-187,284-291).  pose [B,ndir,6]; K [B,3,3];
  * cams: B*ndir*nscale*dfe_camera_floats() floats, index (b*ndir+d)*nscale+s;
- * downscale_host: nscale host floats. */
+ * downscale_host: nscale host floats.
+ * Memory contract: reads pose [B*ndir*6] and K [B*9], writes exactly B*ndir*nscale*dfe_camera_floats() floats of cams (one
+ * thread per camera, 64 per block) and nothing else; no scratch.  Every device pointer needs dword alignment only.  A refusal
+ * (a NULL pointer, a dimension <= 0, nscale above the library's limit) comes before the launch and leaves cams untouched. */
 int dfe_camera_floats(void);
 int dfe_prepare_cameras(const float* pose, const float* K, float* cams, int B, int ndir, int nscale,
                         const float* downscale_host, void* stream);
 
 /* pose_vec2mat (inverse_warp.py:172-187) -> T34 [n,3,4] and/or compute_essential_matrix
- * (inverse_warp.py:354-364) -> E [n,3,3]; either output may be NULL. */
+ * (inverse_warp.py:354-364) -> E [n,3,3]; either output may be NULL.
+ * Memory contract: the forward reads vec [n,6] and writes every element of whichever of T34 / E is given; the backward reads
+ * vec and whichever of gT34 / gE is given (not both NULL) and writes every element of gvec [n,6].  Nothing else is read or
+ * written, no scratch; every pointer needs dword alignment only and the result does not depend on it.  The forward matrices
+ * are the reference's fp32 arithmetic bit for bit (correctly rounded cos / sin); the backward sums in double. */
 int dfe_pose_vec2mat_fwd(const float* vec, float* T34, float* E, int n, void* stream);
 int dfe_pose_vec2mat_bwd(const float* vec, const float* gT34, const float* gE, float* gvec, int n, void* stream);
 
@@ -125,7 +132,16 @@ int dfe_warp_flow_bwd(const float* x, const float* flow, const float* gout, floa
  * (the last three may be NULL).  Backward: g_depth [B,1,H,W], g_refdepth [B,1,H,W]
  * (NULL to skip; every element written, through the scatter workspace g_refdepth_ws of
  * dfe_scatter_ws_bytes(B*H*W) bytes), g_pose [B,6]; partials: workspace of
- * dfe_pose_partials_floats(B,H,W) floats. */
+ * dfe_pose_partials_floats(B,H,W) floats.
+ * Memory contract: the forward reads img, depth, cams (B blocks) and, when out_pdepth is given, ref_depth, and writes every
+ * element of out_img and of each optional output given; the 2x2 footprint is fetched as two dword-aligned 8-byte loads clamped
+ * into the plane.  The backward reads the same inputs and the cotangents given (g_pdepth and g_cdepth may be NULL) and
+ * writes every element of g_depth, g_pose, of g_refdepth when given (which needs g_pdepth and g_refdepth_ws) and of partials:
+ * B * ceil(H*W / 256) rows of 12 floats, one per 256-pixel block, added per sample in block order in double -- bitwise
+ * reproducible, as is the fixed-point scatter behind g_refdepth.  partials and g_refdepth_ws need no initialisation; the library
+ * writes inside dfe_pose_partials_floats / dfe_scatter_ws_bytes(B*H*W) only.  g_refdepth_ws on 16 bytes; every other pointer
+ * needs dword alignment only, and the result does not depend on it.  H < 2 or W < 2 is DFE_ERR_DIMS; every refusal comes
+ * before the first launch and leaves all outputs untouched. */
 int dfe_pose_partials_floats(int B, int H, int W);
 int dfe_inverse_warp2_fwd(const float* img, const float* depth, const float* ref_depth, const float* cams,
                           float* out_img, float* out_valid, float* out_pdepth, float* out_cdepth, int B, int H, int W,
@@ -135,7 +151,11 @@ int dfe_inverse_warp2_bwd(const float* img, const float* depth, const float* ref
                           float* g_refdepth, void* g_refdepth_ws, float* g_pose, float* partials, int B, int H, int W,
                           int align_corners, void* stream);
 
-/* ---- calculate_rigid_flow(depth, pose, intrinsics)  inverse_warp.py:311-342 ---------------- */
+/* ---- calculate_rigid_flow(depth, pose, intrinsics)  inverse_warp.py:311-342 ----------------
+ * Memory contract: the forward reads depth [B,1,H,W] and cams (B blocks) and writes every element of out [B,2,H,W]; the
+ * backward reads depth, cams and gout [B,2,H,W] and writes every element of g_depth [B,1,H,W], g_pose [B,6] and partials
+ * (dfe_pose_partials_floats(B,H,W) floats, no initialisation needed, summed as in dfe_inverse_warp2_bwd).  Nothing else is
+ * touched; every pointer needs dword alignment only; H = W = 1 is accepted.  Refusals come before the first launch. */
 int dfe_rigid_flow_fwd(const float* depth, const float* cams, float* out, int B, int H, int W, void* stream);
 int dfe_rigid_flow_bwd(const float* depth, const float* cams, const float* gout, float* g_depth, float* g_pose,
                        float* partials, int B, int H, int W, void* stream);
@@ -147,7 +167,10 @@ int dfe_rigid_flow_bwd(const float* depth, const float* cams, const float* gout,
  * compute_texture_mask (model_geometry.py:134-140): (mean_c|img - warped| < mean_c|img - source|) -> [B,1,H,W];
  * compute_dynamic_mask (model_geometry.py:699-711): flow, rigid [B,2,H,W] -> mask = (n(|rigid-flow|)^2 <
  *   alpha (n(flow)^2 + n(rigid)^2) + beta), score = 1 / (1e-4 + n(|rigid-flow|)) (score may be NULL).
- * Same device arithmetic as the fused stack: masks are bit-identical to dfe_geom_loss_fwd's mask pack. */
+ * Same device arithmetic as the fused stack: masks are bit-identical to dfe_geom_loss_fwd's mask pack.
+ * Memory contract: each entry point reads its two or three dense inputs and writes every element of each output ([B,1,H,W];
+ * all four of dfe_occ_masks are required, score may be NULL), one thread per pixel, nothing else; no scratch; every pointer
+ * needs dword alignment only.  B > 65535 is DFE_ERR_DIMS; refusals come before the launch and write nothing. */
 int dfe_occ_masks(const float* from_l, const float* tgt, const float* from_r, float* occ_bwd, float* occ_fwd,
                   float* valid_bwd, float* valid_fwd, int B, int H, int W, void* stream);
 int dfe_texture_mask(const float* img, const float* warped, const float* source, float* out, int B, int H, int W,
@@ -158,7 +181,10 @@ int dfe_dynamic_mask(const float* flow, const float* rigid, float* mask, float* 
 /* ---- device-side input pipeline  core/dataset/kitti_prepared.py:63-90,132-152, train.py:171 ------------------
  * in_u8: uint8 [B][3*H0][W0][3] raw stacked triplets (left / target / right along H, channel order as stored);
  * flip: B device bytes (non-zero = horizontal flip of that sample, NULL = none); out: fp32 [B][3][3*H][W] in [0,1]:
- * per frame bilinear resize (half-pixel centres, edge replication) to H x W, flip, / 255, HWC -> CHW. */
+ * per frame bilinear resize (half-pixel centres, edge replication) to H x W, flip, / 255, HWC -> CHW.
+ * Memory contract: reads in_u8 (B*3*H0*W0*3 bytes) and, when given, the B bytes of flip, byte by byte -- neither needs any
+ * alignment -- and writes every element of out (dword alignment), nothing else; no scratch.  The source coordinate is fp32:
+ * at W0 = 300 it carries ~300 * 2^-24 of a pixel, which is the accuracy of the result.  Refusals write nothing. */
 int dfe_prepare_triplets(const unsigned char* in_u8, const unsigned char* flip, float* out, int B, int H0, int W0,
                          int H, int W, void* stream);
 
@@ -190,7 +216,11 @@ int dfe_prepare_triplets_u8(const unsigned char* in_u8, const dfe_u8_desc* desc,
 /* ---- forward-splat occlusion map  core/networks/model_flow.py:33-39 (get_occlusion_mask_from_flow) -----------
  * The reference calls an undefined `transformerFwd`; this is its TrianFlow meaning: out [B,1,H,W] = bilinear forward
  * warp of a ones image by flow [B,2,H,W] (optionally clamped to [0,1]).  Order-independent scatter through ws
- * (dfe_scatter_ws_bytes(B*H*W) bytes); every element of out is written; bitwise reproducible. */
+ * (dfe_scatter_ws_bytes(B*H*W) bytes); every element of out is written; bitwise reproducible.
+ * Memory contract: reads flow, writes every element of out and, inside dfe_scatter_ws_bytes(B*H*W) bytes only, ws, which needs
+ * no initialisation and holds nothing of use afterwards.  ws on 16 bytes; flow and out need dword alignment only.  A source
+ * pixel whose target is NaN or not inside (-1, W) x (-1, H) deposits nothing; a tap outside the image is dropped, the others of
+ * that pixel are kept.  Each weight is one fp32 product rounded to a grid of 2^-35.  clamp01 clamps the finished map in place. */
 int dfe_forward_splat_ones(const float* flow, float* out, void* ws, int B, int H, int W, int clamp01, void* stream);
 
 /* ---- self-test of the short correctly rounded fp32 sequences (csrc/loss_stack_exact.h) ------------------------
@@ -201,7 +231,11 @@ int dfe_forward_splat_ones(const float* flow, float* out, void* ws, int B, int H
  *   [2] x/z over `npairs` pseudo-random pairs, [3] the same with all-ones divisor significands.  All must be 0. */
 int dfe_exact_math_selftest(unsigned long long* counts, unsigned long long npairs, void* stream);
 
-/* ---- SSIM(x, y)  pytorch_ssim/ssim.py:4-19 -------------------------------------------------- */
+/* ---- SSIM(x, y)  pytorch_ssim/ssim.py:4-19 --------------------------------------------------
+ * Memory contract: the forward reads x, y [B,C,H,W] and writes every element of out; the backward reads x, y and gout and writes
+ * every element of whichever of gx / gy is given (not both NULL; one alone returns the bits of the pair).  Tiles of 32 x 8 with a
+ * zero-padded halo staged in LDS: nothing outside the planes is read.  No scratch; dword alignment only.  B*C > 65535 (a grid
+ * dimension) is DFE_ERR_DIMS, before the launch, with nothing written. */
 int dfe_ssim_fwd(const float* x, const float* y, float* out, int B, int C, int H, int W, void* stream);
 int dfe_ssim_bwd(const float* x, const float* y, const float* gout, float* gx, float* gy, int B, int C, int H, int W,
                  void* stream);
@@ -278,7 +312,12 @@ int dfe_resize(const float* in, float* out, int planes, int inH, int inW, int ou
  * `F.interpolate(flow6, scale_factor=2.0, mode='bilinear') * 2.0`; :175-178: `F.interpolate(flow2 * 4.0, [h, w])`):
  * pre_scale = 1: out = resize(in * mult); 0: out = resize(in) * mult -- each rounded like the ATen (CPU) composition.
  * The backward pass is the adjoint as a gather per input element (no atomics, unlike ATen's upsample backward);
- * DFE_ERR_UNSUPPORTED when the up-sampling ratio exceeds 4 per axis. */
+ * DFE_ERR_UNSUPPORTED when the up-sampling ratio exceeds 4 per axis.
+ * Memory contract (dfe_resize and the pair below): `in` [planes,inH,inW] is read, every element of `out` [planes,outH,outW]
+ * written (the backward: gout read, every element of gin [planes,inH,inW] written), one thread per written element, nothing else;
+ * no scratch; dword alignment only, and the result does not depend on it.  Mode 0 and dfe_resize_bilinear_fwd return ATen's
+ * (CPU) bits on both sides of its kernel switch at outH + outW = 128.  The backward's refusal (2 out > 8 in on an axis: the
+ * 12 candidates per axis of its register path) comes before the launch and leaves gin untouched; the forward has no such limit. */
 int dfe_resize_bilinear_fwd(const float* in, float* out, int planes, int inH, int inW, int outH, int outW, float mult,
                             int pre_scale, void* stream);
 int dfe_resize_bilinear_bwd(const float* gout, float* gin, int planes, int inH, int inW, int outH, int outW, float mult,
@@ -475,7 +514,12 @@ int dfe_wino_conv3x3_u_act(const float* x, const float* U, const float* bias, fl
  * (pose_cnn.py:32,43,48: Conv2d(256 | 24 | 12, 12, 1) on 2x7 planes).  x [B,Ci,H,W], weight [Co,Ci] (= [Co,Ci,1,1]).
  * dfe_conv1x1_small_fwd: y = act(conv1x1(x, weight) + bias[co]) (bias may be NULL; act as in dfe_planeconv_fwd).
  * dfe_conv1x1_small_bwd: gx [B,Ci,H,W] and / or gweight [Co,Ci] (either may be NULL) for the output gradient gy [B,Co,H,W]
- * (of the pre-activation: apply dfe_bias_act_bwd first).  One thread per output, serial sums: reproducible. */
+ * (of the pre-activation: apply dfe_bias_act_bwd first).  One thread per output, serial sums: reproducible.
+ * Memory contract: the forward reads x, weight and bias (when given) and writes every element of y; the backward reads gy,
+ * weight (for gx) and x (for gweight) and writes every element of whichever of gx / gweight is given -- each returns the same
+ * bits alone or together.  Nothing else is touched; no scratch; every pointer needs dword alignment only and the result does not
+ * depend on it.  H*W > 256, B*H*W > 4096 or more than 4096 channels on either side is DFE_ERR_UNSUPPORTED
+ * (dfe_conv1x1_small_supported == 0) from both entry points, before any launch, with nothing written. */
 int dfe_conv1x1_small_supported(int B, int Ci, int Co, int H, int W);
 int dfe_conv1x1_small_fwd(const float* x, const float* weight, const float* bias, float slope, float* y, int B, int Ci, int Co,
                           int H, int W, void* stream);

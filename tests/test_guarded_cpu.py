@@ -660,3 +660,194 @@ def test_the_loss_stack_cases_are_margin_checked_and_no_mask_is_constant(shape):
         for k in ("valid_bwd", "valid_fwd", "occ_bwd", "occ_fwd", "dyna_bwd", "dyna_fwd", "texture_bwd", "texture_fwd"):
             frac = float(masks[k][0].mean())
             assert 0.02 < frac < 0.98, (shape, ac, k, frac)
+
+
+# ========================================================================================================= geometry, resize, splat, 1x1
+# Self-tests of tests/guarded_geom.py and tests/geom_cases.py: every float64 reference agrees with float64 ATen / autograd where ATen
+# has the operation, the splat conserves mass, the matrices reach every plane-size class, and no committed inverse_warp2 gradient
+# case has an unsafe pixel left.
+from tests import geom_cases as GEO         # noqa: E402
+from tests import guarded_geom as GG        # noqa: E402
+
+F64 = torch.float64
+
+
+def _close(a, b, tol=1e-12):
+    a, b = a.detach(), b.detach()
+    return float((a - b).abs().max()) <= tol * max(1.0, float(b.abs().max()))
+
+
+def test_geom_pose_reference_is_the_oracles_function_in_float64():
+    from oracle import loss_stack_oracle as O
+    gen = torch.Generator().manual_seed(3)
+    vec = (0.3 * torch.randn(9, 6, generator=gen)).double()
+    gT, gE = torch.randn(9, 3, 4, generator=gen).double(), torch.randn(9, 3, 3, generator=gen).double()
+    T34, E = GG.pose_mats_ref(vec)
+    assert _close(T34, O.pose_vec2mat(vec)) and _close(E, O.compute_essential_matrix(vec))
+    v = vec.clone().requires_grad_(True)
+    want = torch.autograd.grad((O.pose_vec2mat(v) * gT).sum() + (O.compute_essential_matrix(v) * gE).sum(), v)[0]
+    assert _close(GG.pose_mats_vjp_ref(vec, gT, gE), want)
+    assert _close(GG.pose_mats_vjp_ref(vec, gT, None) + GG.pose_mats_vjp_ref(vec, None, gE), want)
+    assert GG.chain_err(want.float(), want) <= 1.0 and GG.chain_err(want * (1 + 8 * G.U24), want) > 4.0
+
+
+@pytest.mark.parametrize("ac", [False, True])
+def test_geom_sampling_reference_is_grid_sample_in_float64(ac):
+    """the zero-padded bilinear sample, values and both gradients, and the whole inverse_warp2 / rigid-flow chain against the
+    oracle's graph run in float64"""
+    from oracle import loss_stack_oracle as O
+    B, H, W = 2, 9, 31
+    c, unsafe, _ = GG.safe_warp_inputs(B, H, W, 5, "oob", ac)
+    assert unsafe == 0
+    img, d, rd, p, K = (c[k].double() for k in ("img", "depth", "ref_depth", "pose", "K"))
+    gen = torch.Generator().manual_seed(1)
+    ix, iy = (torch.rand(B, 40, generator=gen).double() * (W + 3) - 2).requires_grad_(True), (torch.rand(B, 40, generator=gen).double() * (H + 3) - 2).requires_grad_(True)
+    im = img.clone().requires_grad_(True)
+    got = GG.bilinear_zero_ref(im, ix, iy)
+    un = (lambda t, n: 2 * t / (n - 1) - 1) if ac else (lambda t, n: (2 * t + 1) / n - 1)
+    want = F.grid_sample(im, torch.stack([un(ix, W), un(iy, H)], 2)[:, None], mode="bilinear", padding_mode="zeros", align_corners=ac)[:, :, 0]
+    assert _close(got, want)
+    cot = torch.randn(got.shape, generator=gen).double()
+    for a, b in zip(torch.autograd.grad(got, [im, ix, iy], cot, retain_graph=True), torch.autograd.grad(want, [im, ix, iy], cot)):
+        assert _close(a, b, 1e-10)
+    d1, r1, p1 = (t.clone().requires_grad_(True) for t in (d, rd, p))
+    d2, r2, p2 = (t.clone().requires_grad_(True) for t in (d, rd, p))
+    mine = GG.inverse_warp2_ref(img, d1, r1, p1, K, ac)
+    theirs = O.inverse_warp2(img, d2, r2, p2, K, align_corners=ac)        # float64 through the oracle's graph: its K^-1 is fp32-made
+    loss = lambda o: (o[0] * c["wi"].double()).sum() + (o[2] * c["wp"].double()).sum() + (o[3] * c["wc"].double()).sum()
+    for a, b in zip((mine["img"], mine["valid"], mine["pdepth"], mine["cdepth"]), theirs):
+        assert _close(a, b, 1e-5)
+    for a, b in zip(torch.autograd.grad(loss((mine["img"], None, mine["pdepth"], mine["cdepth"])), [d1, r1, p1]), torch.autograd.grad(loss(theirs), [d2, r2, p2])):
+        assert _close(a, b, 1e-4)
+    assert _close(GG.rigid_flow_ref(d, p, K)[0], O.calculate_rigid_flow(d, p, K), 1e-5)
+
+
+def test_geom_ssim_resize_and_area_references_are_atens_in_float64():
+    from oracle import loss_stack_oracle as O
+    gen = torch.Generator().manual_seed(2)
+    x, y = torch.rand(2, 3, 9, 33, generator=gen).double(), torch.rand(2, 3, 9, 33, generator=gen).double()
+    assert _close(GG.ssim_ref(x, y), O.SSIM(x, y), 1e-10)
+    pre, gate = GG.ssim_loss_gate(torch.tensor([1.5, 1.0, 0.0, -1.0, -1.5], dtype=F64))
+    assert gate.tolist() == [0.0, 0.0, 1.0, 0.0, 0.0] and pre.tolist() == [-0.25, 0.0, 0.5, 1.0, 1.25]
+    for (h, w), (H, W) in GEO.RB_CASES + [GEO.RB_REFUSED] + GEO.R0_CASES:
+        v = torch.randn(2, h, w, generator=gen).double().requires_grad_(True)
+        g = torch.randn(2, H, W, generator=gen).double()
+        want = F.interpolate(v[None], (H, W), mode="bilinear", align_corners=False)[0]
+        assert _close(GG.resize_bilinear_ref(v.detach(), (H, W), 3.0), want * 3.0)
+        assert _close(GG.resize_adjoint_ref(g, (h, w), 3.0), torch.autograd.grad(want, v, g)[0] * 3.0)
+        assert bool((GG.resize_adjoint_ref(g, (h, w), -3.0, absolute=True) >= GG.resize_adjoint_ref(g, (h, w), 3.0).abs() - 1e-12).all())
+    for (h, w), (H, W) in GEO.R1_CASES:
+        v = torch.randn(2, h, w, generator=gen).double()
+        assert _close(GG.area_ref(v, (H, W)), F.interpolate(v[None], (H, W), mode="area")[0])
+        assert _close(GG.area_ref(v, (H, W), absolute=True), F.adaptive_avg_pool2d(v.abs()[None], (H, W))[0])
+
+
+def test_geom_conv1x1_references_are_atens_in_float64_and_the_serial_sum_is_serial():
+    gen = torch.Generator().manual_seed(4)
+    for shape in [(3, 24, 12, 2, 7), (2, 5, 7, 16, 16), (1, 1, 1, 1, 1)]:
+        B, Ci, Co, H, W = shape
+        x, w, bias, gy, _ = GG.conv1x1_inputs(shape, True, 11)
+        assert G.margin_ok(GG.conv1x1_ref(x, w, bias), GG.conv1x1_ref(x, w, bias, absolute=True))
+        xd, wd = x.double().requires_grad_(True), w.double().requires_grad_(True)
+        want = F.conv2d(xd, wd[:, :, None, None], bias.double())
+        assert _close(GG.conv1x1_ref(x, w, bias), want)
+        gx, gw = torch.autograd.grad(want, [xd, wd], gy.double())
+        assert _close(GG.conv1x1_gx_ref(gy, w), gx) and _close(GG.conv1x1_gw_ref(gy, x), gw)
+        for f32, f64, A in ((GG.conv1x1_ref(x, w, bias, torch.float32), GG.conv1x1_ref(x, w, bias), GG.conv1x1_ref(x, w, bias, absolute=True)),
+                            (GG.conv1x1_gx_ref(gy, w, torch.float32), GG.conv1x1_gx_ref(gy, w), GG.conv1x1_gx_ref(gy, w, absolute=True)),
+                            (GG.conv1x1_gw_ref(gy, x, torch.float32), GG.conv1x1_gw_ref(gy, x), GG.conv1x1_gw_ref(gy, x, absolute=True))):
+            assert f32.dtype == torch.float32 and f32.shape == f64.shape == A.shape
+            e, zero_ok = G.norm_err(f32, f64, A)
+            assert zero_ok and e <= max(Ci, Co, B * H * W) + 1       # a serial sum of n terms: at most n roundings of at most A each
+
+
+def test_geom_triplet_reference_is_the_half_pixel_resize_with_edge_replication():
+    gen = torch.Generator().manual_seed(6)
+    for (H0, W0), (H, W) in GEO.TRIPLET_CASES:
+        u8 = torch.randint(0, 256, (2, 3 * H0, W0, 3), generator=gen, dtype=torch.uint8)
+        got = GG.triplets_ref(u8, [1, 0], H, W)
+        assert got.shape == (2, 3, 3 * H, W) and got.dtype == F64 and 0.0 <= float(got.min()) and float(got.max()) <= 1.0
+        fr = u8.double().reshape(2, 3, H0, W0, 3).permute(0, 1, 4, 2, 3).reshape(6, 3, H0, W0)        # [b*frame, c, H0, W0]
+        if (H, W) == (H0, W0):
+            want = fr / 255.0
+        elif H <= H0 and W <= W0 or H >= H0 and W >= W0:
+            # F.interpolate(align_corners=False) is the same geometry: half-pixel centres, source index clamped at the borders
+            want = F.interpolate(fr, (H, W), mode="bilinear", align_corners=False) / 255.0
+        want = want.reshape(2, 3, 3, H, W).permute(0, 2, 1, 3, 4).reshape(2, 3, 3 * H, W)
+        assert _close(got[1], want[1], 1e-12) and _close(got[0], want[0].flip(-1), 1e-12)
+        assert _close(GG.triplets_ref(u8, None, H, W)[0], want[0], 1e-12)
+        y32 = GG.triplets_ref(u8, [1, 0], H, W, GG.np.float32)
+        # the fp32 source coordinate carries ~4 roundings at its own magnitude (up to 300 here); a value moves by at most that
+        # per axis (neighbouring bytes / 255 differ by at most 1)
+        assert y32.dtype == torch.float32 and float((y32.double() - got).abs().max()) <= 8 * G.U24 * max(H0, W0)
+
+
+@pytest.mark.parametrize("kind", GEO.SPLAT_KINDS)
+def test_geom_splat_reference_conserves_mass_and_counts_its_taps(kind):
+    B, H, W = 3, 9, 31
+    flow = GG.splat_flow(kind, B, H, W, torch.Generator().manual_seed(8))
+    ref, mass, cnt = GG.splat_ref(flow)
+    assert ref.shape == (B, 1, H, W) and torch.equal(ref, mass) and bool((ref >= 0).all())
+    t = GG.splat_taps(flow)
+    xs, ys = torch.arange(W).float()[None, None, :], torch.arange(H).float()[None, :, None]
+    tx, ty = (xs + flow[:, 0]).reshape(B, -1), (ys + flow[:, 1]).reshape(B, -1)
+    inside = (tx >= 0) & (tx <= W - 1) & (ty >= 0) & (ty <= H - 1)          # all four taps land (or carry a zero weight)
+    per_src = sum(torch.from_numpy(t["w"][k]).double() * torch.from_numpy(t["inb"][k]).double() for k in range(4))
+    assert bool(((per_src - 1.0).abs()[inside] <= 4 * G.U24).all()) and bool((per_src <= 1.0 + 4 * G.U24).all())
+    assert abs(float(ref.sum()) - float(per_src.sum())) <= 1e-9 * max(1.0, float(per_src.sum()))
+    assert float(cnt.sum()) == float(sum(((torch.from_numpy(t["w"][k]) != 0) & torch.from_numpy(t["inb"][k])).sum() for k in range(4)))
+    if kind == "zero":
+        assert torch.equal(ref, torch.ones_like(ref)) and torch.equal(cnt, torch.ones_like(cnt))
+    if kind == "edge":         # half-inside taps: sources that deposit less than 1 but more than 0
+        assert bool(((per_src > 0) & (per_src < 1 - 1e-3)).any())
+    if kind == "nan":
+        assert int((~torch.from_numpy(t["live"])).sum()) >= 1 and bool(torch.isfinite(ref).all())
+    if kind == "out":
+        assert float(ref[0].sum()) < 0.25 * float(ref[1].sum()) and float(ref.sum()) < 0.2 * B * H * W      # most of the mass leaves the image
+
+
+def test_geom_case_matrices_reach_every_plane_size_class():
+    shapes = GEO.PIXEL_SHAPES + [GEO.TINY_SHAPE]
+    assert {GEO.plane_class(h, w) for _, h, w in shapes} == GEO.PLANE_CLASSES
+    assert {GEO.plane_class(h, w) for _, h, w in GEO.PIXEL_SHAPES} == GEO.PLANE_CLASSES - {"pixel"}
+    assert {c[:3] for c in GEO.warp_grad_cases()} == set(GEO.PIXEL_SHAPES) and {c[3] for c in GEO.warp_grad_cases()} == {"rand", "oob"}
+    assert {c[3] for c in GEO.warp_fwd_cases()} == {"rand", "oob", "identity", "clamp"}
+    assert {c[:3] for c in GEO.flow_cases()} >= set(shapes)
+    assert any(-(-h * w // 256) == 2 and h * w % 256 == 23 for _, h, w in GEO.PIXEL_SHAPES)       # two partial rows per sample, 23 live threads
+    assert any(w % 4 for _, h, w in GEO.PIXEL_SHAPES if h * w > 1024)
+    # SSIM tiles of 32 x 8: inside one tile, exactly one, one row and one column past it, three tiles across
+    assert {(-(-w // 32), -(-h // 8)) for _, _, h, w in GEO.SSIM_SHAPES} == {(1, 1), (2, 2), (3, 1)} and (2, 3, 8, 32) in GEO.SSIM_SHAPES
+    # the adjoint's register path: ratio 4 is its limit, one refused case beyond it, one down-sampling case
+    lim = lambda i, o: 2 * o[0] <= 8 * i[0] and 2 * o[1] <= 8 * i[1]
+    assert all(lim(i, o) for i, o in GEO.RB_CASES) and not lim(*GEO.RB_REFUSED)
+    assert any(2 * o[0] == 8 * i[0] and 2 * o[1] == 8 * i[1] for i, o in GEO.RB_CASES) and any(o[0] < i[0] for i, o in GEO.RB_CASES)
+    assert {o[0] + o[1] <= 128 for _, o in GEO.R0_CASES} == {True, False} and any(o[0] + o[1] == 128 for _, o in GEO.R0_CASES) and any(o[0] + o[1] == 129 for _, o in GEO.R0_CASES)
+    assert any(i[0] % o[0] and i[1] % o[1] for i, o in GEO.R1_CASES) and any(i[0] == 2 * o[0] and i[1] == 2 * o[1] for i, o in GEO.R1_CASES)
+    # 1x1: both limits met exactly, both refusals one past them
+    assert any(h * w == 256 for _, _, _, h, w in GEO.C1_SHAPES) and any(b * h * w == 4096 for b, _, _, h, w in GEO.C1_SHAPES)
+    assert {(h * w, b * h * w > 4096) for b, _, _, h, w in GEO.C1_REFUSED} == {(257, False), (241, True)} and any(b * h * w == 4097 for b, _, _, h, w in GEO.C1_REFUSED)
+    assert max(b * d * s for b, d, s in GEO.CAMERA_CASES) > 64 and max(GEO.POSE_N) > 64
+
+
+_GEO_GRAD = GEO.warp_grad_cases()
+
+
+@pytest.mark.parametrize("case", _GEO_GRAD, ids=["%dx%dx%d-%s" % c[:4] for c in _GEO_GRAD])
+def test_geom_margin_builder_leaves_no_unsafe_pixel(case):
+    """the four conditions of tests/guarded_geom.py's warp_unsafe after the depth nudges, for both align_corners settings: the cap
+    is zero -- a condition of the case, not a tolerance; and the nudged inputs still exercise what the case is for"""
+    B, H, W, kind, seed = case
+    for ac in (False, True):
+        c, unsafe, before = GG.safe_warp_inputs(B, H, W, seed, kind, ac)
+        assert unsafe == 0, (case, ac, before)
+        assert not bool(GG.warp_unsafe(c["depth"], c["ref_depth"], c["pose"], c["K"], ac).any())
+        r = GG.inverse_warp2_ref(*(c[k].double() for k in ("img", "depth", "ref_depth", "pose", "K")), ac)
+        if H * W >= 35:
+            assert 0.0 < float(r["valid"].mean()) and (kind != "oob" or float(r["valid"].mean()) < 1.0), (case, ac)
+    for c4 in GEO.flow_cases():
+        if c4[:3] == (B, H, W):
+            assert GG.safe_flow_inputs(*c4[:3], c4[4], c4[3])[1] == 0, c4
+    d = GG.mask_inputs(B, H, W, B + H + W)
+    assert all(G.margin_ok(v, a) for v, a in d["margins"])
+    if H * W >= 35:
+        assert all(0.0 < float(d[k].mean()) < 1.0 for k in ("occ_bwd", "occ_fwd", "texture", "dyna"))

@@ -121,3 +121,73 @@ def test_planeconv_refuses_short_strides_and_large_planes():
     assert lib.dfe_planeconv_wgrad(_p(x), _p(x), _p(d1), _p(ws), 1, 4, 4, 65, 64, st) == -4
     torch.cuda.synchronize()
     assert d1.untouched() and d2.untouched() and ws.untouched() and d1.intact() and ws.intact()
+
+
+# ========================================================================================================= 1x1 on tiny planes
+# dfe_conv1x1_small_fwd / _bwd (PoseCNN's pose_conv and refinement head): cases in tests/geom_cases.py, float64 references and the
+# serial fp32 sum of the host in tests/guarded_geom.py; A = sum |x||w| + |b|; no pre-activation within MARGIN A of zero.
+from tests import geom_cases as GC          # noqa: E402
+from tests import guarded_geom as GG        # noqa: E402
+
+
+def _ins_unchanged(tag, pairs):
+    for i, (c, t) in enumerate(pairs):
+        assert G.bits_equal(c.cpu(), t.reshape(c.view.shape)), (tag, "input %d changed" % i)
+
+
+@pytest.mark.parametrize("shape", GC.C1_SHAPES)
+def test_conv1x1_small_guarded(shape):
+    B, Ci, Co, H, W = shape
+    lib, st = _lib()
+    assert lib.dfe_conv1x1_small_supported(B, Ci, Co, H, W) == 1
+    for with_bias in (True, False):
+        x, w, bias, gy, seed = GG.conv1x1_inputs(shape, with_bias, sum(shape))
+        pre64, A = GG.conv1x1_ref(x, w, bias), GG.conv1x1_ref(x, w, bias, absolute=True)
+        assert G.margin_ok(pre64, A)
+        pre32 = GG.conv1x1_ref(x, w, bias, torch.float32)
+        name = "conv1x1_small %s bias %d" % (shape, with_bias)
+        for slope in GC.C1_SLOPES:
+            first = None
+            for off in GC.OFFS:
+                tag = "%s slope %g off %d" % (name, slope, off)
+                xc, wc, y = G.Carved(x.shape, off, fill=x), G.Carved(w.shape, (off + 1) % 4, fill=w), G.Carved((B, Co, H, W), (off + 2) % 4)
+                bc = G.Carved((Co,), (off + 3) % 4, fill=bias) if with_bias else None
+                assert lib.dfe_conv1x1_small_fwd(_p(xc), _p(wc), _p(bc), ctypes.c_float(slope), _p(y), B, Ci, Co, H, W, st) == 0, tag
+                _check([xc, wc, y] + ([bc] if bc else []), [y], tag)
+                _ins_unchanged(tag, [(xc, x), (wc, w)] + ([(bc, bias)] if bc else []))
+                if first is None:
+                    first = y.cpu()
+                    G.check_bound(tag, first, G.leaky(pre32, slope), G.leaky(pre64, slope), A)
+                assert torch.equal(y.cpu(), first), (tag, "the result depends on the alignment")
+        gx32, gx64, gxA = GG.conv1x1_gx_ref(gy, w, torch.float32), GG.conv1x1_gx_ref(gy, w), GG.conv1x1_gx_ref(gy, w, absolute=True)
+        gw32, gw64, gwA = GG.conv1x1_gw_ref(gy, x, torch.float32), GG.conv1x1_gw_ref(gy, x), GG.conv1x1_gw_ref(gy, x, absolute=True)
+        first = None
+        for off in GC.OFFS:
+            for mode in ("both", "gx", "gweight"):
+                tag = "%s bwd %s off %d" % (name, mode, off)
+                gc, xc, wc = G.Carved(gy.shape, off, fill=gy), G.Carved(x.shape, (off + 1) % 4, fill=x), G.Carved(w.shape, (off + 2) % 4, fill=w)
+                gx = G.Carved(x.shape, (off + 3) % 4) if mode != "gweight" else None
+                gw = G.Carved(w.shape, off) if mode != "gx" else None
+                assert lib.dfe_conv1x1_small_bwd(_p(gc), _p(xc), _p(wc), _p(gx), _p(gw), B, Ci, Co, H, W, st) == 0, tag
+                _check([c for c in (gc, xc, wc, gx, gw) if c], [c for c in (gx, gw) if c], tag)
+                _ins_unchanged(tag, [(gc, gy), (xc, x), (wc, w)])
+                if first is None:
+                    first = (gx.cpu(), gw.cpu())
+                    G.check_bound(name + " gx", first[0], gx32, gx64, gxA)
+                    G.check_bound(name + " gweight", first[1], gw32, gw64, gwA)
+                assert gx is None or torch.equal(gx.cpu(), first[0]), (tag, "gx depends on the alignment or on what else is requested")
+                assert gw is None or torch.equal(gw.cpu(), first[1]), (tag, "gweight depends on the alignment or on what else is requested")
+
+
+@pytest.mark.parametrize("shape", GC.C1_REFUSED)
+def test_conv1x1_small_refuses_larger_planes_and_touches_nothing(shape):
+    """H*W = 257 and B*H*W = 4097: DFE_ERR_UNSUPPORTED from both entry points before anything is launched"""
+    B, Ci, Co, H, W = shape
+    lib, st = _lib()
+    assert lib.dfe_conv1x1_small_supported(B, Ci, Co, H, W) == 0
+    x, w, gy = G.Carved((B, Ci, H, W), 0, fill=torch.ones(B, Ci, H, W)), G.Carved((Co, Ci), 0, fill=torch.ones(Co, Ci)), G.Carved((B, Co, H, W), 0, fill=torch.ones(B, Co, H, W))
+    y, gx, gw = G.Carved((B, Co, H, W), 1), G.Carved((B, Ci, H, W), 2), G.Carved((Co, Ci), 3)
+    assert lib.dfe_conv1x1_small_fwd(_p(x), _p(w), None, ctypes.c_float(0.1), _p(y), B, Ci, Co, H, W, st) == -4
+    assert lib.dfe_conv1x1_small_bwd(_p(gy), _p(x), _p(w), _p(gx), _p(gw), B, Ci, Co, H, W, st) == -4
+    torch.cuda.synchronize()
+    assert all(c.untouched() and c.intact() for c in (y, gx, gw))

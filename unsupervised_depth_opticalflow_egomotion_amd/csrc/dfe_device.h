@@ -254,8 +254,6 @@ __device__ __forceinline__ void rigid_grid_d(const Proj& p, const Divisor dw, co
   if (!live_y) yn = 2.0f;
 }
 
-// Back-propagate (gU, gV) = dL/dU, dL/dV (and optionally gZ = dL/dZ) of one pixel to
-// depth and to the 12 camera sums (dL/db[3], dL/dA[9]) -- SURVEY.md A.3.
 // 1 / x for GRADIENT arithmetic (compared with a tolerance, never feeding a decision): v_rcp_f32 + one Newton step, ~1 ulp,
 // 3 instructions where the IEEE division takes ~10 (two of them quarter rate).  x must be a normal, non-zero float.
 __device__ __forceinline__ float rcp_nr(float x) {
@@ -263,12 +261,20 @@ __device__ __forceinline__ float rcp_nr(float x) {
   return __fmaf_rn(__fmaf_rn(-x, r, 1.0f), r, r);
 }
 
-__device__ __forceinline__ void project_backward(const Proj& p, float depth, float gU, float gV, float gZ,
+// Back-propagate (gU, gV) = dL/dU, dL/dV (and optionally gZ = dL/dZ) of one pixel to
+// depth and to the 12 camera sums (dL/db[3], dL/dA[9]) -- SURVEY.md A.3.
+// The depth gradient is NOT summed as gX q0 + gY q1 + gZr q2.  With X = q0 d + b0 and Z = q2 d + b2 the quotient rule's
+// q0 Z - X q2 is q0 b2 - b0 q2: the two d q0 q2 terms cancel exactly, and for a small translation they are the large ones, so
+// the three-term sum rounds values many times its result (found by the guarded float64 test: 7.4 units of 2^-24 max |g_depth|
+// at a pixel whose terms were -2.82 - 0.22 + 4.14).  dU/dd = (q0 b2 - b0 q2) / Z^2 has no such terms; gZ reaches d through
+// Z alone.  Under the clamp Z is a constant and the two remaining terms are the whole gradient.
+__device__ __forceinline__ void project_backward(const Camera& c, const Proj& p, float depth, float gU, float gV, float gZ,
                                                  float& gdepth, float acc[12]) {
   float invZ = rcp_nr(p.Z);
   float gX = gU * invZ, gY = gV * invZ;
   float gZr = p.clamped ? 0.0f : (gZ - (gU * p.U + gV * p.V) * invZ);
-  gdepth = gX * p.q0 + gY * p.q1 + gZr * p.q2;
+  const float a0 = __fmaf_rn(p.q0, c.b[2], -(c.b[0] * p.q2)), a1 = __fmaf_rn(p.q1, c.b[2], -(c.b[1] * p.q2));
+  gdepth = p.clamped ? (gX * p.q0 + gY * p.q1) : __fmaf_rn(gX * a0 + gY * a1, invZ, gZ * p.q2);
   acc[0] += gX; acc[1] += gY; acc[2] += gZr;
   float c0 = p.r0 * depth, c1 = p.r1 * depth, c2 = p.r2 * depth;
   acc[3] += gX * c0;  acc[4] += gX * c1;  acc[5] += gX * c2;
@@ -305,8 +311,12 @@ __device__ __forceinline__ void occ_weights(float dl, float dr, float& w_bwd, fl
   w_fwd = 1.0f - er / sum;
 }
 
-__device__ __forceinline__ float l2norm2(float a, float b) {  // torch.norm(p=2,dim=1) + 1e-12
-  return sqrtf(a * a + b * b) + 1e-12f;
+// torch.norm(p=2, dim=1) + 1e-12 of a two-channel tensor.  ATen's reduction (NormTwoOps, acc = acc + x * x, contracted by the
+// CPU build) evaluates sqrt(fma(b, b, a * a)) -- probed bit for bit (torch 2.10 CPU, 2380 of 2380 elements; the separately
+// rounded a * a + b * b differs in 8 % of them by one ulp, which reaches the dynamic score and, at the threshold, the mask).
+__device__ __forceinline__ float norm2_sq(float a, float b) { return __fmaf_rn(b, b, a * a); }
+__device__ __forceinline__ float l2norm2(float a, float b) {
+  return sqrtf(norm2_sq(a, b)) + 1e-12f;
 }
 
 // dynamic mask: ||diff||^2 < alpha (||flow||^2 + ||rigid||^2) + beta (model_geometry.py:701-707)

@@ -335,7 +335,7 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PB_ATTR k_geom_point_bwd(GeomDev
         aF[6] = dl2 * x1; aF[7] = dl2 * y1; aF[8] = dl2;
       }
       float gd;
-      project_backward(pr, dsp, gU, gV, gZ, gd, acc + d * PB_PER_DIR);
+      project_backward(cam, pr, dsp, gU, gV, gZ, gd, acc + d * PB_PER_DIR);
       gdisp += gd;
       if (d == 1) {
         // flow consistency: only the forward flow carries gradient (bwd is detached)
@@ -501,7 +501,7 @@ __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_bwd(GeomDev D, GeomBwd
         if (ly) gV = giy * sy * (2.0f / static_cast<float>(H - 1));
       }
       float gd;
-      project_backward(pr, dsp, gU, gV, gZ, gd, acc + d * PB_PER_DIR);
+      project_backward(cam, pr, dsp, gU, gV, gZ, gd, acc + d * PB_PER_DIR);
       gdisp += gd;
     }
     if (G.gdisp[1][s]) G.gdisp[1][s][o1] = gdisp;

@@ -137,8 +137,8 @@ __device__ __forceinline__ float sqrt_cr_full(float x) {
 
 // dyna_decision() with the short square roots (same bits for finite inputs)
 __device__ __forceinline__ bool dyna_decide(float fu, float fv, float ru, float rv, float du, float dv, float alpha, float beta) {
-  const float nf = sqrt_cr_full(fu * fu + fv * fv) + 1e-12f, nr = sqrt_cr_full(ru * ru + rv * rv) + 1e-12f;
-  const float nd = sqrt_cr_full(du * du + dv * dv) + 1e-12f;
+  const float nf = sqrt_cr_full(norm2_sq(fu, fv)) + 1e-12f, nr = sqrt_cr_full(norm2_sq(ru, rv)) + 1e-12f;
+  const float nd = sqrt_cr_full(norm2_sq(du, dv)) + 1e-12f;
   return (nd * nd) < (alpha * (nf * nf + nr * nr) + beta);
 }
 

@@ -512,7 +512,7 @@ __global__ void k_inverse_warp2_bwd(const float* __restrict__ img, const float* 
     float gV = ly ? giy * sy * (2.0f / static_cast<float>(H - 1)) : 0.0f;
     float gZ = g_cdepth ? g_cdepth[static_cast<long>(b) * HW + p] : 0.0f;
     float gd;
-    project_backward(pr, d, gU, gV, gZ, gd, acc);
+    project_backward(cam, pr, d, gU, gV, gZ, gd, acc);
     g_depth[static_cast<long>(b) * HW + p] = gd;
   }
   block_sum<12>(acc, red, partials + (static_cast<long>(b) * gridDim.x + blockIdx.x) * 12);
@@ -541,9 +541,10 @@ __global__ void k_rigid_flow_bwd(const float* __restrict__ depth, const Camera* 
   if (p < HW) {
     const int py = p / W, px = p - py * W;
     const float d = depth[static_cast<long>(b) * HW + p];
-    Proj pr = project(cams[b], px, py, d);
+    const Camera& cam = cams[b];
+    Proj pr = project(cam, px, py, d);
     float gd;
-    project_backward(pr, d, gout[static_cast<long>(b) * 2 * HW + p], gout[static_cast<long>(b) * 2 * HW + HW + p], 0.0f, gd, acc);
+    project_backward(cam, pr, d, gout[static_cast<long>(b) * 2 * HW + p], gout[static_cast<long>(b) * 2 * HW + HW + p], 0.0f, gd, acc);
     g_depth[static_cast<long>(b) * HW + p] = gd;
   }
   block_sum<12>(acc, red, partials + (static_cast<long>(b) * gridDim.x + blockIdx.x) * 12);
