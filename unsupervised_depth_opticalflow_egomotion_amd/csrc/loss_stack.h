@@ -2,6 +2,7 @@
 #pragma once
 #include "dfe_device.h"
 #include "dfe_internal.h"
+#include <type_traits>
 
 namespace dfe {
 
@@ -98,6 +99,31 @@ struct GeomDev {
 
 int geom_layout(const dfe_geom_args* a, GeomLayout* L);
 void geom_dev(const dfe_geom_args* a, const GeomLayout& L, GeomDev* D);
+int check_args(const dfe_geom_args* a, const GeomLayout& L, bool bwd);   // loss_stack_fwd.hip; both directions call it
+
+// ---- event timing of the two launch sequences (loss_stack_fwd.hip).  geom_fwd_impl / geom_bwd_impl record event 0 at
+// their start and one more at the end of each segment (DFE_MARK, over their locals ev, seg, st; ev may be null).
+constexpr int GEOM_MAX_SEGMENTS = DFE_GEOM_FWD_SEGMENTS > DFE_GEOM_BWD_SEGMENTS ? DFE_GEOM_FWD_SEGMENTS : DFE_GEOM_BWD_SEGMENTS;
+struct GeomTimed { int n; hipEvent_t ev[GEOM_MAX_SEGMENTS + 1]; };     // the handle of the _timed entry points
+typedef int (*GeomImpl)(const dfe_geom_args* a, void* stream, hipEvent_t* ev);
+int geom_profiled(GeomImpl impl, int n, const dfe_geom_args* a, void* stream, float* ms_host);
+int geom_timed(GeomImpl impl, int n, const dfe_geom_args* a, void* stream, void** handle);
+#define DFE_MARK() do { if (ev) (void)hipEventRecord(ev[++seg], st); } while (0)
+
+// the runtime number of scales as a compile-time one: f(std::integral_constant<int, NS>) with NS = S in 1..8 (above: 8)
+template <class F>
+inline void with_num_scales(int S, F&& f) {
+  switch (S) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
 
 // ---- rolling-window SSIM helpers (forward and backward kernels)
 struct RowSums { float v[15]; };   // per channel: sum x, y, xx, yy, xy over the 3 horizontal neighbours

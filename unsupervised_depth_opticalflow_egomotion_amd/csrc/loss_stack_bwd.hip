@@ -12,6 +12,10 @@
 //   k_geom_pose_finalize    fixed-order reduction + closed-form 3x3 chains -> grad_pose
 // No float atomics anywhere (the one scatter, of the optional depth-consistency term, adds 64-bit fixed-point
 // integers): gradients are bitwise reproducible run to run.
+// The three point kernels (k_geom_ / k_depth_ / k_flow_point_bwd) share the gradient pieces stated once above
+// k_geom_point_bwd: flow_warp_grad, flow_consis_grad, depth_consis_grad.  k_depth_ and k_flow_point_bwd find their pixel
+// with locate_pixel (loss_stack_exact.h); k_geom_point_bwd keeps its own prologue and its own reconstruction-gradient
+// loop (see the note above it).  Argument check, event timing and the scale-count dispatch come from loss_stack.h.
 #include "loss_stack_exact.h"
 #include "dfe_scatter.h"
 #include <cstdlib>
@@ -191,6 +195,70 @@ k_geom_ssim_bwd_roll(GeomDev D, GeomBwd G, int rigid) {
 // the rigid warps (G.gyr), and the depth-consistency term's gradient wrt the computed depth (the projection's Z), the
 // rigid coordinate (through the sampled source disparity) and the source disparity itself (bilinear scatter in 64-bit
 // fixed point, dfe_scatter.h: order-independent).
+//
+// The gradient pieces that more than one of the three kernels needs, each stated once.  What the kernels deliberately do
+// differently stays with them: the projection and grid variants (project_fast / rigid_grid_d / flow_coords_d and rcp_nr
+// in the geom kernel, the IEEE forms in the depth and flow kernels) and the weights l1c, gq and k they pass in.
+// The area-pyramid reconstruction loop stays written out in k_geom_point_bwd and k_depth_point_bwd: see below.
+
+// Flow warp of one direction at the tap (ix, iy): dL/d(flow) of the L1 term (weight l1c) and of the SSIM term (gw: its
+// gradient wrt the warped image at this pixel, plane stride N); zero where the warp is not kept.
+__device__ __forceinline__ void flow_warp_grad(const float* __restrict__ src, const float* __restrict__ gw, float ix, float iy,
+                                               int H, int W, int N, int ac, const float (&im)[3], float l1c, float& gfu, float& gfv) {
+  const Tap t = make_tap(ix, iy, H, W);
+  if (tap_cover(t) < 0.9999f) return;
+  float gix = 0.0f, giy = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const Corners q = load_corners(src + static_cast<long>(c) * N, t, W, H);
+    float dx, dy;
+    interp_grad(q, t, dx, dy);
+    const float g = gw[static_cast<long>(c) * N] + sgn(interp(q, t) - im[c]) * l1c;
+    gix += g * dx; giy += g * dy;
+  }
+  gfu = gix * flow_coord_scale(W, ac);
+  gfv = giy * flow_coord_scale(H, ac);
+}
+
+// Flow consistency: only the forward flow carries gradient (bwd is detached).  k = (1 - occlusion weight) x normaliser x
+// dL/d(loss), formed by the caller.
+__device__ __forceinline__ void flow_consis_grad(const float (&fu)[2], const float (&fv)[2], float k, float& gfu, float& gfv) {
+  if (k == 0.0f) return;
+  const float rf = sqrtf(fu[1] * fu[1] + fv[1] * fv[1]), nf = rf + 1e-12f;
+  const float nb = l2norm2(fu[0], fv[0]);
+  const float uu = fu[1] / nf, uv = fv[1] / nf;
+  const float au = sgn(uu + fu[0] / nb) * k, av = sgn(uv + fv[0] / nb) * k;
+  const float ir = (rf > 0.0f) ? 1.0f / (rf * nf * nf) : 0.0f, inf_ = rcp_nr(nf);     // nf >= 1e-12
+  gfu += au * (inf_ - fu[1] * fu[1] * ir) + av * (-fv[1] * fu[1] * ir);
+  gfv += au * (-fu[1] * fv[1] * ir) + av * (inf_ - fv[1] * fv[1] * ir);
+}
+
+// Depth consistency q = |cd - pd| / |cd + pd| clamped to [0,1] (gradient passes on the closed interval, like
+// torch.clamp), weight gq: gZ = d/d(cd), the rigid coordinate's share through the sampled source disparity `dsrc` into
+// (gix, giy), and d/d(that disparity) as a four-tap scatter in 64-bit fixed point into `gdq` (null: not wanted).
+__device__ __forceinline__ void depth_consis_grad(const float* __restrict__ dsrc, long long* gdq, const unsigned* scq_header,
+                                                  const Tap& t, int H, int W, float cd, float gq, float& gZ, float& gix, float& giy) {
+  const Corners qd = load_corners(dsrc, t, W, H);
+  const float v = interp(qd, t);
+  const float pd = (v >= 1e-3f || v != v) ? v : 1e-3f;
+  const float num = cd - pd, den = cd + pd, qv = fabsf(num) / fabsf(den);
+  if (!(qv >= 0.0f && qv <= 1.0f)) return;
+  const float a = sgn(num) / fabsf(den), bq = qv * sgn(den) / fabsf(den);
+  gZ = gq * (a - bq);                       // d q / d cd
+  const float gp = (v >= 1e-3f) ? gq * (-a - bq) : 0.0f;   // d q / d pd, cut by the clamp(min=1e-3)
+  float dx, dy;
+  interp_grad(qd, t, dx, dy);
+  gix += gp * dx; giy += gp * dy;
+  if (gdq && gp != 0.0f) {
+    long long* base = gdq + static_cast<long>(t.y0) * W + t.x0;
+    const float gs = gp * scatter_scale(*scq_header).to_fixed;
+    if (t.in_nw) fixed_add(base, to_fixed(gs, t.nw));
+    if (t.in_ne) fixed_add(base + 1, to_fixed(gs, t.ne));
+    if (t.in_sw) fixed_add(base + W, to_fixed(gs, t.sw));
+    if (t.in_se) fixed_add(base + W + 1, to_fixed(gs, t.se));
+  }
+}
+
 #ifndef DFE_PB_WPE
 #define DFE_PB_WPE 0             // 0: the compiler's own register budget (90 VGPRs = 5 waves per SIMD)
 #endif
@@ -199,6 +267,10 @@ k_geom_ssim_bwd_roll(GeomDev D, GeomBwd G, int rigid) {
 #else
 #define DFE_PB_ATTR
 #endif
+// k_geom_point_bwd<true> compiles at the scalar-register ceiling (106 SGPRs), where the number of scalar registers the
+// compiler spills to vector lanes moves with the kernel's text.  With locate_pixel in place of the prologue below it
+// spills 4 to 6 whatever else is folded, with the reconstruction loop behind a shared function 3, as written here 1
+// (profiles/loss_stack_point_refactor.txt, A2).  So the prologue and that loop stay written out in this kernel.
 template <bool DT>
 __global__ void __launch_bounds__(GS_BLOCK) DFE_PB_ATTR k_geom_point_bwd(GeomDev D, GeomT T, GeomBwd G) {
   __shared__ float red[PB_COUNT * 4 * (GS_BLOCK / 64)];
@@ -240,25 +312,9 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PB_ATTR k_geom_point_bwd(GeomDev
       {
         float ix, iy;
         flow_coords_d(px, py, fu[d], fv[d], H, W, D.ac, dw, dh, ix, iy);
-        Tap t = make_tap(ix, iy, H, W);
-        const float keep = (tap_cover(t) < 0.9999f) ? 0.0f : 1.0f;
-        if (keep != 0.0f) {
-          const float* src = D.pyr[d == 0 ? 0 : 2][s] + static_cast<long>(b) * 3 * N;
-          const float* gw = G.gw[s] + (static_cast<long>(d) * B + b) * 3 * N + p;
-          const float l1c = g_fp * (m_rig * cf[d * CF_PER_DIR + CF_RIG] + m_dyn * cf[d * CF_PER_DIR + CF_DYN]);
-          float gix = 0.0f, giy = 0.0f;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            Corners q = load_corners(src + static_cast<long>(c) * N, t, W, H);
-            const float wv = interp(q, t);
-            float dx, dy;
-            interp_grad(q, t, dx, dy);
-            const float g = gw[static_cast<long>(c) * N] + sgn(wv - im[c]) * l1c;
-            gix += g * dx; giy += g * dy;
-          }
-          gfu = gix * flow_coord_scale(W, D.ac);
-          gfv = giy * flow_coord_scale(H, D.ac);
-        }
+        const float l1c = g_fp * (m_rig * cf[d * CF_PER_DIR + CF_RIG] + m_dyn * cf[d * CF_PER_DIR + CF_DYN]);
+        flow_warp_grad(D.pyr[d == 0 ? 0 : 2][s] + static_cast<long>(b) * 3 * N, G.gw[s] + (static_cast<long>(d) * B + b) * 3 * N + p,
+                       ix, iy, H, W, N, D.ac, im, l1c, gfu, gfv);
       }
       // ---- rigid branch
       const Camera& cam = D.cams[(b * 2 + d) * D.S + s];
@@ -281,29 +337,9 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PB_ATTR k_geom_point_bwd(GeomDev
           gix += g * dx; giy += g * dy;
         }
         if (DT && (D.dt & DFE_DEPTH_TERM_CONSIS)) {
-          // q = |cd - pd| / |cd + pd| clamped to [0,1] (gradient passes on the closed interval, like torch.clamp)
-          const int fs = d == 0 ? 0 : 2;
-          const Corners qd = load_corners(D.disp[fs][s] + static_cast<long>(b) * N, t, W, H);
-          const float v = interp(qd, t);
-          const float pd = (v >= 1e-3f || v != v) ? v : 1e-3f, cd = pr.Z;
-          const float num = cd - pd, den = cd + pd, qv = fabsf(num) / fabsf(den);
-          if (qv >= 0.0f && qv <= 1.0f) {
-            const float gq = G.gl[DFE_LOSS_DEPTH_CONSIS * B + b] * 3.0f * cf[d * CF_PER_DIR + CF_DEPTH];   // 1 / (N n_tex)
-            const float a = sgn(num) / fabsf(den), bq = qv * sgn(den) / fabsf(den);
-            gZ = gq * (a - bq);                       // d q / d cd
-            const float gp = (v >= 1e-3f) ? gq * (-a - bq) : 0.0f;   // d q / d pd, cut by the clamp(min=1e-3)
-            float dx, dy;
-            interp_grad(qd, t, dx, dy);
-            gix += gp * dx; giy += gp * dy;
-            if (G.gdisp[fs][s] && gp != 0.0f) {
-              long long* base = G.gdq[fs >> 1][s] + static_cast<long>(b) * N + static_cast<long>(t.y0) * W + t.x0;
-              const float gs = gp * scatter_scale(*G.scq_header).to_fixed;
-              if (t.in_nw) fixed_add(base, to_fixed(gs, t.nw));
-              if (t.in_ne) fixed_add(base + 1, to_fixed(gs, t.ne));
-              if (t.in_sw) fixed_add(base + W, to_fixed(gs, t.sw));
-              if (t.in_se) fixed_add(base + W + 1, to_fixed(gs, t.se));
-            }
-          }
+          const float gq = G.gl[DFE_LOSS_DEPTH_CONSIS * B + b] * 3.0f * cf[d * CF_PER_DIR + CF_DEPTH];   // 1 / (N n_tex)
+          depth_consis_grad(D.disp[2 * d][s] + static_cast<long>(b) * N, G.gdisp[2 * d][s] ? G.gdq[d][s] + static_cast<long>(b) * N : nullptr,
+                            G.scq_header, t, H, W, pr.Z, gq, gZ, gix, giy);
         }
         const float sx = D.ac ? static_cast<float>(W - 1) / 2.0f : static_cast<float>(W) / 2.0f;
         const float sy = D.ac ? static_cast<float>(H - 1) / 2.0f : static_cast<float>(H) / 2.0f;
@@ -337,20 +373,7 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PB_ATTR k_geom_point_bwd(GeomDev
       float gd;
       project_backward(cam, pr, dsp, gU, gV, gZ, gd, acc + d * PB_PER_DIR);
       gdisp += gd;
-      if (d == 1) {
-        // flow consistency: only the forward flow carries gradient (bwd is detached)
-        const float inv = occ ? 0.0f : 1.0f;
-        const float k = inv * cf[CF_CONSIS] * g_fc;
-        if (k != 0.0f) {
-          const float rf = sqrtf(fu[1] * fu[1] + fv[1] * fv[1]), nf = rf + 1e-12f;
-          const float nb = l2norm2(fu[0], fv[0]);
-          const float uu = fu[1] / nf, uv = fv[1] / nf;
-          const float au = sgn(uu + fu[0] / nb) * k, av = sgn(uv + fv[0] / nb) * k;
-          const float ir = (rf > 0.0f) ? 1.0f / (rf * nf * nf) : 0.0f, inf_ = rcp_nr(nf);     // nf >= 1e-12
-          gfu += au * (inf_ - fu[1] * fu[1] * ir) + av * (-fv[1] * fu[1] * ir);
-          gfv += au * (-fu[1] * fv[1] * ir) + av * (inf_ - fv[1] * fv[1] * ir);
-        }
-      }
+      if (d == 1) flow_consis_grad(fu, fv, (occ ? 0.0f : 1.0f) * cf[CF_CONSIS] * g_fc, gfu, gfv);
       if (G.gflow[d][s]) { G.gflow[d][s][o2] = gfu; G.gflow[d][s][o2 + N] = gfv; }
     }
     if (G.gdisp[1][s]) G.gdisp[1][s][o1] = gdisp;
@@ -362,16 +385,10 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PB_ATTR k_geom_point_bwd(GeomDev
 // Model_flow: gradient wrt the flows of the weighted L1 (1-channel mean diff), the SSIM term (gw) and the flow
 // consistency (forward flow only); the soft weights are detached (model_flow.py:124).
 __global__ void __launch_bounds__(GS_BLOCK) k_flow_point_bwd(GeomDev D, GeomBwd G) {
-  const unsigned nblk_total = D.blk_start[D.S];
-  const unsigned blk = xcd_swizzle(blockIdx.x, nblk_total);
-  const int b = blockIdx.y, B = D.B;
-  const int s = find_scale(D.blk_start, D.S, blk);
-  const int H = D.H[s], W = D.W[s], N = D.N[s];
-  const int pl = (blk - D.blk_start[s]) * GS_BLOCK + threadIdx.x;
-  if (pl >= N) return;
-  unsigned upx, upy;
-  tile_pixel<DFE_PB_TILE>(static_cast<unsigned>(pl), W, H, upx, upy);      // wave footprint: loss_stack_exact.h
-  const int px = static_cast<int>(upx), py = static_cast<int>(upy), p = py * W + px;
+  const PixelAt at = locate_pixel<DFE_PB_TILE>(D);
+  if (!at.live) return;                                // no block sum in this kernel: the early return is legal here only
+  const int b = at.b, B = D.B, s = at.s, H = at.H, W = at.W, N = at.N;
+  const int px = static_cast<int>(at.px), py = static_cast<int>(at.py), p = static_cast<int>(at.pm);
   const long o3 = static_cast<long>(b) * 3 * N + p, o2 = static_cast<long>(b) * 2 * N + p;
   const float* it = D.pyr[1][s];
   const float im[3] = {it[o3], it[o3 + N], it[o3 + 2 * N]};
@@ -386,36 +403,9 @@ __global__ void __launch_bounds__(GS_BLOCK) k_flow_point_bwd(GeomDev D, GeomBwd 
     float gfu = 0.0f, gfv = 0.0f;
     float ix, iy;
     flow_coords(px, py, fu[d], fv[d], H, W, D.ac, ix, iy);
-    Tap t = make_tap(ix, iy, H, W);
-    const float keep = (tap_cover(t) < 0.9999f) ? 0.0f : 1.0f;
-    if (keep != 0.0f) {
-      const float* src = D.pyr[d == 0 ? 0 : 2][s] + static_cast<long>(b) * 3 * N;
-      const float* gw = G.gw[s] + (static_cast<long>(d) * B + b) * 3 * N + p;
-      const float l1c = g_fp * wgt * cf[d * CF_PER_DIR + CF_RIG];
-      float gix = 0.0f, giy = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        Corners q = load_corners(src + static_cast<long>(c) * N, t, W, H);
-        float dx, dy;
-        interp_grad(q, t, dx, dy);
-        const float g = gw[static_cast<long>(c) * N] + sgn(interp(q, t) - im[c]) * l1c;
-        gix += g * dx; giy += g * dy;
-      }
-      gfu = gix * flow_coord_scale(W, D.ac);
-      gfv = giy * flow_coord_scale(H, D.ac);
-    }
-    if (d == 1) {
-      const float k = (1.0f - wgt) * cf[CF_CONSIS] * g_fc;
-      if (k != 0.0f) {
-        const float rf = sqrtf(fu[1] * fu[1] + fv[1] * fv[1]), nf = rf + 1e-12f;
-        const float nb = l2norm2(fu[0], fv[0]);
-        const float uu = fu[1] / nf, uv = fv[1] / nf;
-        const float au = sgn(uu + fu[0] / nb) * k, av = sgn(uv + fv[0] / nb) * k;
-        const float ir = (rf > 0.0f) ? 1.0f / (rf * nf * nf) : 0.0f, inf_ = rcp_nr(nf);     // nf >= 1e-12
-        gfu += au * (inf_ - fu[1] * fu[1] * ir) + av * (-fv[1] * fu[1] * ir);
-        gfv += au * (-fu[1] * fv[1] * ir) + av * (inf_ - fv[1] * fv[1] * ir);
-      }
-    }
+    flow_warp_grad(D.pyr[d == 0 ? 0 : 2][s] + static_cast<long>(b) * 3 * N, G.gw[s] + (static_cast<long>(d) * B + b) * 3 * N + p,
+                   ix, iy, H, W, N, D.ac, im, g_fp * wgt * cf[d * CF_PER_DIR + CF_RIG], gfu, gfv);
+    if (d == 1) flow_consis_grad(fu, fv, (1.0f - wgt) * cf[CF_CONSIS] * g_fc, gfu, gfv);
     if (G.gflow[d][s]) { G.gflow[d][s][o2] = gfu; G.gflow[d][s][o2 + N] = gfv; }
   }
 }
@@ -425,19 +415,13 @@ __global__ void __launch_bounds__(GS_BLOCK) k_flow_point_bwd(GeomDev D, GeomBwd 
 template <bool DT>
 __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_bwd(GeomDev D, GeomBwd G) {
   __shared__ float red[PB_COUNT * 4 * (GS_BLOCK / 64)];
-  const unsigned nblk_total = D.blk_start[D.S];
-  const unsigned blk = xcd_swizzle(blockIdx.x, nblk_total);
-  const int b = blockIdx.y, B = D.B;
-  const int s = find_scale(D.blk_start, D.S, blk);
-  const int H = D.H[s], W = D.W[s], N = D.N[s];
-  const int pl = (blk - D.blk_start[s]) * GS_BLOCK + threadIdx.x;
+  const PixelAt at = locate_pixel<DFE_PB_TILE>(D);
+  const int b = at.b, B = D.B, s = at.s, H = at.H, W = at.W, N = at.N;
   float acc[PB_COUNT];
 #pragma unroll
   for (int i = 0; i < PB_COUNT; ++i) acc[i] = 0.0f;
-  if (pl < N) {
-    unsigned upx, upy;
-    tile_pixel<DFE_PB_TILE>(static_cast<unsigned>(pl), W, H, upx, upy);    // wave footprint: loss_stack_exact.h
-    const int px = static_cast<int>(upx), py = static_cast<int>(upy), p = py * W + px;
+  if (at.live) {
+    const int px = static_cast<int>(at.px), py = static_cast<int>(at.py), p = static_cast<int>(at.pm);
     const long o3 = static_cast<long>(b) * 3 * N + p, o1 = static_cast<long>(b) * N + p;
     const float* it = D.pyr[1][s];
     const float im[3] = {it[o3], it[o3 + N], it[o3 + 2 * N]};
@@ -471,30 +455,8 @@ __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_bwd(GeomDev D, GeomBwd
             gix += g * dx; giy += g * dy;
           }
         }
-        if (consis) {
-          const int fs = d == 0 ? 0 : 2;
-          const Corners qd = load_corners(D.disp[fs][s] + static_cast<long>(b) * N, t, W, H);
-          const float v = interp(qd, t);
-          const float pd = (v >= 1e-3f || v != v) ? v : 1e-3f, cd = pr.Z;
-          const float num = cd - pd, den = cd + pd, qv = fabsf(num) / fabsf(den);
-          if (qv >= 0.0f && qv <= 1.0f) {
-            const float gq = G.gl[DFE_LOSS_DEPTH_CONSIS * B + b] / static_cast<float>(N);
-            const float a = sgn(num) / fabsf(den), bq = qv * sgn(den) / fabsf(den);
-            gZ = gq * (a - bq);
-            const float gp = (v >= 1e-3f) ? gq * (-a - bq) : 0.0f;
-            float dx, dy;
-            interp_grad(qd, t, dx, dy);
-            gix += gp * dx; giy += gp * dy;
-            if (G.gdisp[fs][s] && gp != 0.0f) {
-              long long* base = G.gdq[fs >> 1][s] + static_cast<long>(b) * N + static_cast<long>(t.y0) * W + t.x0;
-              const float gs = gp * scatter_scale(*G.scq_header).to_fixed;
-              if (t.in_nw) fixed_add(base, to_fixed(gs, t.nw));
-              if (t.in_ne) fixed_add(base + 1, to_fixed(gs, t.ne));
-              if (t.in_sw) fixed_add(base + W, to_fixed(gs, t.sw));
-              if (t.in_se) fixed_add(base + W + 1, to_fixed(gs, t.se));
-            }
-          }
-        }
+        if (consis) depth_consis_grad(D.disp[2 * d][s] + static_cast<long>(b) * N, G.gdisp[2 * d][s] ? G.gdq[d][s] + static_cast<long>(b) * N : nullptr,
+                                      G.scq_header, t, H, W, pr.Z, G.gl[DFE_LOSS_DEPTH_CONSIS * B + b] / static_cast<float>(N), gZ, gix, giy);
         const float sx = D.ac ? static_cast<float>(W - 1) / 2.0f : static_cast<float>(W) / 2.0f;
         const float sy = D.ac ? static_cast<float>(H - 1) / 2.0f : static_cast<float>(H) / 2.0f;
         if (lx) gU = gix * sx * (2.0f / static_cast<float>(W - 1));
@@ -506,7 +468,7 @@ __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_bwd(GeomDev D, GeomBwd
     }
     if (G.gdisp[1][s]) G.gdisp[1][s][o1] = gdisp;
   }
-  block_sum<PB_COUNT>(acc, red, G.bpart + (static_cast<long>(b) * nblk_total + blk) * PB_COUNT);
+  block_sum<PB_COUNT>(acc, red, G.bpart + at.slot * PB_COUNT);
 }
 
 // ---------------------------------------------------------------------- flow smoothness backward
@@ -1073,11 +1035,8 @@ static int geom_bwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
   GeomLayout L;
   int rc = geom_layout(a, &L);
   if (rc != DFE_OK) return rc;
-  if (!a->workspace || !a->grad_losses || (a->mode != 2 && !a->pose)) return DFE_ERR_NULL;
-  if (!aligned16(a->workspace)) return DFE_ERR_DIMS;   // as the forward: include/dfe_hip.h
-  if (a->workspace_floats < L.total) return DFE_ERR_WORKSPACE;
-  for (int f = 0; f < 3; ++f) { if (!a->img[f]) return DFE_ERR_NULL; if (a->mode != 2) for (int s = 0; s < L.S; ++s) if (!a->disp[f][s]) return DFE_ERR_NULL; }
-  if (a->mode != 1) for (int d = 0; d < 2; ++d) for (int s = 0; s < L.S; ++s) if (!a->flow[d][s]) return DFE_ERR_NULL;
+  rc = check_args(a, L, true);
+  if (rc != DFE_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* ws = a->workspace;
   GeomDev D;
@@ -1101,7 +1060,6 @@ static int geom_bwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
       G.gdq[fi][s] = (G.rmw_all && s < L.S) ? scatter_acc(ws + L.o_scq) + (static_cast<long>(fi) * L.off_px[L.S] + L.off_px[s]) * L.B : nullptr;
   const unsigned nblk_total = L.blk_start[L.S];
   int seg = 0;
-#define DFE_MARK() do { if (ev) (void)hipEventRecord(ev[++seg], st); } while (0)
   if (ev) (void)hipEventRecord(ev[0], st);
   if (G.rmw_all) {   // the projected-depth scatter: zero accumulators + the analytic bound of what is added to them
     const int rc = scatter_begin_bound(ws + L.o_scq, 2L * L.B * L.off_px[L.S], st);
@@ -1162,16 +1120,7 @@ static int geom_bwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
   }
   {
     const dim3 g(L.dsm_units, 3 * L.B);
-    switch (L.S) {
-      case 1: k_geom_disp_smooth_bwd1<1><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-      case 2: k_geom_disp_smooth_bwd1<2><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-      case 3: k_geom_disp_smooth_bwd1<3><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-      case 4: k_geom_disp_smooth_bwd1<4><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-      case 5: k_geom_disp_smooth_bwd1<5><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-      case 6: k_geom_disp_smooth_bwd1<6><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-      case 7: k_geom_disp_smooth_bwd1<7><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-      default: k_geom_disp_smooth_bwd1<8><<<g, 64, 0, st>>>(D, G, L.dsm_strips); break;
-    }
+    with_num_scales(L.S, [&](auto ns) { k_geom_disp_smooth_bwd1<decltype(ns)::value><<<g, 64, 0, st>>>(D, G, L.dsm_strips); });
   }
   DFE_LAUNCH_CHECK();
   DFE_MARK();
@@ -1205,36 +1154,16 @@ static int geom_bwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
     DFE_LAUNCH_CHECK();
   }
   DFE_MARK();
-#undef DFE_MARK
   return DFE_OK;
 }
 
 extern "C" int dfe_geom_loss_bwd(const dfe_geom_args* a, void* stream) { return geom_bwd_impl(a, stream, nullptr); }
 
 extern "C" int dfe_geom_loss_bwd_profiled(const dfe_geom_args* a, void* stream, float* ms_host) {
-  if (!ms_host) return DFE_ERR_NULL;
-  hipEvent_t ev[DFE_GEOM_BWD_SEGMENTS + 1];
-  for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) return DFE_ERR_LAUNCH;
-  int rc = geom_bwd_impl(a, stream, ev);
-  if (rc == DFE_OK) {
-    (void)hipEventSynchronize(ev[DFE_GEOM_BWD_SEGMENTS]);
-    for (int i = 0; i < DFE_GEOM_BWD_SEGMENTS; ++i) (void)hipEventElapsedTime(&ms_host[i], ev[i], ev[i + 1]);
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  return rc;
+  return geom_profiled(geom_bwd_impl, DFE_GEOM_BWD_SEGMENTS, a, stream, ms_host);
 }
 
-// see dfe_geom_loss_fwd_timed; the handle layout is shared (DFE_GEOM_BWD_SEGMENTS <= DFE_GEOM_FWD_SEGMENTS)
-namespace { struct GeomTimedB { int n; hipEvent_t ev[DFE_GEOM_FWD_SEGMENTS + 1]; }; }
-
+// see dfe_geom_loss_fwd_timed: the same handle, collected by dfe_geom_timed_collect
 extern "C" int dfe_geom_loss_bwd_timed(const dfe_geom_args* a, void* stream, void** handle) {
-  if (!handle) return DFE_ERR_NULL;
-  static_assert(DFE_GEOM_BWD_SEGMENTS <= DFE_GEOM_FWD_SEGMENTS, "handle layout");
-  GeomTimedB* t = new GeomTimedB;
-  t->n = DFE_GEOM_BWD_SEGMENTS;
-  for (int i = 0; i <= t->n; ++i) if (hipEventCreate(&t->ev[i]) != hipSuccess) { delete t; return DFE_ERR_LAUNCH; }
-  const int rc = geom_bwd_impl(a, stream, t->ev);
-  if (rc != DFE_OK) { for (int i = 0; i <= t->n; ++i) (void)hipEventDestroy(t->ev[i]); delete t; return rc; }
-  *handle = t;
-  return DFE_OK;
+  return geom_timed(geom_bwd_impl, DFE_GEOM_BWD_SEGMENTS, a, stream, handle);
 }

@@ -95,6 +95,50 @@ __device__ __forceinline__ void tile_pixel(unsigned p, int W, int H, unsigned& p
   } else { py = p / Wu; px = p - py * Wu; }
 }
 
+// Where a thread of one of the point kernels works: grid x = blocks over all scales (XCD-swizzled), y = sample, one
+// pixel per thread.  RCP picks the tile_pixel overload (rW = GeomT::rW, the kernels that carry the table), TW the wave
+// footprint (DFE_PT_TILE / DFE_PB_TILE).  px, py, pm are meaningful only where `live`.  (k_geom_point_bwd writes the
+// same steps out: loss_stack_bwd.hip says why.)
+struct PixelAt {
+  int b, s, H, W, N;
+  long slot;                  // this block's row in the per-block partial sums: b * (blocks per sample) + block
+  unsigned px, py, pm;        // the pixel and its index in memory (py * W + px)
+  bool live;                  // false: the thread lies past the scale's last pixel
+};
+template <int TW, bool RCP = false>
+__device__ __forceinline__ PixelAt locate_pixel(const GeomDev& D, const float* rW = nullptr) {
+  PixelAt a;
+  const unsigned nblk_total = D.blk_start[D.S];
+  const unsigned blk = xcd_swizzle(blockIdx.x, nblk_total);
+  a.b = blockIdx.y;
+  a.s = find_scale(D.blk_start, D.S, blk);
+  a.H = D.H[a.s]; a.W = D.W[a.s]; a.N = D.N[a.s];
+  a.slot = static_cast<long>(a.b) * nblk_total + blk;
+  const unsigned p = (blk - D.blk_start[a.s]) * GS_BLOCK + threadIdx.x;
+  a.live = p < static_cast<unsigned>(a.N);
+  a.px = 0; a.py = 0;
+  if (a.live) {
+    if constexpr (RCP) tile_pixel<TW>(p, a.W, a.H, rW[a.s], a.px, a.py);
+    else tile_pixel<TW>(p, a.W, a.H, a.px, a.py);
+  }
+  a.pm = a.py * static_cast<unsigned>(a.W) + a.px;
+  return a;
+}
+
+// the three channel planes of an image (N4 = bytes per plane) sampled at one tap
+__device__ __forceinline__ void fast_sample3(const float* __restrict__ base, unsigned N4, const FastTap& t, float (&o)[3]) {
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) o[ch] = fast_sample(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + ch * N4), t);
+}
+
+// depth-consistency value clamp(|cd - pd| / |cd + pd|, 0, 1): cd = the projection's Z, pd = the source disparity plane
+// sampled at the rigid coordinate, clamp(min=1e-3) with NaN passing (inverse_warp.py:259-262)
+__device__ __forceinline__ float depth_consis_value(const float* __restrict__ disp, const FastTap& t, float cd) {
+  const float v = fast_sample(disp, t);
+  const float pd = (v >= 1e-3f || v != v) ? v : 1e-3f;
+  return fminf(fmaxf(fabsf(cd - pd) / fabsf(cd + pd), 0.0f), 1.0f);
+}
+
 // projection with the correctly rounded short sequences: X / Z and Y / Z share RN(1 / Z) (same bits as project())
 __device__ __forceinline__ Proj project_fast(const Camera& c, int x, int y, float depth) {
   Proj p;

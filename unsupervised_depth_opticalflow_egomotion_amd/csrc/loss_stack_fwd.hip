@@ -12,6 +12,9 @@
 //   k_geom_reduce_fwd + k_geom_assemble_fwd   fixed-order reduction of block partials -> loss vectors + normalisers
 // All (sample, scale) images are batched into each launch: scale 2 alone (13 k px) cannot fill
 // 256 CUs.  Partials are reduced in a fixed order (no float atomics): bitwise reproducible.
+// The three point kernels (k_geom_ / k_depth_ / k_flow_point_fwd) find their pixel with locate_pixel and share fast_sample3
+// and depth_consis_value (loss_stack_exact.h).  The host part at the end also holds what the backward file calls: the one
+// argument check of both directions and the event-timing layer of the _profiled / _timed entry points (loss_stack.h).
 #include "loss_stack_exact.h"
 #include "dfe_camera.h"
 #include <cstdint>
@@ -363,18 +366,11 @@ __global__ void __launch_bounds__(64) k_geom_area_coarse(PyrJobs jobs) {
 // pixels per thread with 8-byte streamed accesses (21 -> 10.5 streamed vector-memory instructions per pixel) was measured
 // and rejected: the two interleaved chains need 155 VGPRs (3 waves per SIMD): 59.9 vs 49.8 us in the loss_stack loop,
 // 40-41 vs 37.7 us inside the train step.
-// DFE_ABL: compile-time ablation switches of k_geom_point_fwd for the cost study of profiles/r03_point_fwd_ablation.md
-// (tools/ablate_point_fwd.sh builds one library per value; 0 = the shipped kernel, no code depends on it then).
-//   1 no block reductions   2 gathers at the pixel's own position (coherent)   4 no stores   8 rigid branch without gathers
-//  16 flow-warp branch without gathers   32 no epipolar / flow-consistency terms   64 no projection arithmetic
-// 128 no streamed source-pyramid loads
-#ifndef DFE_ABL
-#define DFE_ABL 0
-#endif
+// What each ingredient of k_geom_point_fwd costs (compile-time ablation study): profiles/r03_point_fwd_ablation.md.
 
 struct PointCtx {
-  int b, s, H, W, ac;
-  unsigned N4, p4;
+  int s, H, W, ac;
+  unsigned N4;
   float alpha, beta;
   const float *srcL, *srcR, *areaL, *areaR;   // block-uniform plane bases of this sample
   const float *dispL, *dispR;                  // DT: the source frames' disparity planes of this sample and scale
@@ -400,15 +396,11 @@ __device__ __forceinline__ void point_pixel(const PointCtx& c, int px, int py, c
   for (int d = 0; d < 2; ++d) {
     float ix, iy;
     flow_coords_d(px, py, in.fu[d], in.fv[d], H, W, c.ac, c.dw, c.dh, ix, iy);
-    FastTap t = make_fast_tap(ix, iy, H, W);
-    if (DFE_ABL & 2) { t.o0 = min(c.p4, c.N4 - 8u); t.o1 = t.o0; }
+    const FastTap t = make_fast_tap(ix, iy, H, W);
     const float keep = (fast_cover(t) < 0.9999f) ? 0.0f : 1.0f;
-    const float* src = d == 0 ? c.srcL : c.srcR;
+    fast_sample3(d == 0 ? c.srcL : c.srcR, c.N4, t, wv[d]);
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      if (DFE_ABL & 16) wv[d][ch] = (d == 0 ? in.sl[ch] : in.sr[ch]) * (keep + t.wa0);
-      else wv[d][ch] = fast_sample(reinterpret_cast<const float*>(reinterpret_cast<const char*>(src) + ch * c.N4), t) * keep;
-    }
+    for (int ch = 0; ch < 3; ++ch) wv[d][ch] *= keep;
     valid[d] = !(wv[d][0] == 0.0f && wv[d][1] == 0.0f && wv[d][2] == 0.0f);
     dif[d] = mean3_abs_diff(in.i0, in.i1, in.i2, wv[d][0], wv[d][1], wv[d][2]);
   }
@@ -418,24 +410,16 @@ __device__ __forceinline__ void point_pixel(const PointCtx& c, int px, int py, c
 #pragma unroll
   for (int d = 0; d < 2; ++d) {
     const Camera& cam = c.cam[d * c.cam_stride];
-    Proj pr;
-    if (DFE_ABL & 64) { pr.U = static_cast<float>(px) + in.dsp; pr.V = static_cast<float>(py) + in.dsp * cam.b[0]; pr.Z = 1.0f; }
-    else pr = project_fast(cam, px, py, in.dsp);
+    const Proj pr = project_fast(cam, px, py, in.dsp);
     const float ru = pr.U - static_cast<float>(px), rv = pr.V - static_cast<float>(py);
     const float du = fabsf(ru - in.fu[d]), dv = fabsf(rv - in.fv[d]);
     const bool dyna = dyna_decide(in.fu[d], in.fv[d], ru, rv, du, dv, c.alpha, c.beta);
     float xn, yn; bool lx, ly;
     rigid_grid_d(pr, c.dw, c.dh, xn, yn, lx, ly);
-    FastTap t = make_fast_tap(unnormalize(xn, W, c.ac), unnormalize(yn, H, c.ac), H, W);
-    if (DFE_ABL & 2) { t.o0 = min(c.p4, c.N4 - 8u); t.o1 = t.o0; }
-    const float* ar = d == 0 ? c.areaL : c.areaR;
+    const FastTap t = make_fast_tap(unnormalize(xn, W, c.ac), unnormalize(yn, H, c.ac), H, W);
     const float* sp = d == 0 ? in.sl : in.sr;
     float rec[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      if (DFE_ABL & 8) rec[ch] = sp[ch] * (t.wa0 + t.wb1);
-      else rec[ch] = fast_sample(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ar) + ch * c.N4), t);
-    }
+    fast_sample3(d == 0 ? c.areaL : c.areaR, c.N4, t, rec);
     const float e_rec = mean3_abs_diff(in.i0, in.i1, in.i2, rec[0], rec[1], rec[2]);
     const float e_src = mean3_abs_diff(in.i0, in.i1, in.i2, sp[0], sp[1], sp[2]);
     const bool tex = e_rec < e_src;
@@ -444,10 +428,7 @@ __device__ __forceinline__ void point_pixel(const PointCtx& c, int px, int py, c
     const float m_tex = tex ? m_rig : 0.0f;
     if (DT) {
       yr[d][0] = rec[0] * m_tex; yr[d][1] = rec[1] * m_tex; yr[d][2] = rec[2] * m_tex;
-      const float v = fast_sample(d == 0 ? c.dispL : c.dispR, t);
-      const float pd = (v >= 1e-3f || v != v) ? v : 1e-3f;
-      const float q = fabsf(pr.Z - pd) / fabsf(pr.Z + pd);
-      dc[d] = fminf(fmaxf(q, 0.0f), 1.0f) * m_tex;
+      dc[d] = depth_consis_value(d == 0 ? c.dispL : c.dispR, t, pr.Z) * m_tex;
     }
     const float l1_rec = (fabsf(in.i0 - rec[0]) + fabsf(in.i1 - rec[1])) + fabsf(in.i2 - rec[2]);
     const float l1_wrp = (fabsf(in.i0 - wv[d][0]) + fabsf(in.i1 - wv[d][1])) + fabsf(in.i2 - wv[d][2]);
@@ -456,7 +437,7 @@ __device__ __forceinline__ void point_pixel(const PointCtx& c, int px, int py, c
     a[PT_M_RIG] += m_rig;       a[PT_L1_RIG] += l1_wrp * m_rig;
     a[PT_M_DYN] += m_dyn;       a[PT_L1_DYN] += l1_wrp * m_dyn;
     a[PT_M_VO] += vo;
-    if (c.s == 0 && !(DFE_ABL & 32)) {
+    if (c.s == 0) {
       a[PT_FDIFF] += (du + dv) * m_rig;
       const Epi& e = c.epi[d];
       const float x1 = static_cast<float>(px), y1 = static_cast<float>(py);
@@ -474,7 +455,6 @@ __device__ __forceinline__ void point_pixel(const PointCtx& c, int px, int py, c
   }
   // flow consistency (model_geometry.py:195-210): |unit(fwd) + unit(bwd)| on (1 - occ_fwd)
   // loss-only: 1-ulp sqrt / reciprocal
-  if (DFE_ABL & 32) return;
   const float rf = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(in.fu[1] * in.fu[1] + in.fv[1] * in.fv[1]) + 1e-12f);
   const float rb = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(in.fu[0] * in.fu[0] + in.fv[0] * in.fv[0]) + 1e-12f);
   const float inv = occ[1] ? 0.0f : 1.0f;
@@ -539,30 +519,24 @@ __device__ __forceinline__ void point_block_sums(float (&acc)[PT_COUNT], float* 
 template <bool DT>
 // Register budget: left alone the compiler squeezes the kernel into 66 VGPRs (7 waves per SIMD); with the budget of 5
 // waves it takes 75 (6 waves) and schedules the loads further ahead: 51.8 -> 48.3 us in the loss_stack loop, 0.326 ->
-// 0.330 of the roofline inside the train step (round 3).  8 waves (64 VGPRs) spill: 62.8 us.
+// 0.330 of the roofline inside the train step (round 3).  8 waves (64 VGPRs) spill: 62.8 us.  (75 is round 3's figure;
+// the kernel has compiled to 74 since, the same 6-waves class.)
 #ifndef DFE_PT_WPE
 #define DFE_PT_WPE 5
 #endif
 #define DFE_PT_ATTR __attribute__((amdgpu_waves_per_eu(DFE_PT_WPE, DFE_PT_WPE)))
 __global__ void __launch_bounds__(GS_BLOCK) DFE_PT_ATTR k_geom_point_fwd(GeomDev D, GeomT T, float* __restrict__ part, float* __restrict__ part2) {
   __shared__ float red[PT_COUNT * 4 * (GS_BLOCK / 64)];
-  const unsigned nblk_total = D.blk_start[D.S];
-  const unsigned blk = xcd_swizzle(blockIdx.x, nblk_total);
-  const int b = blockIdx.y;
-  const int s = find_scale(D.blk_start, D.S, blk);
-  const int H = D.H[s], W = D.W[s], N = D.N[s];
-  const unsigned p = (blk - D.blk_start[s]) * GS_BLOCK + threadIdx.x;
+  const PixelAt at = locate_pixel<DFE_PT_TILE, true>(D, T.rW);    // a wave covers a 16 x 4 pixel tile (loss_stack_exact.h)
+  const int b = at.b, s = at.s, N = at.N;
   float acc[PT_COUNT];
 #pragma unroll
   for (int i = 0; i < PT_COUNT; ++i) acc[i] = 0.0f;
   float dc[2] = {0.0f, 0.0f};
-  if (p < static_cast<unsigned>(N)) {
-    unsigned px, py;
-    tile_pixel<DFE_PT_TILE>(p, W, H, T.rW[s], px, py);      // a wave covers a 16 x 4 pixel tile (loss_stack_exact.h)
-    const unsigned pm = py * static_cast<unsigned>(W) + px;   // the pixel this thread computes (index in memory)
-    const unsigned p4 = pm * 4u, N4 = static_cast<unsigned>(N) * 4u;
+  if (at.live) {
+    const unsigned p4 = at.pm * 4u, N4 = static_cast<unsigned>(N) * 4u;
     PointCtx c;
-    c.b = b; c.s = s; c.H = H; c.W = W; c.ac = D.ac; c.N4 = N4; c.p4 = p4; c.alpha = D.alpha; c.beta = D.beta;
+    c.s = s; c.H = at.H; c.W = at.W; c.ac = D.ac; c.N4 = N4; c.alpha = D.alpha; c.beta = D.beta;
     c.srcL = D.pyr[0][s] + static_cast<long>(b) * 3 * N; c.srcR = D.pyr[2][s] + static_cast<long>(b) * 3 * N;
     c.areaL = D.area[0][s] + static_cast<long>(b) * 3 * N; c.areaR = D.area[1][s] + static_cast<long>(b) * 3 * N;
     c.cam = D.cams + (b * 2) * D.S + s; c.cam_stride = D.S; c.epi = D.epi + b * 2;
@@ -575,16 +549,11 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PT_ATTR k_geom_point_fwd(GeomDev
     in.i0 = ldb(it, p4); in.i1 = ldb(it, p4 + N4); in.i2 = ldb(it, p4 + 2 * N4);
     in.fu[0] = ldb(flb, p4); in.fv[0] = ldb(flb, p4 + N4); in.fu[1] = ldb(flf, p4); in.fv[1] = ldb(flf, p4 + N4);
     in.dsp = ldb(D.disp[1][s] + static_cast<long>(b) * N, p4);
-    if (DFE_ABL & 128) { in.sl[0] = in.i1; in.sl[1] = in.i2; in.sl[2] = in.i0; in.sr[0] = in.i2; in.sr[1] = in.i0; in.sr[2] = in.i1; }
-    else {
-      in.sl[0] = ldb(c.srcL, p4); in.sl[1] = ldb(c.srcL, p4 + N4); in.sl[2] = ldb(c.srcL, p4 + 2 * N4);
-      in.sr[0] = ldb(c.srcR, p4); in.sr[1] = ldb(c.srcR, p4 + N4); in.sr[2] = ldb(c.srcR, p4 + 2 * N4);
-    }
+    in.sl[0] = ldb(c.srcL, p4); in.sl[1] = ldb(c.srcL, p4 + N4); in.sl[2] = ldb(c.srcL, p4 + 2 * N4);
+    in.sr[0] = ldb(c.srcR, p4); in.sr[1] = ldb(c.srcR, p4 + N4); in.sr[2] = ldb(c.srcR, p4 + 2 * N4);
     float yw[2][3], yr[2][3];
     unsigned bits;
-    point_pixel<DT>(c, static_cast<int>(px), static_cast<int>(py), in, yw, bits, acc, yr, dc);
-    if (DFE_ABL & 4) { if (yw[0][0] + yw[0][1] + yw[0][2] + yw[1][0] + yw[1][1] + yw[1][2] == 1234.5f) D.mask[s][0] = 1; }
-    else
+    point_pixel<DT>(c, static_cast<int>(at.px), static_cast<int>(at.py), in, yw, bits, acc, yr, dc);
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
       float* ywp = D.yw[s] + (static_cast<long>(d) * D.B + b) * 3 * N;
@@ -596,18 +565,10 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PT_ATTR k_geom_point_fwd(GeomDev
         for (int ch = 0; ch < 3; ++ch) stb(yrp, p4 + ch * N4, yr[d][ch]);
       }
     }
-    if (!(DFE_ABL & 4)) (D.mask[s] + static_cast<long>(b) * N)[pm] = static_cast<unsigned char>(bits);
-    else if (bits == 0x12345u) D.mask[s][1] = 1;
+    (D.mask[s] + static_cast<long>(b) * N)[at.pm] = static_cast<unsigned char>(bits);
   }
-  if (DFE_ABL & 1) {
-    float tot = 0.0f;
-#pragma unroll
-    for (int i = 0; i < PT_COUNT; ++i) tot += acc[i];
-    if (tot == 1234.5f) part[0] = tot;
-    return;
-  }
-  point_block_sums(acc, red, part + (static_cast<long>(b) * nblk_total + blk) * PT_COUNT);
-  if (DT) block_sum<2>(dc, red, part2 + (static_cast<long>(b) * nblk_total + blk) * 2);
+  point_block_sums(acc, red, part + at.slot * PT_COUNT);
+  if (DT) block_sum<2>(dc, red, part2 + at.slot * 2);
 }
 
 // ---------------------------------------------------------------------- depth-only pointwise forward
@@ -618,20 +579,14 @@ __global__ void __launch_bounds__(GS_BLOCK) DFE_PT_ATTR k_geom_point_fwd(GeomDev
 template <bool DT>
 __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_fwd(GeomDev D, float* __restrict__ part, float* __restrict__ part2) {
   __shared__ float red[PT_COUNT * 4 * (GS_BLOCK / 64)];
-  const unsigned nblk_total = D.blk_start[D.S];
-  const unsigned blk = xcd_swizzle(blockIdx.x, nblk_total);
-  const int b = blockIdx.y;
-  const int s = find_scale(D.blk_start, D.S, blk);
-  const int H = D.H[s], W = D.W[s], N = D.N[s];
-  const unsigned pl = (blk - D.blk_start[s]) * GS_BLOCK + threadIdx.x;
+  const PixelAt at = locate_pixel<DFE_PT_TILE>(D);
+  const int b = at.b, s = at.s, H = at.H, W = at.W, N = at.N;
   float acc[PT_COUNT];
 #pragma unroll
   for (int i = 0; i < PT_COUNT; ++i) acc[i] = 0.0f;
   float dc[2] = {0.0f, 0.0f};
-  if (pl < static_cast<unsigned>(N)) {
-    unsigned px, py;
-    tile_pixel<DFE_PT_TILE>(pl, W, H, px, py);               // wave footprint: loss_stack_exact.h
-    const unsigned p = py * static_cast<unsigned>(W) + px;
+  if (at.live) {
+    const unsigned px = at.px, py = at.py, p = at.pm;
     const unsigned p4 = p * 4u, N4 = static_cast<unsigned>(N) * 4u;
     const float* it = D.pyr[1][s] + static_cast<long>(b) * 3 * N;
     const float i0 = ldb(it, p4), i1 = ldb(it, p4 + N4), i2 = ldb(it, p4 + 2 * N4);
@@ -646,10 +601,8 @@ __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_fwd(GeomDev D, float* 
       rigid_grid_d(pr, dw, dh, xn, yn, lx, ly);
       const bool valid = fmaxf(fabsf(xn), fabsf(yn)) <= 1.0f;
       const FastTap t = make_fast_tap(unnormalize(xn, W, D.ac), unnormalize(yn, H, D.ac), H, W);
-      const float* ar = D.area[d][s] + static_cast<long>(b) * 3 * N;
       float rec[3];
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) rec[ch] = fast_sample(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ar) + ch * N4), t);
+      fast_sample3(D.area[d][s] + static_cast<long>(b) * 3 * N, N4, t, rec);
       const float* sp = D.pyr[d == 0 ? 0 : 2][s] + static_cast<long>(b) * 3 * N;
       const bool tex = mean3_abs_diff(i0, i1, i2, rec[0], rec[1], rec[2]) < mean3_abs_diff(i0, i1, i2, ldb(sp, p4), ldb(sp, p4 + N4), ldb(sp, p4 + 2 * N4));
       const float m = (valid && tex) ? 1.0f : 0.0f;
@@ -662,15 +615,13 @@ __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_fwd(GeomDev D, float* 
 #pragma unroll
           for (int ch = 0; ch < 3; ++ch) stb(yrp, p4 + ch * N4, rec[ch] * m);
         }
-        const float v = fast_sample(D.disp[d == 0 ? 0 : 2][s] + static_cast<long>(b) * N, t);
-        const float pd = (v >= 1e-3f || v != v) ? v : 1e-3f;
-        dc[d] = fminf(fmaxf(fabsf(pr.Z - pd) / fabsf(pr.Z + pd), 0.0f), 1.0f);
+        dc[d] = depth_consis_value(D.disp[d == 0 ? 0 : 2][s] + static_cast<long>(b) * N, t, pr.Z);
       }
     }
     (D.mask[s] + static_cast<long>(b) * N)[p] = static_cast<unsigned char>(bits);
   }
-  block_sum<PT_COUNT>(acc, red, part + (static_cast<long>(b) * nblk_total + blk) * PT_COUNT);
-  if (DT) block_sum<2>(dc, red, part2 + (static_cast<long>(b) * nblk_total + blk) * 2);
+  block_sum<PT_COUNT>(acc, red, part + at.slot * PT_COUNT);
+  if (DT) block_sum<2>(dc, red, part2 + at.slot * 2);
 }
 
 // ---------------------------------------------------------------------- flow-only pointwise forward
@@ -679,19 +630,13 @@ __global__ void __launch_bounds__(GS_BLOCK) k_depth_point_fwd(GeomDev D, float* 
 // consistency on (1 - weight_fwd).  Writes the float weights and the weighted warped images.
 __global__ void __launch_bounds__(GS_BLOCK) k_flow_point_fwd(GeomDev D, float* __restrict__ part) {
   __shared__ float red[PT_COUNT * 4 * (GS_BLOCK / 64)];
-  const unsigned nblk_total = D.blk_start[D.S];
-  const unsigned blk = xcd_swizzle(blockIdx.x, nblk_total);
-  const int b = blockIdx.y;
-  const int s = find_scale(D.blk_start, D.S, blk);
-  const int H = D.H[s], W = D.W[s], N = D.N[s];
-  const unsigned pl = (blk - D.blk_start[s]) * GS_BLOCK + threadIdx.x;
+  const PixelAt at = locate_pixel<DFE_PT_TILE>(D);
+  const int b = at.b, s = at.s, H = at.H, W = at.W, N = at.N;
   float acc[PT_COUNT];
 #pragma unroll
   for (int i = 0; i < PT_COUNT; ++i) acc[i] = 0.0f;
-  if (pl < static_cast<unsigned>(N)) {
-    unsigned px, py;
-    tile_pixel<DFE_PT_TILE>(pl, W, H, px, py);               // wave footprint: loss_stack_exact.h
-    const unsigned p = py * static_cast<unsigned>(W) + px;
+  if (at.live) {
+    const unsigned px = at.px, py = at.py, p = at.pm;
     const unsigned p4 = p * 4u, N4 = static_cast<unsigned>(N) * 4u;
     const float* it = D.pyr[1][s] + static_cast<long>(b) * 3 * N;
     const float i0 = ldb(it, p4), i1 = ldb(it, p4 + N4), i2 = ldb(it, p4 + 2 * N4);
@@ -705,9 +650,9 @@ __global__ void __launch_bounds__(GS_BLOCK) k_flow_point_fwd(GeomDev D, float* _
       flow_coords_d(px, py, fu[d], fv[d], H, W, D.ac, dw, dh, ix, iy);
       const FastTap t = make_fast_tap(ix, iy, H, W);
       const float keep = (fast_cover(t) < 0.9999f) ? 0.0f : 1.0f;
-      const float* src = D.pyr[d == 0 ? 0 : 2][s] + static_cast<long>(b) * 3 * N;
+      fast_sample3(D.pyr[d == 0 ? 0 : 2][s] + static_cast<long>(b) * 3 * N, N4, t, wv[d]);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) wv[d][c] = fast_sample(reinterpret_cast<const float*>(reinterpret_cast<const char*>(src) + c * N4), t) * keep;
+      for (int c = 0; c < 3; ++c) wv[d][c] *= keep;
       vld[d] = (wv[d][0] == 0.0f && wv[d][1] == 0.0f && wv[d][2] == 0.0f) ? 0.0f : 1.0f;
       dif[d] = mean3_abs_diff(i0, i1, i2, wv[d][0], wv[d][1], wv[d][2]);
     }
@@ -729,7 +674,7 @@ __global__ void __launch_bounds__(GS_BLOCK) k_flow_point_fwd(GeomDev D, float* _
     acc[PT_INV] = inv;
     acc[PT_CONSIS] = (fabsf(fu[1] / nf + fu[0] / nb) + fabsf(fv[1] / nf + fv[0] / nb)) * inv;
   }
-  block_sum<PT_COUNT>(acc, red, part + (static_cast<long>(b) * nblk_total + blk) * PT_COUNT);
+  block_sum<PT_COUNT>(acc, red, part + at.slot * PT_COUNT);
 }
 
 // ---------------------------------------------------------------------- SSIM forward (stage P), rolling window
@@ -1087,15 +1032,16 @@ __global__ void k_geom_assemble_fwd(GeomDev D, const float* __restrict__ sums, c
   losses[DFE_LOSS_DEPTH_CONSIS * B + b] = static_cast<float>(l_dcs);
 }
 
-}  // namespace dfe
-
-using namespace dfe;
-
-static int check_args(const dfe_geom_args* a, const GeomLayout& L, bool bwd) {
+// ---------------------------------------------------------------------- host: argument check, event timing
+// The checks of both directions in the order each has always made them.  What only one direction enforces stands behind
+// `bwd`: the backward asks for grad_losses and the pose (before the alignment test) and for neither K, K_inv, losses nor
+// the grid bound on B; the forward asks for those.
+int check_args(const dfe_geom_args* a, const GeomLayout& L, bool bwd) {
   if (!a->workspace) return DFE_ERR_NULL;
+  if (bwd && (!a->grad_losses || (a->mode != 2 && !a->pose))) return DFE_ERR_NULL;
   if (!aligned16(a->workspace)) return DFE_ERR_DIMS;   // the memory contract of include/dfe_hip.h
-  if (a->mode != 2 && (!a->pose || !a->K)) return DFE_ERR_NULL;
-  if (a->mode == 0 && !a->K_inv) return DFE_ERR_NULL;
+  if (!bwd && a->mode != 2 && (!a->pose || !a->K)) return DFE_ERR_NULL;
+  if (!bwd && a->mode == 0 && !a->K_inv) return DFE_ERR_NULL;
   if (a->workspace_floats < L.total) return DFE_ERR_WORKSPACE;
   for (int f = 0; f < 3; ++f) {
     if (!a->img[f]) return DFE_ERR_NULL;
@@ -1103,10 +1049,40 @@ static int check_args(const dfe_geom_args* a, const GeomLayout& L, bool bwd) {
   }
   if (a->mode != 1) for (int d = 0; d < 2; ++d) for (int s = 0; s < L.S; ++s) if (!a->flow[d][s]) return DFE_ERR_NULL;
   if (!bwd && !a->losses) return DFE_ERR_NULL;
-  if (bwd && !a->grad_losses) return DFE_ERR_NULL;
-  if (a->B > 21845) return DFE_ERR_DIMS;   // grid.y carries up to 3*B (frames x samples) <= 65535
+  if (!bwd && a->B > 21845) return DFE_ERR_DIMS;   // grid.y carries up to 3*B (frames x samples) <= 65535
   return DFE_OK;
 }
+
+// impl under n + 1 events, read out at once (the call synchronises on the last event)
+int geom_profiled(GeomImpl impl, int n, const dfe_geom_args* a, void* stream, float* ms_host) {
+  if (!ms_host) return DFE_ERR_NULL;
+  hipEvent_t ev[GEOM_MAX_SEGMENTS + 1];
+  for (int i = 0; i <= n; ++i) if (hipEventCreate(&ev[i]) != hipSuccess) return DFE_ERR_LAUNCH;
+  const int rc = impl(a, stream, ev);
+  if (rc == DFE_OK) {
+    (void)hipEventSynchronize(ev[n]);
+    for (int i = 0; i < n; ++i) (void)hipEventElapsedTime(&ms_host[i], ev[i], ev[i + 1]);
+  }
+  for (int i = 0; i <= n; ++i) (void)hipEventDestroy(ev[i]);
+  return rc;
+}
+
+// Deferred read-out: events are recorded in stream order with no host synchronisation, so the launches can be
+// timed inside a running training step; dfe_geom_timed_collect waits for the last event of that call only.
+int geom_timed(GeomImpl impl, int n, const dfe_geom_args* a, void* stream, void** handle) {
+  if (!handle) return DFE_ERR_NULL;
+  GeomTimed* t = new GeomTimed;
+  t->n = n;
+  for (int i = 0; i <= t->n; ++i) if (hipEventCreate(&t->ev[i]) != hipSuccess) { delete t; return DFE_ERR_LAUNCH; }
+  const int rc = impl(a, stream, t->ev);
+  if (rc != DFE_OK) { for (int i = 0; i <= t->n; ++i) (void)hipEventDestroy(t->ev[i]); delete t; return rc; }
+  *handle = t;
+  return DFE_OK;
+}
+
+}  // namespace dfe
+
+using namespace dfe;
 
 
 // The two pyramid decisions of the forward, stated once: geom_fwd_impl launches by them and dfe_geom_plan reports them.
@@ -1182,7 +1158,6 @@ static int geom_fwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
   GeomT T{};
   tile_dev(L, &T);
   int seg = 0;
-#define DFE_MARK() do { if (ev) (void)hipEventRecord(ev[++seg], st); } while (0)
   if (ev) (void)hipEventRecord(ev[0], st);
   // cameras: downscale = H / H_s as the reference computes it (float division of ints)
   float downs[DFE_MAX_SCALES];
@@ -1291,16 +1266,7 @@ static int geom_fwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
   if (a->mode != 2) {
     const dim3 g(L.dsm_units, 3 * L.B);
     float* dp = ws + L.o_dpart;
-    switch (L.S) {
-      case 1: k_geom_disp_smooth_fwd<1><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-      case 2: k_geom_disp_smooth_fwd<2><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-      case 3: k_geom_disp_smooth_fwd<3><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-      case 4: k_geom_disp_smooth_fwd<4><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-      case 5: k_geom_disp_smooth_fwd<5><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-      case 6: k_geom_disp_smooth_fwd<6><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-      case 7: k_geom_disp_smooth_fwd<7><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-      default: k_geom_disp_smooth_fwd<8><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); break;
-    }
+    with_num_scales(L.S, [&](auto ns) { k_geom_disp_smooth_fwd<decltype(ns)::value><<<g, 64, 0, st>>>(D, dp, L.dsm_strips); });
   }
   DFE_LAUNCH_CHECK();
   DFE_MARK();
@@ -1315,38 +1281,17 @@ static int geom_fwd_impl(const dfe_geom_args* a, void* stream, hipEvent_t* ev) {
                                                       ws + L.o_coef, a->losses);
   DFE_LAUNCH_CHECK();
   DFE_MARK();
-#undef DFE_MARK
   return DFE_OK;
 }
 
 int dfe_geom_loss_fwd(const dfe_geom_args* a, void* stream) { return geom_fwd_impl(a, stream, nullptr); }
 
 int dfe_geom_loss_fwd_profiled(const dfe_geom_args* a, void* stream, float* ms_host) {
-  if (!ms_host) return DFE_ERR_NULL;
-  hipEvent_t ev[DFE_GEOM_FWD_SEGMENTS + 1];
-  for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) return DFE_ERR_LAUNCH;
-  int rc = geom_fwd_impl(a, stream, ev);
-  if (rc == DFE_OK) {
-    (void)hipEventSynchronize(ev[DFE_GEOM_FWD_SEGMENTS]);
-    for (int i = 0; i < DFE_GEOM_FWD_SEGMENTS; ++i) (void)hipEventElapsedTime(&ms_host[i], ev[i], ev[i + 1]);
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  return rc;
+  return geom_profiled(geom_fwd_impl, DFE_GEOM_FWD_SEGMENTS, a, stream, ms_host);
 }
 
-// Deferred read-out: events are recorded in stream order with no host synchronisation, so the launches can be
-// timed inside a running training step; dfe_geom_timed_collect waits for the last event of that call only.
-struct GeomTimed { int n; hipEvent_t ev[DFE_GEOM_FWD_SEGMENTS + 1]; };
-
 int dfe_geom_loss_fwd_timed(const dfe_geom_args* a, void* stream, void** handle) {
-  if (!handle) return DFE_ERR_NULL;
-  GeomTimed* t = new GeomTimed;
-  t->n = DFE_GEOM_FWD_SEGMENTS;
-  for (int i = 0; i <= t->n; ++i) if (hipEventCreate(&t->ev[i]) != hipSuccess) { delete t; return DFE_ERR_LAUNCH; }
-  const int rc = geom_fwd_impl(a, stream, t->ev);
-  if (rc != DFE_OK) { for (int i = 0; i <= t->n; ++i) (void)hipEventDestroy(t->ev[i]); delete t; return rc; }
-  *handle = t;
-  return DFE_OK;
+  return geom_timed(geom_fwd_impl, DFE_GEOM_FWD_SEGMENTS, a, stream, handle);
 }
 
 int dfe_geom_timed_collect(void* handle, float* ms_host) {
