@@ -714,6 +714,50 @@ int dfe_geom_loss_fwd_timed(const dfe_geom_args* args, void* stream, void** hand
 int dfe_geom_loss_bwd_timed(const dfe_geom_args* args, void* stream, void** handle);
 int dfe_geom_timed_collect(void* handle, float* ms_host);
 
+/* ---- evaluation metrics on a device-resident set (evaluate_flow.py:85-174, evaluate_depth.py:13-52, evaluation_utils.py:11-32)
+ * A set of N samples of differing sizes lies in planes padded to [N,Hmax,Wmax] (Wmax a multiple of 4, the planes on 16 bytes:
+ * DFE_ERR_DIMS otherwise) with an int table per sample: flow `dims` [N,2] = H, W; depth `dims` [N,6] = H, W and the crop box
+ * y0, y1, x0, x1 (half open, computed by the host as evaluate_depth.py does).  A call takes a batch of n <= 1024 predictions at
+ * the training size (h, w) for the set rows first .. first+n-1 and writes one float64 record per sample to records[0 .. n).
+ * The prediction is resized to (H_i, W_i) bilinearly with half-pixel centres and edge replication: the source coordinate in
+ * double, its weight rounded to fp32, top = a (1 - wx) + b wx, bot likewise, top (1 - wy) + bot wy in fp32.  Per-pixel
+ * arithmetic is the reference's in fp32; every sum is in double and added in an order fixed by sample, block and thread index,
+ * so a record does not depend on the batch it ran in, the stream or the run.  The only atomics are integer adds on histogram
+ * bins.  The size table is read on the device and clamped to the planes: no entry can carry an access outside them.  Padding
+ * (columns >= W_i, rows >= H_i) may hold anything; it reaches no sum.
+ *
+ * dfe_eval_flow: pred [n,2,h,w]; gt_u, gt_v fp32 planes; flags a byte plane, bit 0 valid, bit 1 noc, bit 2 moving.  Each tap is
+ *   scaled by fl32(W_i / w) (u) or fl32(H_i / h) (v) before the resize; epe = sqrt(du^2 + dv^2); an outlier is
+ *   epe > 3 and epe / max(sqrt(u^2 + v^2), 1e-10) > 0.05.  Record, dfe_eval_flow_record_doubles() = 16 doubles:
+ *     0 sum epe valid   1 sum epe noc   2 sum epe (valid - noc)   3 sum epe valid mv   4 sum epe valid (1 - mv)
+ *     5 sum valid       6 sum noc       7 sum (valid - noc): a pixel with noc = 1, valid = 0 counts -1, as in the reference
+ *     8 outliers under valid   9 under valid mv   10 under valid (1 - mv)   11 sum valid mv   12 sum valid (1 - mv)   13-15 zero
+ *   Two launches: blocks -> ws (dfe_eval_flow_ws_bytes(n) bytes, 8-byte aligned, no initialisation), then the blocks of a sample
+ *   in index order -> its record.
+ * dfe_eval_flow_finish: the records of a whole task -> table[8] = epe, epe_noc, epe_occ, err_rate, epe_move, epe_static,
+ *   move_err_rate, static_err_rate: the ratio per sample (the occ denominator clamped to >= 1), the mean over the samples in
+ *   index order, in double; the last four are 0 without has_moving (eval_flow_avg without moving masks).
+ * dfe_eval_depth: disp [n,1,h,w]; gt one fp32 plane.  mask = gt > min_depth and gt < max_depth inside the crop box;
+ *   pred = 1 / (resize(disp) + 1e-4), written to the workspace for the masked pixels only and read from there by the later
+ *   passes; the medians of gt[mask] and pred[mask] in numpy's sense (the mean of the two middle values for an even count) by an
+ *   exact radix select over the bit patterns (positive floats order as unsigned integers): per 8-bit digit a histogram launch
+ *   (an LDS histogram per block, folded into a per-sample global integer histogram) and a pick launch, both middle ranks of both
+ *   planes carried through the same four passes; then pred *= med_gt / med_pred, both clamped to [min_depth, max_depth], and
+ *   the seven sums.  Record, dfe_eval_depth_record_doubles() = 10 doubles: abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3,
+ *   median(gt[mask]), median(pred[mask]) (each an fp32 value), the masked count.  An empty mask gives NaN metrics.
+ *   ws: dfe_eval_depth_ws_bytes(n, Hmax, Wmax) bytes on 16 bytes, no initialisation; n planes of pred first.  All samples of the
+ *   batch run in one grid (blocks per sample, n); eleven enqueued operations per call.
+ * A smaller ws_bytes is DFE_ERR_WORKSPACE; every refusal comes before the first launch and writes nothing. */
+int dfe_eval_flow_record_doubles(void);
+int dfe_eval_depth_record_doubles(void);
+long dfe_eval_flow_ws_bytes(int n);
+long dfe_eval_depth_ws_bytes(int n, int Hmax, int Wmax);
+int dfe_eval_flow(const float* pred, int n, int h, int w, const float* gt_u, const float* gt_v, const unsigned char* flags,
+                  const int* dims, int N, int Hmax, int Wmax, int first, void* ws, long ws_bytes, double* records, void* stream);
+int dfe_eval_flow_finish(const double* records, int N, int has_moving, double* table, void* stream);
+int dfe_eval_depth(const float* disp, int n, int h, int w, const float* gt, const int* dims, int N, int Hmax, int Wmax, int first,
+                   float min_depth, float max_depth, void* ws, long ws_bytes, double* records, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,9 @@
 
 Same flags and the same model construction / ``load_state_dict(weights['model_state_dict'], strict=False)`` /
 ``eval()`` sequence as the reference (test.py:347-360), plus ``--session {off,eager,graph}`` (default off: the models' own methods;
-otherwise every task calls them through an ``inference.InferenceSession``, see there).  Tasks:
+otherwise every task calls them through an ``inference.InferenceSession``, see there) and ``--fused_eval`` (default off: the two
+flow tasks and the depth task from a device-resident set through ``eval_device.Evaluator``, what ``train.py`` runs every
+``--test_interval`` iterations; not together with ``--result_dir``).  Tasks:
 
 * ``kitti_flow_2012`` / ``kitti_flow_2015`` (test.py:21-87): image pairs + 16-bit flow ground truth of ``cfg.gt_2012_dir`` /
   ``cfg.gt_2015_dir`` -> ``inference_flow`` -> ``eval_flow_avg`` (with the object-map moving masks for 2015);
@@ -150,6 +152,27 @@ def test_eigen_depth(cfg, model, dev):
     return res
 
 
+def test_fused(cfg, model, dev, task):
+    """``--fused_eval``: the task from a device-resident set through eval_device.Evaluator (batched inference, metric kernels
+    behind each batch, one host transfer); prints what the per-image task prints.  ``model``: the model itself, in eval mode."""
+    from unsupervised_depth_opticalflow_egomotion_amd import eval_device
+    session = "graph" if getattr(cfg, "session", "off") == "graph" else "eager"
+    if task == "kitti_depth":
+        raw = require_dir(cfg, "raw_base_dir")
+        dset = eval_device.DepthEvalSet.from_eigen(raw, getattr(cfg, "eigen_dir", None) or "./data/eigen", cfg.img_hw, dev)
+        res = eval_device.Evaluator(model, cfg, depth=dset, session=session).run()["eval_eigen_res"]
+        print("{:>10}, {:>10}, {:>10}, {:>10}, {:>10}, {:>10}, {:>10} ".format("abs_rel", "sq_rel", "rms", "log_rms", "a1", "a2", "a3"))
+        print("{:10.4f}, {:10.4f}, {:10.3f}, {:10.3f}, {:10.3f}, {:10.3f}, {:10.3f} ".format(*res))
+        return res
+    year = int(task[-4:])
+    fset = eval_device.FlowEvalSet.from_kitti(require_dir(cfg, "gt_%d_dir" % year), cfg.img_hw, year, dev)
+    res = eval_device.Evaluator(model, cfg, **{"flow_%d" % year: fset}, session=session).run()["eval_%d_res" % year]
+    print("CONFIG: {0}, mode: {1}".format(cfg.config_file, cfg.mode))
+    print("[EVAL] [KITTI %d]" % year)
+    print(res)
+    return res
+
+
 def test_pose_odom(cfg, model, dev):
     """test.py:137-194: ATE / RE over 3-frame odometry snippets."""
     root = require_dir(cfg, "kitti_odom_dir")
@@ -208,7 +231,16 @@ def main():
     ap.add_argument("--session", choices=("off", "eager", "graph"), default="off",
                     help="run the tasks through an inference.InferenceSession: fused eval-mode BatchNorm and the scale-0 head alone "
                          "(eager), replayed from a hipGraph (graph); off = the models' own methods")
+    ap.add_argument("--fused_eval", action="store_true",
+                    help="kitti_flow_2012 / kitti_flow_2015 / kitti_depth from a device-resident set: batched inference through an "
+                         "InferenceSession and the metric kernels (eval_device.Evaluator); keeps no per-image prediction on the host, "
+                         "so it cannot be combined with --result_dir")
     args = ap.parse_args()
+    fused = args.fused_eval
+    if fused and args.result_dir:
+        raise ValueError("--fused_eval keeps no per-image prediction on the host: it cannot write them to --result_dir")
+    if fused and args.task not in ("kitti_flow_2012", "kitti_flow_2015", "kitti_depth"):
+        raise ValueError("--fused_eval covers the tasks kitti_flow_2012, kitti_flow_2015 and kitti_depth, not %r" % args.task)
     if not args.config_file or not os.path.exists(args.config_file):
         raise ValueError("config file not found.")
     with open(args.config_file, "r") as f:
@@ -241,6 +273,9 @@ def main():
         model.load_state_dict(state, strict=False)
     model.eval()
     print("Model Loaded.")
+    if fused:
+        test_fused(cfg_new, model, dev, args.task)
+        return
     if args.session != "off":
         from unsupervised_depth_opticalflow_egomotion_amd.inference import InferenceSession
         model = InferenceSession(model, graph=args.session == "graph")

@@ -9,7 +9,13 @@ with one process per GPU over RCCL (ddp.wrap: one flat gradient all-reduce per s
 torchrun); the data source is the synthetic KITTI-shaped triplet generator by default (``data_source: synthetic``), or the
 reference's prepared KITTI tree with ``--data_source prepared --prepared_base_dir DIR`` (train.txt, stacked-triplet PNGs and
 calib files as KITTI_RAW.prepare_data_mp writes them; read by prepared_data.PreparedFeeder on ``--num_workers`` decode threads
-with the image half on the device); periodic KITTI evaluation (train.py:136-164) needs the datasets and is skipped (``--no_test`` semantics).
+with the image half on the device).  Periodic KITTI evaluation (train.py:136-164) is honoured: every ``--test_interval``
+iterations (iteration 0 included) unless ``--no_test``, rank 0 runs KITTI flow 2012 / 2015 and / or Eigen depth by mode
+(``periodic_eval``) from device-resident sets (eval_device.Evaluator: batched inference through an InferenceSession, metric
+kernels behind each batch, one host transfer per task), prints the reference's tables and pickles the list of result packs to
+``model_dir/log.pkl`` (the format of the reference's Visualizer.dump_log).  A task runs when the config names its data and the
+directory exists (``gt_2012_dir``, ``gt_2015_dir``, ``raw_base_dir`` + ``eigen_dir``); the shipped config names none, so with it
+nothing is evaluated.
 Checkpoints keep the reference format: {iteration, model_state_dict, optimizer_state_dict} in
 iter_{N}.pth and last.pth (train.py:21-29)."""
 import argparse
@@ -49,6 +55,48 @@ def print_loss(iter_, loss_pack, weights, total, guard=None):
     if guard is not None:
         line += " | gnorm {:.2f} clip {:.2f} skipped {:d}".format(guard["grad_norm"], guard["clip_coef"], guard["skipped_steps"])
     print(line, flush=True)
+
+
+def build_evaluator(cfg, model, dev):
+    """The evaluator of the mode's tasks whose data the config names and which exist (None: nothing to evaluate).  The sets are read
+    and prepared here, once."""
+    from unsupervised_depth_opticalflow_egomotion_amd import eval_device
+    if getattr(cfg, "no_test", False):
+        return None
+    sets = {}
+    for task in eval_device.tasks_for_mode(cfg.mode):
+        if task == "depth":
+            raw, eigen = getattr(cfg, "raw_base_dir", None), getattr(cfg, "eigen_dir", None)
+            if raw and eigen and os.path.isdir(raw) and os.path.isdir(eigen):
+                sets[task] = eval_device.DepthEvalSet.from_eigen(raw, eigen, cfg.img_hw, dev)
+        else:
+            year = int(task[-4:])
+            gt_dir = getattr(cfg, "gt_%d_dir" % year, None)
+            if gt_dir and os.path.isdir(gt_dir):
+                sets[task] = eval_device.FlowEvalSet.from_kitti(gt_dir, cfg.img_hw, year, dev)
+    if not sets:
+        return None
+    return eval_device.Evaluator(ddp.unwrap(model), cfg, **sets)
+
+
+def periodic_eval(cfg, evaluator, it, log_list):
+    """train.py:136-164: at ``it % test_interval == 0`` unless ``no_test``, run the evaluator, print the reference's lines, append
+    the result pack to ``log_list`` and pickle the list to ``model_dir/log.pkl``.  Returns the pack, or None when nothing ran."""
+    if evaluator is None or getattr(cfg, "no_test", False) or it % cfg.test_interval != 0:
+        return None
+    pack = evaluator.run()
+    for year in (2012, 2015):
+        if "eval_%d_res" % year in pack:
+            print("[EVAL] [KITTI %d]" % year)
+            print(pack["eval_%d_res" % year], flush=True)
+    if "eval_eigen_res" in pack:
+        print("[EVAL] [KITTI Eigen depth]")
+        print("{:>10}, {:>10}, {:>10}, {:>10}, {:>10}, {:>10}, {:>10} ".format("abs_rel", "sq_rel", "rms", "log_rms", "a1", "a2", "a3"))
+        print("{:10.4f}, {:10.4f}, {:10.3f}, {:10.3f}, {:10.3f}, {:10.3f}, {:10.3f} ".format(*pack["eval_eigen_res"]), flush=True)
+    log_list.append(pack)
+    with open(os.path.join(cfg.model_dir, "log.pkl"), "wb") as fh:
+        pickle.dump(log_list, fh)
+    return pack
 
 
 def train(cfg):
@@ -110,8 +158,10 @@ def train(cfg):
         from unsupervised_depth_opticalflow_egomotion_amd import profiling
         profiling.enable()
         prof = profiling.Profiler(silent=rank != 0)
+    evaluator, log_list = (build_evaluator(cfg, model, dev) if rank == 0 else None), []      # rank 0 alone evaluates; no collective
     t0 = time.time()
     for it in range(start, cfg.num_iterations):
+        periodic_eval(cfg, evaluator, it, log_list)
         if feeder is not None:
             inputs = next(feeder)      # batch it - start of the per-rank shard: idx = (it - start) * B * world + rank * B + j
         else:
