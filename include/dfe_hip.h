@@ -758,6 +758,45 @@ int dfe_eval_flow_finish(const double* records, int N, int has_moving, double* t
 int dfe_eval_depth(const float* disp, int n, int h, int w, const float* gt, const int* dims, int N, int Hmax, int Wmax, int first,
                    float min_depth, float max_depth, void* ws, long ws_bytes, double* records, void* stream);
 
+/* ---- top-k selection in pixel order  model_geometry.py:427-437 (top_ratio_sample) ------------------------------------------
+ * scores [planes, n] -> idx int32 [planes, k]: the pixel indices of the k largest scores of each plane in ASCENDING pixel order.
+ * Order of torch.topk: NaN ranks above +inf, -0 equals +0; equal scores at the threshold go to the lower pixel index.  One
+ * workgroup per plane: a radix select over order-preserving keys (LDS integer histograms), then an ordered compaction.  No float
+ * atomics and no host read: bitwise reproducible and capturable.
+ * Memory contract: reads scores [planes * n], writes every element of idx [planes * k] and of ws, dfe_topk_ws_bytes(planes, n, k)
+ * bytes on 4 bytes, no initialisation: per plane four words -- the threshold's key, the count of scores above it, the count of
+ * ties taken, 0.  1 <= k <= n, or DFE_ERR_DIMS before the launch. */
+long dfe_topk_ws_bytes(int planes, int n, int k);
+int dfe_topk_select(const float* scores, int* idx, void* ws, int planes, int n, int k, void* stream);
+
+/* ---- triangulation loss  model_geometry.py:569-683, call site :939-940 -------------------------------------------------------
+ * Point (d, b, j), d < 2 directions (0: target -> left, 1: target -> right), b < B, j < num, is the pixel
+ * idx[d*B + b][pick[j]] (idx int32 [2B, k] from dfe_topk_select, pick int64 [num] in [0, k); both are clamped on the device, so
+ * no entry can carry an access outside the planes).  flow_bwd / flow_fwd [B,2,H,W] scale-0 flows, disp_t / disp_l / disp_r
+ * [B,1,H,W], T34 [B,2,12] (pose_vec2mat of both directions), K / K_inv [B,9].  The match (x, y, x + u, y + v) is mid-point
+ * triangulated under P1 = K [I|0], P2 = K T34, reprojected into both views, disp_t is sampled at the first coordinate and the
+ * source disparity at the second (bilinear, reflection padding, align_corners as given) -- the reference's expressions and
+ * epsilons, evaluated in double.
+ * dfe_triangulate_fwd: writes rec, 2*B*num records of four doubles (inter1, z1, inter2, z2).
+ * dfe_triangulate_stats: per (b, d, view) the lower medians of inter and z (torch.median: rank (num-1)/2; radix select in LDS,
+ *   num <= 16384 or DFE_ERR_UNSUPPORTED), the detached scale and scale_adapt's a, the view's loss -> stats [B,2,2,4] doubles
+ *   (scale, a, a / (scale + 1e-12), loss), then loss[b] = (L00 + L01) + (L10 + L11).  Sums in double, order fixed by thread index.
+ * dfe_triangulate_bwd: from gloss [B]: grads, 7*B*H*W floats = the gradients of flow_bwd, flow_fwd (2*B*H*W each), disp_t, disp_l,
+ *   disp_r (B*H*W each), every element written; gT34 [B,2,12].  scale and a are constants, as in the reference.  Per-point
+ *   derivatives by forward-mode duals; points repeat, so every scatter goes through 64-bit fixed-point accumulators (integer
+ *   atomics); gT34 from per-block partial sums added in block order.  ws: dfe_triangulate_ws_bytes(B, H, W, num) bytes on 16
+ *   bytes, no initialisation.  A memset and three launches.
+ * Every result is bitwise reproducible.  H, W >= 2, H*W < 2^28, k <= H*W; refusals come before the first launch. */
+long dfe_triangulate_ws_bytes(int B, int H, int W, int num);
+int dfe_triangulate_fwd(const float* flow_bwd, const float* flow_fwd, const float* disp_t, const float* disp_l,
+                        const float* disp_r, const float* T34, const float* K, const float* K_inv, const int* idx,
+                        const long long* pick, double* rec, int B, int H, int W, int k, int num, int align_corners, void* stream);
+int dfe_triangulate_stats(const double* rec, double* stats, float* loss, int B, int num, void* stream);
+int dfe_triangulate_bwd(const float* flow_bwd, const float* flow_fwd, const float* disp_t, const float* disp_l,
+                        const float* disp_r, const float* T34, const float* K, const float* K_inv, const int* idx,
+                        const long long* pick, const double* stats, const float* gloss, float* grads, float* gT34, void* ws,
+                        int B, int H, int W, int k, int num, int align_corners, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,8 +137,12 @@ class GeometrySolvers:
         return torch.pow(1.0 - pred_tri_depth / (tri_depth + 1e-12), 2).mean((1, 2))
 
     def compute_triangulate_loss(self, match, pose, K, K_inv, depth_pred1, depth_pred2):
-        d1, d2 = depth_pred1[0], depth_pred2[0]
         P1, P2 = compute_projection_matrix(pose, K)
+        return self.triangulate_loss_from_projections(match, P1, P2, K, K_inv, depth_pred1[0], depth_pred2[0])
+
+    def triangulate_loss_from_projections(self, match, P1, P2, K, K_inv, d1, d2):
+        """compute_triangulate_loss after its projection matrices (pose_vec2mat is a HIP operator; this part is plain torch
+        on any device and float type)."""
         pts = self.midpoint_triangulate(match, K, K_inv, P1, P2)
         c1, z1 = self.reproject(P1, pts)
         c2, z2 = self.reproject(P2, pts)

@@ -163,6 +163,8 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         # the two depth terms the reference keeps commented (model_geometry.py:889-891,897-899); off = placeholders
         self.enable_depth_ssim = bool(getattr(cfg, "enable_depth_ssim", False))
         self.enable_depth_consis = bool(getattr(cfg, "enable_depth_consis", False))
+        # the triangulation term the reference keeps commented (model_geometry.py:939-940); off = placeholder
+        self.enable_triangle = bool(getattr(cfg, "enable_triangle", False))
 
     # ---- inference API (model_geometry.py:282-302)
     def infer_depth(self, img):
@@ -247,6 +249,61 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
                 self.compute_consis_loss(pd_r, cd_r, fwd_tex)
         return out
 
+    def triangle_term(self, disp_l0, disp_t0, disp_r0, pose, flow_bwd0, flow_fwd0, K, K_inv, return_draw=False):
+        """``loss_triangle`` of the commented call site (model_geometry.py:939-940) -> (B,), enabled by
+        ``cfg.enable_triangle``: the matches of both directions are sampled as ``sample_match`` samples them from
+        ``flow_diff_scores[0]`` and go through ``compute_triangulate_loss``, as four fused launches (triangulate.py) instead
+        of the torch composition of GeometrySolvers -- no host read, capturable, bitwise reproducible.
+
+        Scores: the existing rigid-flow and dynamic-mask kernels at scale 0 under ``no_grad``, both directions in one call,
+        as ``compute_dynamic_mask`` defines ``flow_diff_scores[0]``.  ``k = int(ratio * H * W)`` pixels per sample and
+        direction are kept (dfe_topk_select), ``num`` of them drawn with replacement by one ``torch.randint`` on the device
+        generator (it follows ``torch.manual_seed``), shared by the batch and both directions.  The pose matrices come from
+        ``PoseMatsFn``, so the pose's chain rule stays there.
+
+        Deviations from the reference, all deliberate:
+        * selection order -- the reference draws ranks in ``topk``'s sorted order; here the draw indexes the pixel-ordered
+          top-k set.  Same law (uniform over the top-ratio set, with replacement), different bits;
+        * the "some scores are zero" branch of ``robust_rand_sample`` is not reproduced: it needs a host sync and is reachable
+          only with non-finite network outputs.  Such pixels rank by ``topk``'s order (NaN first); a resulting non-finite loss
+          is the gradient guard's business (FusedAdam ``skip_nonfinite``);
+        * as at the commented call site, the raw disparity lists are passed as "depth" (SURVEY.md A.7);
+        * geom mode only."""
+        from . import triangulate
+        B, _, H, W = flow_bwd0.shape
+        dev = flow_bwd0.device
+        with torch.no_grad():
+            pose2 = torch.cat([pose[:, 0], pose[:, 1]], 0)
+            rigid = ops.RigidFlowFn.apply(torch.cat([disp_t0, disp_t0], 0), pose2, torch.cat([K, K], 0))
+            _, score = ops.dynamic_mask(torch.cat([flow_bwd0, flow_fwd0], 0), rigid, self.flow_consist_alpha,
+                                        self.flow_consist_beta)
+            k = int(self.ratio * H * W)
+            idx = triangulate.topk_select(score.view(2 * B, H * W), k)
+            pick = torch.randint(0, k, [int(self.num)], device=dev)
+        T34 = ops.PoseMatsFn.apply(pose.reshape(2 * B, 6))[0].view(B, 2, 3, 4)
+        loss = triangulate.triangulate_loss(flow_bwd0, flow_fwd0, disp_t0, disp_l0, disp_r0, T34, K, K_inv, idx, pick,
+                                            ops.get_align_corners())
+        return (loss, idx, pick) if return_draw else loss
+
+    def triangle_term_torch(self, disp_l0, disp_t0, disp_r0, T34, flow_bwd0, flow_fwd0, K, K_inv, idx, pick, matches=None):
+        """The per-operator cross-check of ``triangle_term`` (like ``disabled_depth_terms``): the body of the existing
+        ``compute_triangulate_loss`` of GeometrySolvers fed with the same ``idx`` / ``pick`` and the pose matrices
+        ``T34`` [B,2,3,4] (``PoseMatsFn``'s output) -- plain torch, any device, any float type.  ``matches``: (match_bwd,
+        match_fwd) [B,4,num] given directly instead of gathered from the flows (golden G11's matches are off the pixel grid)."""
+        if matches is None:
+            B, _, H, W = flow_bwd0.shape
+            matches = []
+            for d, flow in enumerate((flow_bwd0, flow_fwd0)):
+                pix = idx[d * B:(d + 1) * B].long()[:, pick.long()]                      # [B,num]
+                x, y = (pix % W).to(flow.dtype), torch.div(pix, W, rounding_mode="floor").to(flow.dtype)
+                uv = torch.gather(flow.reshape(B, 2, H * W), 2, pix.unsqueeze(1).expand(-1, 2, -1))
+                matches.append(torch.stack([x, y, x + uv[:, 0], y + uv[:, 1]], 1))
+        eye = torch.zeros(K.shape[0], 3, 4, dtype=K.dtype, device=K.device)
+        eye[:, 0, 0] = eye[:, 1, 1] = eye[:, 2, 2] = 1.0
+        P1 = K.bmm(eye)
+        return self.triangulate_loss_from_projections(matches[0], P1, K.bmm(T34[:, 0]), K, K_inv, disp_t0, disp_l0) + \
+            self.triangulate_loss_from_projections(matches[1], P1, K.bmm(T34[:, 1]), K, K_inv, disp_t0, disp_r0)
+
     def loss_stack(self, img_l, img, img_r, disp_l, disp_t, disp_r, pose, flows_bwd, flows_fwd, K, K_inv):
         """Everything from model_geometry.py:797 to :951 -> (loss_pack, mask_pack)."""
         S = self.num_scales
@@ -259,6 +316,11 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         dev = img.device
         loss_pack = LossRows({k: (active[k] if k in active else _zeros2(dev)) for k in LOSS_ORDER_GEOM})
         loss_pack.rows = active.rows
+        if getattr(self, "enable_triangle", False):
+            loss_pack["loss_triangle"], idx, pick = self.triangle_term(disp_l[0], disp_t[0], disp_r[0], pose, flows_bwd[0],
+                                                                       flows_fwd[0], K.contiguous(), K_inv.contiguous(),
+                                                                       return_draw=True)
+            self.triangle_draw = (idx, pick)      # the set and the draw of this step (triangle_term_torch takes them)
 
         def u8(*names):
             """sample 0, scale 0 of the product of the named masks, decoded from the 1-byte mask pack only when the
