@@ -839,6 +839,55 @@ int dfe_eight_point_loss_fwd(const float* E, const float* Kt_inv, const float* K
 int dfe_eight_point_loss_bwd(const float* E, const float* Kt_inv, const float* K_inv, const float* F32, const float* gloss,
                              float* gE, int B, void* stream);
 
+/* ---- PnP loss  model_geometry.py:473-530, call site :944-945 -----------------------------------------------------------------
+ * The robust pose that reprojects the target frame's back-projected matches onto their matched pixels (the robust branch of
+ * GeometrySolvers.pnp -- _pnp_hypotheses, scoring, consensus, _pnp_refine, re-score, _pnp_refine -- step for step, all
+ * estimation arithmetic in double) and the L1 loss between that pose and the pose vector.
+ * Planes, idx and pick as the eight-point entry takes them and clamps them.  Match j of plane p = d*B + b at pixel (x, y) is the
+ * point X = K_inv[b] (x, y, 1) * disp_t[b][pixel], formed in double from the fp32 inputs (the composition's compute_pnp_loss
+ * rounds it to fp32 first: a deliberate deviation), and the pixel (x + u, y + v), the sums formed in fp32 and then widened.  As at
+ * the commented call site the raw scale-0 disparity of the target frame is the "depth" of both directions.  sets int32
+ * [B, hyp, 6]: the minimal sets, indices into [0, num) (clamped on the device); both directions of sample b use sets[b].
+ * K, K_inv fp32 [B, 9]: K[b] projects sample b (fx, fy, cx, cy = K[0], K[4], K[2], K[5]; its inverse, formed in double as the
+ * adjugate over the determinant, normalises the hypotheses' pixels), K_inv[b] back-projects it.
+ * The pnp ransac entry: a memset of the counts and four launches, no host read.
+ *   1. points [2B, num, 5] doubles: X, Y, Z, x + u, y + v.
+ *   2. per (plane, hypothesis) the six-point DLT pose of its 6 matches: the 12x12 normal matrix of the system
+ *      [Xh, 0, -u Xh; 0, Xh, -v Xh] (in LDS, 288 doubles per thread with the eigenvectors), its smallest eigenvector by cyclic
+ *      Jacobi (at most 24 sweeps), the left 3x3 projected onto SO(3) by a one-sided Jacobi (at most 12 sweeps), the scale from the
+ *      mean singular value (at least 1e-300), the sign from the determinant.  A hypothesis only votes.
+ *   3. per (plane, hypothesis) the count of matches with eu^2 + ev^2 <= thresh^2 and z > 0, the projection dividing by
+ *      max(z, 1e-9); a non-finite residual is an outlier.  Blocks hold a tile of 256 matches and pass the hypotheses through LDS
+ *      in tiles of 64; integer atomics only.
+ *   4. per plane: the hypothesis with the most inliers (ties: the lowest index) and its inlier set, all matches if that set has
+ *      fewer than 6; iters Levenberg-Marquardt iterations on SE(3) over the set (left-multiplied exp([omega]x), damping scaled by
+ *      max(diag H, 1e-12), accept on cn < cost, lambda * 0.3 on accept and * 5 on reject within [1e-9, 1e6], lambda = 1e-3 at the
+ *      start; the 28 sums of an iteration -- 21 of H, 6 of g, the cost -- reduced in double in an order fixed by thread index;
+ *      the 6x6 solve by elimination with partial pivoting); the inlier set of the refined pose (fewer than 6: the previous set);
+ *      max(iters / 2, 1) more iterations on it; the rotation's logarithm.
+ *   Writes every element of P64 [2B, 6] doubles = (T, axis-angle), of P32 [2B, 6] (the same values rounded once) and of info int32
+ *   [2B, 4]: the winning hypothesis, its count, the sizes of the two refinement sets after their fall-backs.  NaN or inf in a
+ *   sample's flows or disparity at a sampled pixel gives an unspecified, possibly non-finite pose for that sample's planes and
+ *   leaves the other samples' bits alone; every loop has a fixed bound.
+ *   ws: the ws_bytes entry's answer for (B, num, hyp), bytes on 16 bytes, no initialisation, every byte of the five sections'
+ *   payload written.  Sections, each starting on 16 bytes, r16 = rounded up to 16: points at 0 (40*2B*num bytes); the hypotheses'
+ *   (R row-major, T) [2B, hyp, 12] doubles at 80*B*num; the counts int32 [2B, hyp] at 80*B*num + 192*B*hyp; the 0/1 weights of the
+ *   first refinement int32 [2B, num] after r16(8*B*hyp) more; those of the second refinement after r16(8*B*num) more.
+ *   Refusals before the first launch: num < 6, hyp < 1, k > H*W, k < 1, H*W >= 2^28, iters < 1 -> DFE_ERR_DIMS; num > 16384 or
+ *   hyp > 4096 -> DFE_ERR_UNSUPPORTED; ws not on 16 bytes or P64 not on 8 -> DFE_ERR_DIMS.
+ * The loss entries: pose fp32 [B, 2, 6] (row b*2 + d), P32 [2B, 6] (plane d*B + b), beta the rotation part's weight.
+ *   forward: loss[b] = sum over d of mean_3(|P[:3] - pose[:3]| + beta |P[3:] - pose[3:]|) in fp32 -- (T, axis-angle) against
+ *   (translation, Euler angles), the reference's comparison as written.  Writes every element of loss [B]; one launch.
+ *   backward: from gloss [B] writes every element of gpose [B, 2, 6] = gloss[b] / 3 * sign(pose - P) * (1 | beta), sign(0) = 0;
+ *   P is a constant.  No workspace; one launch.
+ * Every result is bitwise reproducible (no float atomics). */
+long dfe_pnp_ws_bytes(int B, int num, int hyp);
+int dfe_pnp_ransac(const float* flow_bwd, const float* flow_fwd, const float* disp_t, const int* idx, const long long* pick,
+                   const int* sets, const float* K, const float* K_inv, double* P64, float* P32, int* info, void* ws, int B, int H,
+                   int W, int k, int num, int hyp, int iters, double thresh, void* stream);
+int dfe_pnp_loss_fwd(const float* pose, const float* P32, float* loss, int B, float beta, void* stream);
+int dfe_pnp_loss_bwd(const float* pose, const float* P32, const float* gloss, float* gpose, int B, float beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

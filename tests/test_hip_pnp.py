@@ -1,0 +1,299 @@
+"""The PnP operator (pnp.py over csrc/ops_pnp.hip) against the float64 composition of ``GeometrySolvers.pnp`` on the same sets and on
+float64 points formed as the operator forms them, on the cases of tests/pnp_cases.py: (B, H, W, k, num, hyp) = (2, 12, 20, 72, 64,
+32) without and with noise, (2, 13, 19, 72, 70, 33) and (2, 20, 24, 320, 300, 70) -- num above the scoring kernel's match tile
+(PNP_MATCH_TILE = 256: two blocks per plane, the second partly filled) and hyp above its hypothesis tile (PNP_HYP_TILE = 64) and no
+multiple of it -- plus the case whose first refinement falls back to all matches.  Every buffer of the raw entry points is carved
+out of a guarded one.
+
+Votes and weights are integers and the cases keep every residual a relative 1e-6 away from the threshold: they must be EQUAL.
+``P64``: Levenberg-Marquardt's accept test ``cn < cost`` is decided on rounding noise once the iteration has converged, and the
+minimum of a cost known to a relative 1e-16 is located to about its square root, so equality with the composition is not the
+contract.  Measured on the device, max |P - P_comp| / max |P_comp| over the planes of all cases is P_MEASURED
+(profiles/pnp_ebound.txt, next to the composition's own 20-versus-40-iteration difference); P_BOUND is ten times that.  The
+noise-free case recovers the analytic pose to TRUE_MEASURED (what fp32 flows, disparities and camera matrices allow; same file),
+asserted at ten times that.  Loss and gradient: the project's written tolerances, 5e-6 relative and 2e-5 of the
+gradient's scale."""
+import ctypes
+import functools
+
+import pytest
+import torch
+
+from tests import guarded as G
+from tests import pnp_cases as PC
+
+pytestmark = pytest.mark.gpu
+
+P_MEASURED = 1.273e-09
+P_BOUND = 10.0 * P_MEASURED
+TRUE_MEASURED = 1.212e-07
+TRUE_BOUND = 10.0 * TRUE_MEASURED
+P = ctypes.c_void_p
+
+
+def _i32(carved):
+    return carved.view.contiguous().view(torch.int32).cpu()
+
+
+def raw_ransac(case, sets=None, flow_bwd=None, flow_fwd=None, disp_t=None, offsets=(1, 2, 3, 2), iters=PC.ITERS):
+    """dfe_pnp_ransac with the flows, the disparity, the camera matrices, every output and the workspace carved -> dict of CPU
+    tensors; guards checked."""
+    from unsupervised_depth_opticalflow_egomotion_amd import _lib, pnp
+    lib = _lib.get_lib()
+    B, H, W, k, num = (case[n] for n in ("B", "H", "W", "k", "num"))
+    sets = (case["sets"] if sets is None else sets).cuda().contiguous()
+    hyp = sets.shape[1]
+    fb = G.Carved((B, 2, H, W), offset_floats=offsets[0], fill=case["flow_bwd"] if flow_bwd is None else flow_bwd)
+    ff = G.Carved((B, 2, H, W), offset_floats=offsets[1], fill=case["flow_fwd"] if flow_fwd is None else flow_fwd)
+    dt = G.Carved((B, 1, H, W), offset_floats=offsets[2], fill=case["disp_t"] if disp_t is None else disp_t)
+    Kc = G.Carved((B, 9), offset_floats=1, fill=case["K"].reshape(B, 9))
+    Kic = G.Carved((B, 9), offset_floats=3, fill=case["K_inv"].reshape(B, 9))
+    idx, pick = case["idx"].cuda(), case["pick"].cuda()
+    P64 = G.Carved((2 * B * 6, 2), offset_floats=offsets[3])          # doubles: 8-byte aligned, not 16
+    P32 = G.Carved((2 * B, 6), offset_floats=offsets[2])
+    info = G.Carved((2 * B, 4), offset_floats=1)
+    sec = pnp.workspace_sections(B, num, hyp)
+    assert lib.dfe_pnp_ws_bytes(B, num, hyp) == sec["bytes"]
+    ws = G.Carved((sec["bytes"] // 4,), offset_floats=0)
+    _lib.check(lib.dfe_pnp_ransac(P(fb.ptr), P(ff.ptr), P(dt.ptr), P(idx.data_ptr()), P(pick.data_ptr()), P(sets.data_ptr()), P(Kc.ptr),
+                                  P(Kic.ptr), P(P64.ptr), P(P32.ptr), P(info.ptr), P(ws.ptr), B, H, W, k, num, hyp, iters, PC.THRESH,
+                                  _lib.stream_ptr()), "dfe_pnp_ransac")
+    torch.cuda.synchronize()
+    for c in (fb, ff, dt, Kc, Kic, P64, P32, info, ws):
+        assert c.intact()
+    words = _i32(ws)
+    sl = lambda name, n: words[sec[name] // 4:sec[name] // 4 + n]   # noqa: E731
+    return dict(P64=P64.view.contiguous().view(torch.float64).cpu().reshape(2 * B, 6), P32=P32.cpu().reshape(2 * B, 6),
+                info=_i32(info).reshape(2 * B, 4), counts=sl("counts", 2 * B * hyp).reshape(2 * B, hyp),
+                w1=sl("w1", 2 * B * num).reshape(2 * B, num), w2=sl("w2", 2 * B * num).reshape(2 * B, num),
+                written=P32.written() and info.written())
+
+
+@functools.lru_cache(maxsize=None)
+def result(key):
+    """(case with its float64 composition, the kernels' outputs): computed once, shared, never changed."""
+    case = PC.make_case(key) if key != "fallback" else PC.fallback_case()
+    return case, raw_ransac(case)
+
+
+def rel_err(Pd, ref):
+    """the largest difference of a plane's pose relative to that pose's scale, over the planes"""
+    return float(((Pd - ref).abs().amax(1) / ref.abs().amax(1)).max())
+
+
+def _equal_decisions(out, c):
+    assert out["written"]
+    assert torch.equal(out["counts"].long(), c["counts"])                       # every hypothesis, as integers
+    assert torch.equal(out["w1"].long(), c["w1"].long()) and torch.equal(out["w2"].long(), c["w2"].long())
+    info = out["info"].long()
+    assert torch.equal(info[:, 0], c["best"]) and torch.equal(info[:, 1], c["counts"].max(1)[0])
+    assert torch.equal(info[:, 2], c["w1"].sum(1).long()) and torch.equal(info[:, 3], c["w2"].sum(1).long())
+
+
+@pytest.mark.parametrize("key", PC.SHAPES)
+def test_votes_sets_and_info_equal_the_composition(key):
+    case, out = result(key)
+    _equal_decisions(out, case["comp"])
+    assert torch.equal(out["info"][:, 1].long(), out["w1"].sum(1).long())       # the consensus is the winner's inlier set (>= 6)
+
+
+def test_p64_against_the_composition_and_p32_is_its_rounding():
+    worst = 0.0
+    for key in PC.SHAPES:
+        case, out = result(key)
+        ref = case["comp"]["P"]
+        assert bool(torch.isfinite(out["P64"]).all())
+        e = rel_err(out["P64"], ref)
+        yard = rel_err(PC.composition_of(case, case["x"], case["X"], iterations=2 * PC.ITERS)["P"], ref)
+        print("EBOUND pnp P64 %s max|dP|/max|P| %.3e; the composition at 40 iterations against itself at 20: %.3e"
+              % ("x".join(str(int(v)) for v in key), e, yard))
+        worst = max(worst, e)
+        assert torch.equal(out["P32"], out["P64"].float())                      # rounded once: bit equality
+    print("EBOUND pnp P64 all cases %.3e bound %.3e" % (worst, P_BOUND))
+    assert worst <= P_BOUND, (worst, P_BOUND)
+
+
+def test_the_noise_free_case_recovers_the_analytic_pose():
+    case, out = result(PC.SHAPES[0])
+    assert not case["noisy"]
+    e = float((out["P64"] - case["P_true"]).abs().max())
+    ec = float((case["comp"]["P"] - case["P_true"]).abs().max())
+    print("EBOUND pnp noise-free max|P - P_true| %.3e (the composition: %.3e) bound %.3e" % (e, ec, TRUE_BOUND))
+    assert e <= TRUE_BOUND, (e, TRUE_BOUND)
+
+
+def test_the_fallback_case_refines_over_all_matches_first():
+    case, out = result("fallback")
+    c = case["comp"]
+    _equal_decisions(out, c)
+    few = c["n1raw"] < 6
+    assert bool(few.any())
+    info = out["info"].long()
+    assert bool((info[few, 1] < 6).all()) and bool((info[few, 2] == case["num"]).all()) and bool((out["w1"][few] == 1).all())
+    assert bool((info[few, 3] >= 6).all())                                      # the refinement over all matches still converged
+    e = rel_err(out["P64"], c["P"])
+    print("EBOUND pnp P64 fall-back case max|dP|/max|P| %.3e bound %.3e" % (e, P_BOUND))
+    assert e <= P_BOUND, (e, P_BOUND)
+
+
+def test_tied_counts_go_to_the_lowest_index():
+    """Two identical hypotheses: the winner of plane (d = 0, b = 0) is copied to another slot of sample 0's sets; both have the
+    maximum count of that plane and the lower slot wins.  The estimate does not move."""
+    key = PC.SHAPES[0]
+    case, out = result(key)
+    best = int(case["comp"]["best"][0])
+    slot = 0 if best != 0 else 1
+    sets = case["sets"].clone()
+    sets[0, slot] = sets[0, best]
+    tied = raw_ransac(case, sets=sets)
+    assert int(tied["counts"][0, slot]) == int(tied["counts"][0, best]) == int(out["info"][0, 1])
+    assert int(tied["info"][0, 0]) == min(slot, best) and int(tied["info"][0, 1]) == int(out["info"][0, 1])
+    assert torch.equal(tied["w1"][0], out["w1"][0]) and torch.equal(tied["P64"][0], out["P64"][0])
+
+
+def _loss_reference(P64, pose, beta, weights):
+    """float64: compute_pnp_loss's expression per direction and sample, fed the given pose estimate; the gradient of
+    sum(weights * loss) with respect to the pose vector."""
+    import torch.nn.functional as F
+    B = pose.shape[0]
+    pose = pose.double().requires_grad_(True)
+    loss = 0
+    for d in range(2):
+        est = P64[d * B:(d + 1) * B]
+        term = F.l1_loss(est[:, :3], pose[:, d, :3], reduction="none") + beta * F.l1_loss(est[:, 3:], pose[:, d, 3:], reduction="none")
+        loss = loss + term.mean(1)
+    (loss * weights.double()).sum().backward()
+    return loss.detach(), pose.grad
+
+
+@pytest.mark.parametrize("scale", [1.0, 40.0])
+def test_loss_and_gradient_against_float64(scale):
+    """Two pose scales; element (1, 0, 4) of the pose vector equals ``P32`` exactly: sign(0) = 0, the gradient there is 0."""
+    from unsupervised_depth_opticalflow_egomotion_amd import pnp
+    case, out = result(PC.SHAPES[2])
+    B, beta = case["B"], 0.75
+    w = torch.tensor([0.7, 1.3])
+    pose = PC.pose_vectors(case, scale=scale)
+    pose[1, 0, 4] = out["P32"][0 * B + 1, 4]
+    l64, g64 = _loss_reference(out["P32"].double(), pose, beta, w)
+    assert float(g64[1, 0, 4]) == 0.0
+    Pc = G.Carved((2 * B, 6), offset_floats=2, fill=out["P32"])
+    p = pose.cuda().requires_grad_(True)
+    loss = pnp.PnpLossFn.apply(p, Pc.view, beta)
+    (loss * w.cuda()).sum().backward()
+    torch.cuda.synchronize()
+    assert Pc.intact()
+    el = float(((loss.detach().double().cpu() - l64).abs() / l64.abs()).max())
+    eg = float((p.grad.double().cpu() - g64).abs().max() / g64.abs().max())
+    print("EBOUND pnp loss scale %g: loss %.3e (5e-6)  dpose %.3e (2e-5)" % (scale, el, eg))
+    assert el <= 5e-6 and eg <= 2e-5
+    assert float(p.grad[1, 0, 4]) == 0.0 and int((p.grad == 0).sum()) == 1
+
+
+def test_loss_entry_points_in_guarded_buffers():
+    from unsupervised_depth_opticalflow_egomotion_amd import _lib
+    lib = _lib.get_lib()
+    for key in PC.SHAPES[1:]:
+        case, out = result(key)
+        B = case["B"]
+        ins = [G.Carved((B, 2, 6), offset_floats=1, fill=PC.pose_vectors(case)), G.Carved((2 * B, 6), offset_floats=3, fill=out["P32"])]
+        loss, gloss, gp = G.Carved((B,), offset_floats=1), G.Carved((B,), offset_floats=3, fill=torch.tensor([0.7, 1.3])), G.Carved((B, 2, 6), offset_floats=2)
+        st = _lib.stream_ptr()
+        beta = ctypes.c_float(0.5)
+        _lib.check(lib.dfe_pnp_loss_fwd(*[P(c.ptr) for c in ins], P(loss.ptr), B, beta, st), "fwd")
+        _lib.check(lib.dfe_pnp_loss_bwd(*[P(c.ptr) for c in ins], P(gloss.ptr), P(gp.ptr), B, beta, st), "bwd")
+        torch.cuda.synchronize()
+        assert all(c.intact() for c in ins + [loss, gloss, gp]) and loss.written() and gp.written()
+
+
+def test_refusals_come_before_any_launch():
+    from unsupervised_depth_opticalflow_egomotion_amd import _lib
+    lib = _lib.get_lib()
+    out = G.Carved((64,), offset_floats=0)
+    odd = G.Carved((64,), offset_floats=1)
+    x = torch.zeros(4096, device="cuda")
+    p, o, st = P(x.data_ptr()), P(out.ptr), _lib.stream_ptr()
+
+    def call(H, W, k, num, hyp, iters=20, P64=o, ws=o):
+        return lib.dfe_pnp_ransac(p, p, p, p, p, p, p, p, P64, o, o, ws, 1, H, W, k, num, hyp, iters, 1.0, st)
+    assert call(8, 8, 16, 5, 4) == -2           # num = 5
+    assert call(8, 8, 16, 6, 0) == -2           # hyp = 0
+    assert call(8, 8, 65, 6, 4) == -2 and call(8, 8, 0, 6, 4) == -2           # k outside [1, H*W]
+    assert call(1 << 14, 1 << 14, 16, 6, 4) == -2                             # H*W = 2^28
+    assert call(8, 8, 16, 6, 4, iters=0) == -2
+    assert call(8, 8, 16, 6, 4, P64=P(odd.ptr)) == -2 and call(8, 8, 16, 6, 4, ws=P(odd.ptr)) == -2      # 4 bytes past 16
+    assert call(8, 8, 16, 16385, 4) == -4 and call(8, 8, 16, 6, 4097) == -4
+    assert lib.dfe_pnp_ransac(None, p, p, p, p, p, p, p, o, o, o, o, 1, 8, 8, 16, 6, 4, 20, 1.0, st) == -1
+    assert lib.dfe_pnp_loss_fwd(p, p, o, 0, ctypes.c_float(1.0), st) == -2
+    assert lib.dfe_pnp_loss_bwd(p, p, p, o, 0, ctypes.c_float(1.0), st) == -2
+    torch.cuda.synchronize()
+    assert out.untouched() and out.intact() and odd.untouched() and odd.intact()
+
+
+@pytest.mark.parametrize("where", ["flow", "disp"])
+def test_a_nan_in_one_sample_leaves_the_other_samples_bits(where):
+    """Run once per input: NaN at a sampled pixel of sample 1's backward flow / of its disparity.  The call returns (every loop
+    is bounded); sample 0's poses, info and loss keep their bits."""
+    from unsupervised_depth_opticalflow_egomotion_amd import pnp
+    key = PC.SHAPES[1]
+    case, out = result(key)
+    B = case["B"]
+    pix = int(case["idx"][1, case["pick"][3]])                      # plane d = 0, b = 1, match 3
+    fb, dt = case["flow_bwd"].clone(), case["disp_t"].clone()
+    if where == "flow":
+        fb[1, 0].view(-1)[pix] = float("nan")
+    else:
+        dt[1, 0].view(-1)[pix] = float("nan")
+    bad = raw_ransac(case, flow_bwd=fb, disp_t=dt)
+    for plane in (0, 2):                                            # sample 0, both directions
+        assert torch.equal(bad["P64"][plane], out["P64"][plane]) and torch.equal(bad["info"][plane], out["info"][plane]), plane
+    if where == "flow":                                             # the forward direction of sample 1 did not read the flow
+        assert torch.equal(bad["P64"][3], out["P64"][3])
+    pose = PC.pose_vectors(case).cuda()
+    with torch.no_grad():
+        loss = pnp.PnpLossFn.apply(pose, bad["P32"].cuda(), 1.0).cpu()
+        good = pnp.PnpLossFn.apply(pose, out["P32"].cuda(), 1.0).cpu()
+    assert bool(torch.isfinite(loss[0])) and G.bits_equal(loss[0:1], good[0:1])
+
+
+def test_two_runs_give_the_same_bits_and_the_wrapper_agrees():
+    from unsupervised_depth_opticalflow_egomotion_amd import pnp
+    key = PC.SHAPES[3]
+    case, out = result(key)
+    again = raw_ransac(case, offsets=(3, 0, 1, 0))
+    assert torch.equal(again["P64"], out["P64"]) and torch.equal(again["info"], out["info"]) and torch.equal(again["counts"], out["counts"])
+    P32, P64, info, ws = pnp.pnp_ransac(case["flow_bwd"].cuda(), case["flow_fwd"].cuda(), case["disp_t"].cuda(), case["idx"].cuda(),
+                                        case["pick"].cuda(), case["sets"].cuda(), case["K"].cuda(), case["K_inv"].cuda(),
+                                        iters=PC.ITERS, thresh=PC.THRESH, return_ws=True)
+    assert torch.equal(P64.cpu(), out["P64"]) and G.bits_equal(P32, out["P32"]) and torch.equal(info.cpu(), out["info"])
+    assert ws.numel() == pnp.workspace_sections(case["B"], case["num"], case["hyp"])["bytes"]
+
+    def loss_and_grad():
+        p = PC.pose_vectors(case).cuda().requires_grad_(True)
+        loss = pnp.PnpLossFn.apply(p, P32, 1.0)
+        loss.sum().backward()
+        return loss.detach(), p.grad
+    (l1, g1), (l2, g2) = loss_and_grad(), loss_and_grad()
+    assert G.bits_equal(l1, l2) and G.bits_equal(g1, g2)
+    with pytest.raises(ValueError):
+        pnp.pnp_ransac(case["flow_bwd"].cuda(), case["flow_fwd"].cuda(), case["disp_t"].cuda(), case["idx"].cuda(),
+                       case["pick"].cuda()[:5], case["sets"].cuda(), case["K"].cuda(), case["K_inv"].cuda())
+
+
+def test_properties_on_the_products_own_sets():
+    """``minimal_sets_device(k=6)``'s draw (with replacement: some sets repeat an index and only lose the vote): the pose is no
+    further from the analytic one than twice the composition on the same input."""
+    from unsupervised_depth_opticalflow_egomotion_amd import pnp
+    case = PC.make_case(PC.SHAPES[2])
+    B, num = case["B"], case["num"]
+    m = PC.solvers()
+    sets = m.minimal_sets_device(B, num, torch.device("cuda"), k=6)
+    assert tuple(sets.shape) == (B, 256, 6) and any(row.unique().numel() < 6 for row in sets.cpu().reshape(-1, 6))
+    _, P64, info = pnp.pnp_ransac(case["flow_bwd"].cuda(), case["flow_fwd"].cuda(), case["disp_t"].cuda(), case["idx"].cuda(),
+                                  case["pick"].cuda(), sets, case["K"].cuda(), case["K_inv"].cuda())
+    comp = PC.composition_of(case, case["x"], case["X"], sets=sets.cpu())["P"]
+    P64 = P64.cpu()
+    for p in range(2 * B):
+        dist = lambda Q: float((Q[p] - case["P_true"][p]).abs().max())   # noqa: E731
+        assert dist(P64) <= 2.0 * dist(comp), (p, dist(P64), dist(comp))
+    assert int(info[:, 1].min()) >= 6

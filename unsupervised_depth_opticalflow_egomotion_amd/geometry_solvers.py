@@ -22,11 +22,11 @@
   1-pixel consensus set -- then a Levenberg-Marquardt refinement on SE(3) over that set (float64 inside), same
   (T, axis-angle) output convention; property tests (30 % gross outliers, pose within 1e-2).
 
-``Model_geometry.forward`` reaches none of these torch compositions (the reference keeps the calls commented, :939-951).  Two
-of the three lines train through fused kernels behind a switch instead: ``loss_triangle`` (cfg ``enable_triangle``,
-triangulate.py) and ``loss_eight_point`` (cfg ``enable_eight_point``, eight_point.py; FM_RANSAC only, with the minimal sets of
-``_minimal_sets`` held on the device by ``minimal_sets_device``).  The compositions here are their cross-checks;
-``loss_pnp`` stays a placeholder."""
+``Model_geometry.forward`` reaches none of these torch compositions (the reference keeps the calls commented, :939-951).  All
+three lines train through fused kernels behind a switch instead: ``loss_triangle`` (cfg ``enable_triangle``, triangulate.py),
+``loss_eight_point`` (cfg ``enable_eight_point``, eight_point.py; FM_RANSAC only) and ``loss_pnp`` (cfg ``enable_pnp``, pnp.py;
+the robust branch of ``pnp``), the last two with the minimal sets of ``_minimal_sets`` held on the device by
+``minimal_sets_device``.  The compositions here are their cross-checks."""
 import torch
 import torch.nn.functional as F
 
@@ -225,13 +225,14 @@ class GeometrySolvers:
         g.manual_seed(int(self.ransac_seed) + 1000003 * n + 7919 * k)
         return torch.randint(0, n, (b, int(self.ransac_iters), k), generator=g).to(device)
 
-    def minimal_sets_device(self, b, n, device):
-        """``_minimal_sets(b, n, 8, ...)`` as an int32 device tensor [b,h,8], drawn once per (b, n, device, ransac_seed,
-        ransac_iters) and kept: a step uploads nothing, and a captured graph reads the sets by address."""
+    def minimal_sets_device(self, b, n, device, k=8):
+        """``_minimal_sets(b, n, k, ...)`` as an int32 device tensor [b,h,k] (k = 8: the eight-point term's sets, 6: the PnP
+        term's), drawn once per (b, n, device, ransac_seed, ransac_iters, k) and kept: a step uploads nothing, and a captured
+        graph reads the sets by address."""
         cache = self.__dict__.setdefault("_minimal_sets_cache", {})
-        key = (int(b), int(n), str(device), int(self.ransac_seed), int(self.ransac_iters))
+        key = (int(b), int(n), str(device), int(self.ransac_seed), int(self.ransac_iters), int(k))
         if key not in cache:
-            cache[key] = self._minimal_sets(b, n, 8, "cpu").to(torch.int32).to(device).contiguous()
+            cache[key] = self._minimal_sets(b, n, int(k), "cpu").to(torch.int32).to(device).contiguous()
         return cache[key]
 
     def compute_fundmental_mat(self, matches, pose_vec=None, intrinsics=None, intrinsics_inverse=None, robust=True):

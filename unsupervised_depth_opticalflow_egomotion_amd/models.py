@@ -168,6 +168,8 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         self.enable_triangle = bool(getattr(cfg, "enable_triangle", False))
         # the eight-point term the reference keeps commented (model_geometry.py:949-950); off = placeholder
         self.enable_eight_point = bool(getattr(cfg, "enable_eight_point", False))
+        # the PnP term the reference keeps commented (model_geometry.py:944-945); off = placeholder
+        self.enable_pnp = bool(getattr(cfg, "enable_pnp", False))
         self.ransac_iters = int(getattr(cfg, "geometric_ransac_iters", GeometrySolvers.ransac_iters))
         self.ransac_seed = int(getattr(cfg, "geometric_ransac_seed", GeometrySolvers.ransac_seed))
         if self.enable_eight_point and self.dataset == "nyuv2":
@@ -302,6 +304,27 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         loss = eight_point.EightPointLossFn.apply(E, K, K_inv, F32)
         return (loss, F64) if return_F else loss
 
+    def pnp_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, K_inv, draw=None, return_pose=False):
+        """``loss_pnp`` of the commented call site (model_geometry.py:944-945) -> (B,), enabled by ``cfg.enable_pnp``:
+        ``compute_pnp_loss`` of both directions on the matches of ``geometric_draw`` (``draw`` = (idx, pick) of this step when
+        another geometric term has drawn already), as fused launches (pnp.py): the robust pose of the back-projected matches --
+        ``ransac_iters`` six-point hypotheses from sets held on the device (``minimal_sets_device(k=6)``), the 1-pixel consensus,
+        20 + 10 Levenberg-Marquardt iterations, detached as in the reference -- and the L1 loss against the pose vector, the
+        rotation part weighted by ``cfg.pose_beta``.  The gradient reaches the pose alone.  No host read, capturable, bitwise
+        reproducible.  The mean over the batch is the reference's scalar.
+
+        Deviations: pnp.py's docstring (line 509's ``K[0]`` for every sample and the (T, axis-angle) against (translation, Euler)
+        comparison kept as written; the point formed in double; the triangulation term's draw deviations; cv2 cannot be pinned);
+        geom mode only.  ``return_pose``: also the step's poses [2B,6] float64."""
+        from . import pnp
+        B = flow_bwd0.shape[0]
+        idx, pick = draw if draw is not None else self.geometric_draw(disp_t0, pose, flow_bwd0, flow_fwd0, K)
+        sets = self.minimal_sets_device(B, int(pick.shape[0]), flow_bwd0.device, k=6)
+        K0 = K[:1].detach().expand(B, 3, 3).contiguous()          # line 509: K[0] projects every sample
+        P32, P64, _ = pnp.pnp_ransac(flow_bwd0, flow_fwd0, disp_t0, idx, pick, sets, K0, K_inv, iters=20, thresh=1.0)
+        loss = pnp.PnpLossFn.apply(pose, P32, float(getattr(self, "beta", 1)))
+        return (loss, P64) if return_pose else loss
+
     def triangle_term(self, disp_l0, disp_t0, disp_r0, pose, flow_bwd0, flow_fwd0, K, K_inv, return_draw=False):
         """``loss_triangle`` of the commented call site (model_geometry.py:939-940) -> (B,), enabled by
         ``cfg.enable_triangle``: the matches of both directions are sampled as ``sample_match`` samples them from
@@ -358,7 +381,8 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         loss_pack = LossRows({k: (active[k] if k in active else _zeros2(dev)) for k in LOSS_ORDER_GEOM})
         loss_pack.rows = active.rows
         tri, eight = getattr(self, "enable_triangle", False), getattr(self, "enable_eight_point", False)
-        if tri or eight:        # one selection and one draw per step, whichever terms are on
+        pnp_on = getattr(self, "enable_pnp", False)
+        if tri or eight or pnp_on:        # one selection and one draw per step, whichever terms are on
             Kc, Kic = K.contiguous(), K_inv.contiguous()
             idx, pick = self.geometric_draw(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc)
             self.triangle_draw = (idx, pick)      # the set and the draw of this step (triangle_term_torch takes them)
@@ -369,6 +393,10 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
                 loss_pack["loss_eight_point"], F64 = self.eight_point_term(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc, Kic,
                                                                            draw=(idx, pick), return_F=True)
                 self.eight_point_F = F64.detach()     # the step's fundamental matrices [2B,3,3] (plane d*B + b)
+            if pnp_on:
+                loss_pack["loss_pnp"], P64 = self.pnp_term(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc, Kic, draw=(idx, pick),
+                                                           return_pose=True)
+                self.pnp_pose = P64.detach()          # the step's poses [2B,6] = (T, axis-angle) (plane d*B + b)
 
         def u8(*names):
             """sample 0, scale 0 of the product of the named masks, decoded from the 1-byte mask pack only when the
