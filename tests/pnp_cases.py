@@ -43,6 +43,20 @@ SEEDS = {
 }
 SHAPES = tuple(sorted(SEEDS))
 FALLBACK = ((2, 13, 19, 72, 70, 33, True), 1)          # found with find_seed(*key, fallback=True)
+# The edge cases, name -> (key, seed, fallback, rot), found with find_seed(*key, fallback=fallback, rot=rot): "zero" -- 24 matches
+# and 4 hypotheses leave two planes without a single vote (best count 0, winner slot 0), where both fall-backs run; "rot0.3" --
+# rotations of up to 0.3 rad per axis; "rot0" -- none at all and no noise, so the final axis-angle lies in so3_log's series branch;
+# "tiles" -- num exactly one match tile (no second block), hyp exactly two hypothesis tiles; "b1" / "b3" -- one sample and an odd
+# number of them.
+EDGE_SEEDS = {
+    "zero": ((2, 12, 20, 72, 24, 4, True), 0, True, 0.02),
+    "rot0.3": ((2, 12, 20, 72, 64, 32, True), 0, False, 0.3),
+    "rot0": ((2, 12, 20, 72, 64, 32, False), 0, False, 0.0),
+    "tiles": ((2, 20, 24, 320, 256, 128, True), 0, False, 0.02),
+    "b1": ((1, 12, 20, 72, 64, 32, True), 0, False, 0.02),
+    "b3": ((3, 12, 20, 72, 64, 64, True), 1, False, 0.02),
+}
+EDGE_SHAPES = tuple(sorted(EDGE_SEEDS))
 
 
 def solvers(sets=None):
@@ -55,8 +69,9 @@ def solvers(sets=None):
     return m
 
 
-def build(seed, B, H, W, k, num, hyp, noisy):
-    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them."""
+def build(seed, B, H, W, k, num, hyp, noisy, rot=0.02):
+    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them.  ``rot``: the range of each of the
+    pose's three rotation angles (the default draws today's cases bit for bit)."""
     from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers as S
     rng = np.random.default_rng(seed)
     K = np.zeros((B, 3, 3))
@@ -75,7 +90,7 @@ def build(seed, B, H, W, k, num, hyp, noisy):
         for d in range(2):
             sign = rng.choice([-1.0, 1.0], 2)
             t = np.array([sign[0] * rng.uniform(1.0, 1.4), sign[1] * rng.uniform(0.7, 1.0), rng.uniform(-0.3, 0.3)])
-            R = _rotation(rng.uniform(-0.02, 0.02, 3))
+            R = _rotation(rng.uniform(-rot, rot, 3))
             pose[d, b, :, :3], pose[d, b, :, 3] = R, t
             p = np.einsum("ij,jhw->ihw", K[b] @ R, X) + (K[b] @ t)[:, None, None]
             u, v = p[0] / p[2] - xs, p[1] / p[2] - ys
@@ -232,10 +247,11 @@ def well_conditioned(f, fallback=False):
     return ok and (f["best_min"] < 6 if fallback else f["consensus"] >= 6)
 
 
-def find_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, fallback=False):
-    """The first seed from ``start`` whose case meets the conditions (run once on the CPU; the result goes into SEEDS / FALLBACK)."""
+def find_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, fallback=False, rot=0.02):
+    """The first seed from ``start`` whose case meets the conditions (run once on the CPU; the result goes into SEEDS / FALLBACK /
+    EDGE_SEEDS)."""
     for seed in range(start, start + tries):
-        if well_conditioned(conditions(build(seed, B, H, W, k, num, hyp, noisy)), fallback):
+        if well_conditioned(conditions(build(seed, B, H, W, k, num, hyp, noisy, rot)), fallback):
             return seed
     raise RuntimeError("no seed found")
 
@@ -265,6 +281,13 @@ def make_case(key):
 def fallback_case():
     """The case of FALLBACK: some plane's best count is below 6, so its first refinement runs over all matches; (a)-(d) asserted."""
     return _checked(build(FALLBACK[1], *FALLBACK[0]), True)
+
+
+@functools.lru_cache(maxsize=None)
+def make_edge_case(name):
+    """The case of EDGE_SEEDS[name], likewise: (a)-(e), or (a)-(d) and "some plane's best count is below 6" on a fall-back case."""
+    key, seed, fallback, rot = EDGE_SEEDS[name]
+    return _checked(build(seed, *key, rot=rot), fallback)
 
 
 def pose_vectors(case, seed=0, scale=1.0):

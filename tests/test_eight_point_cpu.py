@@ -82,3 +82,59 @@ def test_the_header_declares_the_new_entries():
         assert lib.dfe_eight_point_ws_bytes(B, num, hyp) == sec["bytes"]
         assert all(sec[n] % 16 == 0 for n in sec)
     assert lib.dfe_eight_point_ws_bytes(0, 8, 8) == 0
+
+
+def _crc(case, names):
+    import zlib
+    c = 0
+    for n in names:
+        c = zlib.crc32(case[n].contiguous().numpy().tobytes(), c)
+    return c
+
+
+def test_the_existing_tables_and_their_draws_are_unchanged():
+    """SHAPES keeps its four keys in their places, and the generator-only tensors of every existing case (the camera matrices:
+    the first draws; idx, pick and sets: the last) carry the checksums taken before the edge table existed."""
+    want = {(2, 12, 20, 72, 64, 32, False): (0, 2623675490), (2, 12, 20, 72, 64, 32, True): (1, 2804939302),
+            (2, 13, 19, 72, 70, 33, True): (0, 3405646239), (2, 20, 24, 320, 300, 70, True): (1, 2126196865)}
+    assert EC.SHAPES == tuple(sorted(want)) and EC.SEEDS == {k: v[0] for k, v in want.items()}
+    for key, (seed, crc) in want.items():
+        assert _crc(EC.build(seed, *key), ("K", "idx", "pick", "sets")) == crc, key
+
+
+@pytest.mark.parametrize("name", EC.EDGE_SHAPES)
+def test_the_edge_cases_meet_their_conditions(name):
+    (B, H, W, k, num, hyp, noisy), seed, fallback = EC.EDGE_SEEDS[name]
+    case = EC.make_edge_case(name)                                  # asserts the conditions itself
+    f, c = case["figures"], case["comp"]
+    assert f["api_equal"] and f["margin"] >= EC.MARGIN and f["same_set"] and f["gap"] >= EC.GAP and f["sep"] >= 1e-7
+    assert EC.well_conditioned(f, fallback) and not EC.well_conditioned(f, not fallback)
+    assert case["idx"].dtype == torch.int32 and tuple(case["idx"].shape) == (2 * B, k)
+    assert case["pick"].unique().numel() == num and tuple(case["sets"].shape) == (B, hyp, 8)
+    assert all(row.unique().numel() == 8 for row in case["sets"].reshape(-1, 8))
+    first, second = (c["n1raw"] < 8).tolist(), (c["n2raw"] < 8).tolist()
+    tiles = "num %d = %g match tiles, hyp %d = %g hypothesis tiles" % (num, num / EC.MATCH_TILE, hyp, hyp / EC.HYP_TILE)
+    print("EDGE eight_point %s seed %d: n1raw %s n2raw %s; first fall-back on planes %s, second on %s; %s; y %.3e"
+          % (name, seed, [int(v) for v in c["n1raw"]], [int(v) for v in c["n2raw"]], [p for p, v in enumerate(first) if v],
+             [p for p, v in enumerate(second) if v], tiles, EC.reference_spread(case)))
+    if name == "both":
+        assert first == [True, False, False, False] and second == [True, False, False, False]
+        assert bool((c["w1"][0] == 1).all()) and torch.equal(c["w2"][0], c["w1"][0])
+    elif name == "second":
+        assert first == [False] * 4 and second == [False, False, True, False] and torch.equal(c["w2"][2], c["w1"][2])
+        assert not bool((c["w1"][2] == 1).all())                   # the kept set is a proper consensus, not "all matches"
+    else:
+        assert f["consensus"] >= 8 and not any(first) and not any(second)
+    if name == "tiles":
+        assert num == EC.MATCH_TILE and hyp == 2 * EC.HYP_TILE
+    if name in ("b1", "b3"):
+        assert B == int(name[1]) and tuple(c["F"].shape) == (2 * B, 3, 3)
+    assert bool((c["F"][:, 2, 2] == 1.0).all())
+
+
+def test_the_reference_spread_is_rounding_noise_on_the_existing_cases():
+    """y of the F bound: ``eigh`` of the normal matrix against ``svd`` of the design matrix, both float64.  On the isolated null
+    directions the helper asserts it stays orders below the distance to the truth."""
+    for key in EC.SHAPES:
+        y = EC.reference_spread(EC.make_case(key))
+        assert 0.0 <= y < 1e-9, (key, y)

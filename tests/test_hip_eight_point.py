@@ -3,13 +3,17 @@
 tests/eight_point_cases.py: (B, H, W, k, num, hyp) = (2, 12, 20, 72, 64, 32) without and with noise, (2, 13, 19, 72, 70, 33) and
 (2, 20, 24, 320, 300, 70) -- num above the scoring kernel's match tile (EP_MATCH_TILE = 256: two blocks per plane, the second
 partly filled) and hyp above its hypothesis tile (EP_HYP_TILE = 64) and no multiple of it.  Every buffer of the raw entry points
-is carved out of a guarded one.
+is carved out of a guarded one.  The edge cases (EC.EDGE_SEEDS): both fall-backs of the consensus (fewer than 8 votes: all
+matches; fewer than 8 inliers of the first refit: its set is kept), num = 256 and hyp = 128 (exactly one match tile and two
+hypothesis tiles), B = 1 and B = 3.
 
 Votes and weights are integers and the cases keep every residual a relative 1e-6 away from the threshold: they must be EQUAL.
 ``F64``: max |F - F_comp| / max |F_comp| over all cases measured on the device is 1.786e-11
 (profiles/eight_point_ebound.txt); F_BOUND is 16 x that -- the headroom is for another eigen-iteration path under another
 compiler -- and is asserted to lie below the composition's own distance to ``F_true`` on the noisy cases.  Loss and gradient:
-the project's written tolerances, 5e-6 relative and 2e-5 of the gradient's scale."""
+the project's written tolerances, 5e-6 relative and 2e-5 of the gradient's scale.  An edge case is held to
+max(F_BOUND, 16 x y), y = the float64 composition's own spread on that case between ``eigh`` of the normal matrix and ``svd``
+of the design matrix (EC.reference_spread, CPU only; profiles/eight_point_ebound.txt)."""
 import ctypes
 import functools
 
@@ -24,10 +28,18 @@ pytestmark = pytest.mark.gpu
 F_MEASURED = 1.786e-11
 F_BOUND = 16.0 * F_MEASURED
 P = ctypes.c_void_p
+WEIGHTS_OF = {1: (0.7,), 2: (0.7, 1.3), 3: (0.7, 1.3, 0.9)}         # a different cotangent per sample
 
 
 def _i32(carved):
     return carved.view.contiguous().view(torch.int32).cpu()
+
+
+def _doubles_written(carved):
+    """``Carved.written`` for a buffer of doubles: every double finite and neither of its words the sentinel.  (``written`` reads
+    the words as floats, and the low word of a finite double is a NaN or an infinity once in 128 doubles: seen at B = 3.)"""
+    words = _i32(carved)
+    return bool(torch.isfinite(carved.view.contiguous().view(torch.float64)).all()) and bool((words != G.SENTINEL).all())
 
 
 def raw_ransac(case, sets=None, flow_bwd=None, flow_fwd=None, offsets=(1, 2, 3, 2)):
@@ -57,13 +69,20 @@ def raw_ransac(case, sets=None, flow_bwd=None, flow_fwd=None, offsets=(1, 2, 3, 
     return dict(F64=F64.view.contiguous().view(torch.float64).cpu().reshape(2 * B, 3, 3), F32=F32.cpu().reshape(2 * B, 3, 3),
                 info=_i32(info).reshape(2 * B, 4), counts=sl("counts", 2 * B * hyp).reshape(2 * B, hyp),
                 w1=sl("w1", 2 * B * num).reshape(2 * B, num), w2=sl("w2", 2 * B * num).reshape(2 * B, num),
-                written=F64.written() and F32.written() and info.written())
+                written=_doubles_written(F64) and F32.written() and info.written())
 
 
 @functools.lru_cache(maxsize=None)
 def result(key):
     """(case with its float64 composition, the kernels' outputs): computed once, shared, never changed."""
     case = EC.make_case(key)
+    return case, raw_ransac(case)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_result(name):
+    """``result`` for a case of EC.EDGE_SEEDS."""
+    case = EC.make_edge_case(name)
     return case, raw_ransac(case)
 
 
@@ -82,6 +101,46 @@ def test_votes_sets_and_info_equal_the_composition(key):
     assert torch.equal(info[:, 0], c["best"]) and torch.equal(info[:, 1], c["counts"].max(1)[0])
     assert torch.equal(info[:, 2], c["w1"].sum(1).long()) and torch.equal(info[:, 3], c["w2"].sum(1).long())
     assert torch.equal(info[:, 1], out["w1"].sum(1).long())                     # the consensus is the winner's inlier set (>= 8)
+
+
+@pytest.mark.parametrize("name", EC.EDGE_SHAPES)
+def test_edge_votes_sets_and_info_equal_the_composition(name):
+    case, out = edge_result(name)
+    c, num = case["comp"], case["num"]
+    assert out["written"]
+    assert torch.equal(out["counts"].long(), c["counts"])
+    assert torch.equal(out["w1"].long(), c["w1"].long()) and torch.equal(out["w2"].long(), c["w2"].long())
+    info = out["info"].long()
+    assert torch.equal(info[:, 0], c["best"]) and torch.equal(info[:, 1], c["counts"].max(1)[0])
+    assert torch.equal(info[:, 2], c["w1"].sum(1).long()) and torch.equal(info[:, 3], c["w2"].sum(1).long())
+    first, second = c["n1raw"] < 8, c["n2raw"] < 8
+    assert torch.equal(info[~first, 1], out["w1"][~first].sum(1).long())        # a consensus is the winner's inlier set
+    if EC.EDGE_SEEDS[name][2]:
+        assert bool((first | second).any())
+    else:
+        assert not bool((first | second).any())
+    assert bool((info[first, 1] < 8).all()) and bool((info[first, 2] == num).all()) and bool((out["w1"][first] == 1).all())
+    assert torch.equal(out["w2"][second], out["w1"][second]) and torch.equal(info[second, 3], info[second, 2])
+    if name == "both":
+        assert first.tolist() == [True, False, False, False] and second.tolist() == [True, False, False, False]
+    if name == "second":
+        assert not bool(first.any()) and second.tolist() == [False, False, True, False]
+
+
+@pytest.mark.parametrize("name", EC.EDGE_SHAPES)
+def test_edge_f64_against_the_composition(name):
+    case, out = edge_result(name)
+    ref = case["comp"]["F"]
+    assert bool(torch.isfinite(out["F64"]).all())
+    y = EC.reference_spread(case)
+    bound = max(F_BOUND, 16.0 * y)
+    e = rel_err(out["F64"], ref)
+    dist = min(float((ref[p] - case["F_true"][p]).abs().max() / case["F_true"][p].abs().max()) for p in range(ref.shape[0]))
+    print("EBOUND eight_point F64 edge %s %s max|dF|/max|F| %.3e; y (eigh against svd, float64) %.3e bound %.3e; the composition's "
+          "distance to F_true: min %.3e" % (name, "x".join(str(int(v)) for v in EC.EDGE_SEEDS[name][0]), e, y, bound, dist))
+    assert bound < dist                     # otherwise the case could not tell the estimate from the truth
+    assert torch.equal(out["F32"], out["F64"].float())
+    assert e <= bound, (e, bound)
 
 
 def test_f64_against_the_composition_and_f32_is_its_rounding():
@@ -161,10 +220,19 @@ def _loss_reference(F64, K, K_inv, pose, weights):
 @pytest.mark.parametrize("scale", [1.0, 40.0])
 def test_loss_and_gradient_against_float64(scale):
     """``scale`` = 40 puts most differences beyond smooth-L1's knee (|d| >= 1), 1 keeps them in the quadratic part."""
+    _loss_against_float64(*result(EC.SHAPES[2]), scale)
+
+
+@pytest.mark.parametrize("scale", [1.0, 40.0])
+@pytest.mark.parametrize("name", ["b1", "b3"])
+def test_loss_and_gradient_at_one_sample_and_three(name, scale):
+    _loss_against_float64(*edge_result(name), scale, tag=" " + name)
+
+
+def _loss_against_float64(case, out, scale, tag=""):
     from unsupervised_depth_opticalflow_egomotion_amd import eight_point, ops
-    case, out = result(EC.SHAPES[2])
     B = case["B"]
-    w = torch.tensor([0.7, 1.3])
+    w = torch.tensor(WEIGHTS_OF[B])
     pose = EC.pose_vectors(case)
     pose[:, :, :3] *= scale
     l64, gpose64, gE64 = _loss_reference(out["F64"], case["K"], case["K_inv"], pose, w)
@@ -181,22 +249,29 @@ def test_loss_and_gradient_against_float64(scale):
     el = float(((loss.detach().double().cpu() - l64).abs() / l64.abs()).max())
     eg = float((p.grad.double().cpu() - gpose64).abs().max() / gpose64.abs().max())
     ee = float((E.grad.double().cpu() - gE64).abs().max() / gE64.abs().max())
-    print("EBOUND eight_point loss scale %g: loss %.3e (5e-6)  dpose %.3e  dE %.3e (2e-5)" % (scale, el, eg, ee))
+    print("EBOUND eight_point loss%s scale %g: loss %.3e (5e-6)  dpose %.3e  dE %.3e (2e-5)" % (tag, scale, el, eg, ee))
     assert el <= 5e-6 and eg <= 2e-5 and ee <= 2e-5
 
 
 def test_loss_entry_points_in_guarded_buffers():
+    _guarded_loss_entry_points([result(key) for key in EC.SHAPES[1:]])
+
+
+def test_loss_entry_points_in_guarded_buffers_at_one_sample_and_three():
+    _guarded_loss_entry_points([edge_result(name) for name in ("b1", "b3")])
+
+
+def _guarded_loss_entry_points(results):
     from unsupervised_depth_opticalflow_egomotion_amd import _lib, eight_point, ops
     lib = _lib.get_lib()
-    for key in EC.SHAPES[1:]:
-        case, out = result(key)
+    for case, out in results:
         B = case["B"]
         with torch.no_grad():
             E = ops.PoseMatsFn.apply(EC.pose_vectors(case).cuda().reshape(2 * B, 6))[1]
             Kt = eight_point.inverse_transposed(case["K"].cuda())
         ins = [G.Carved((2 * B, 9), offset_floats=1, fill=E), G.Carved((B, 9), offset_floats=2, fill=Kt),
                G.Carved((B, 9), offset_floats=3, fill=case["K_inv"]), G.Carved((2 * B, 9), offset_floats=0, fill=out["F32"])]
-        loss, gloss, gE = G.Carved((B,), offset_floats=1), G.Carved((B,), offset_floats=3, fill=torch.tensor([0.7, 1.3])), G.Carved((2 * B, 9), offset_floats=1)
+        loss, gloss, gE = G.Carved((B,), offset_floats=1), G.Carved((B,), offset_floats=3, fill=torch.tensor(WEIGHTS_OF[B])), G.Carved((2 * B, 9), offset_floats=1)
         st = _lib.stream_ptr()
         _lib.check(lib.dfe_eight_point_loss_fwd(*[P(c.ptr) for c in ins], P(loss.ptr), B, st), "fwd")
         _lib.check(lib.dfe_eight_point_loss_bwd(*[P(c.ptr) for c in ins], P(gloss.ptr), P(gE.ptr), B, st), "bwd")

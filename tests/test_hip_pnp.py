@@ -3,7 +3,10 @@ float64 points formed as the operator forms them, on the cases of tests/pnp_case
 32) without and with noise, (2, 13, 19, 72, 70, 33) and (2, 20, 24, 320, 300, 70) -- num above the scoring kernel's match tile
 (PNP_MATCH_TILE = 256: two blocks per plane, the second partly filled) and hyp above its hypothesis tile (PNP_HYP_TILE = 64) and no
 multiple of it -- plus the case whose first refinement falls back to all matches.  Every buffer of the raw entry points is carved
-out of a guarded one.
+out of a guarded one.  The edge cases (PC.EDGE_SEEDS): planes without a single vote (best count 0, winner slot 0, both fall-backs),
+rotations of 0.13 to 0.37 rad and of none at all (so3_log's series branch), num = 256 and hyp = 128 (exactly one match tile and
+two hypothesis tiles), B = 1 and B = 3.  An edge case is held to max(P_BOUND, 10 x y), y = the composition at 40 iterations
+against itself at 20 on that case.
 
 Votes and weights are integers and the cases keep every residual a relative 1e-6 away from the threshold: they must be EQUAL.
 ``P64``: Levenberg-Marquardt's accept test ``cn < cost`` is decided on rounding noise once the iteration has converged, and the
@@ -29,6 +32,7 @@ P_BOUND = 10.0 * P_MEASURED
 TRUE_MEASURED = 1.212e-07
 TRUE_BOUND = 10.0 * TRUE_MEASURED
 P = ctypes.c_void_p
+WEIGHTS_OF = {1: (0.7,), 2: (0.7, 1.3), 3: (0.7, 1.3, 0.9)}         # a different cotangent per sample
 
 
 def _i32(carved):
@@ -76,6 +80,13 @@ def result(key):
     return case, raw_ransac(case)
 
 
+@functools.lru_cache(maxsize=None)
+def edge_result(name):
+    """``result`` for a case of PC.EDGE_SEEDS."""
+    case = PC.make_edge_case(name)
+    return case, raw_ransac(case)
+
+
 def rel_err(Pd, ref):
     """the largest difference of a plane's pose relative to that pose's scale, over the planes"""
     return float(((Pd - ref).abs().amax(1) / ref.abs().amax(1)).max())
@@ -95,6 +106,47 @@ def test_votes_sets_and_info_equal_the_composition(key):
     case, out = result(key)
     _equal_decisions(out, case["comp"])
     assert torch.equal(out["info"][:, 1].long(), out["w1"].sum(1).long())       # the consensus is the winner's inlier set (>= 6)
+
+
+@pytest.mark.parametrize("name", PC.EDGE_SHAPES)
+def test_edge_votes_sets_and_info_equal_the_composition(name):
+    case, out = edge_result(name)
+    c, num = case["comp"], case["num"]
+    _equal_decisions(out, c)
+    first, second = c["n1raw"] < 6, c["n2raw"] < 6
+    info = out["info"].long()
+    assert torch.equal(info[~first, 1], out["w1"][~first].sum(1).long())        # a consensus is the winner's inlier set
+    if name == "zero":                                                           # no hypothesis gets a vote on planes 0 and 2
+        assert first.tolist() == [True, False, True, False] and second.tolist() == [True, False, True, False]
+        for plane in (0, 2):
+            assert info[plane].tolist() == [0, 0, num, num], (plane, info[plane].tolist())
+            assert bool((out["counts"][plane] == 0).all()) and bool((out["w1"][plane] == 1).all()) and bool((out["w2"][plane] == 1).all())
+    else:
+        assert not bool((first | second).any())
+
+
+@pytest.mark.parametrize("name", PC.EDGE_SHAPES)
+def test_edge_p64_against_the_composition(name):
+    case, out = edge_result(name)
+    ref = case["comp"]["P"]
+    assert bool(torch.isfinite(out["P64"]).all())
+    y = rel_err(PC.composition_of(case, case["x"], case["X"], iterations=2 * PC.ITERS)["P"], ref)
+    bound = max(P_BOUND, 10.0 * y)
+    e = rel_err(out["P64"], ref)
+    norms = out["P64"][:, 3:].norm(dim=1)
+    print("EBOUND pnp P64 edge %s %s max|dP|/max|P| %.3e; y (the composition at 40 iterations against itself at 20) %.3e bound %.3e; "
+          "axis-angle norms %.3e to %.3e" % (name, "x".join(str(int(v)) for v in PC.EDGE_SEEDS[name][0]), e, y, bound,
+                                              float(norms.min()), float(norms.max())))
+    assert torch.equal(out["P32"], out["P64"].float())                          # rounded once: bit equality
+    assert e <= bound, (e, bound)
+    if name == "rot0.3":
+        assert float(norms.min()) > 0.1 and float(norms.max()) < 0.6
+    if name == "rot0":                                                          # the series branch, and the analytic pose
+        assert float(norms.max()) < 1e-6
+        et = float((out["P64"] - case["P_true"]).abs().max())
+        ec = float((case["comp"]["P"] - case["P_true"]).abs().max())
+        print("EBOUND pnp noise-free rot 0 max|P - P_true| %.3e (the composition: %.3e) bound %.3e" % (et, ec, TRUE_BOUND))
+        assert et <= TRUE_BOUND, (et, TRUE_BOUND)
 
 
 def test_p64_against_the_composition_and_p32_is_its_rounding():
@@ -169,14 +221,25 @@ def _loss_reference(P64, pose, beta, weights):
 @pytest.mark.parametrize("scale", [1.0, 40.0])
 def test_loss_and_gradient_against_float64(scale):
     """Two pose scales; element (1, 0, 4) of the pose vector equals ``P32`` exactly: sign(0) = 0, the gradient there is 0."""
+    _loss_against_float64(*result(PC.SHAPES[2]), scale, at=1)
+
+
+@pytest.mark.parametrize("scale", [1.0, 40.0])
+@pytest.mark.parametrize("name", ["b1", "b3"])
+def test_loss_and_gradient_at_one_sample_and_three(name, scale):
+    """Element (B - 1, 0, 4) of the pose vector equals ``P32`` exactly, as above."""
+    case, out = edge_result(name)
+    _loss_against_float64(case, out, scale, at=case["B"] - 1, tag=" " + name)
+
+
+def _loss_against_float64(case, out, scale, at, tag=""):
     from unsupervised_depth_opticalflow_egomotion_amd import pnp
-    case, out = result(PC.SHAPES[2])
     B, beta = case["B"], 0.75
-    w = torch.tensor([0.7, 1.3])
+    w = torch.tensor(WEIGHTS_OF[B])
     pose = PC.pose_vectors(case, scale=scale)
-    pose[1, 0, 4] = out["P32"][0 * B + 1, 4]
+    pose[at, 0, 4] = out["P32"][0 * B + at, 4]
     l64, g64 = _loss_reference(out["P32"].double(), pose, beta, w)
-    assert float(g64[1, 0, 4]) == 0.0
+    assert float(g64[at, 0, 4]) == 0.0
     Pc = G.Carved((2 * B, 6), offset_floats=2, fill=out["P32"])
     p = pose.cuda().requires_grad_(True)
     loss = pnp.PnpLossFn.apply(p, Pc.view, beta)
@@ -185,19 +248,26 @@ def test_loss_and_gradient_against_float64(scale):
     assert Pc.intact()
     el = float(((loss.detach().double().cpu() - l64).abs() / l64.abs()).max())
     eg = float((p.grad.double().cpu() - g64).abs().max() / g64.abs().max())
-    print("EBOUND pnp loss scale %g: loss %.3e (5e-6)  dpose %.3e (2e-5)" % (scale, el, eg))
+    print("EBOUND pnp loss%s scale %g: loss %.3e (5e-6)  dpose %.3e (2e-5)" % (tag, scale, el, eg))
     assert el <= 5e-6 and eg <= 2e-5
-    assert float(p.grad[1, 0, 4]) == 0.0 and int((p.grad == 0).sum()) == 1
+    assert float(p.grad[at, 0, 4]) == 0.0 and int((p.grad == 0).sum()) == 1
 
 
 def test_loss_entry_points_in_guarded_buffers():
+    _guarded_loss_entry_points([result(key) for key in PC.SHAPES[1:]])
+
+
+def test_loss_entry_points_in_guarded_buffers_at_one_sample_and_three():
+    _guarded_loss_entry_points([edge_result(name) for name in ("b1", "b3")])
+
+
+def _guarded_loss_entry_points(results):
     from unsupervised_depth_opticalflow_egomotion_amd import _lib
     lib = _lib.get_lib()
-    for key in PC.SHAPES[1:]:
-        case, out = result(key)
+    for case, out in results:
         B = case["B"]
         ins = [G.Carved((B, 2, 6), offset_floats=1, fill=PC.pose_vectors(case)), G.Carved((2 * B, 6), offset_floats=3, fill=out["P32"])]
-        loss, gloss, gp = G.Carved((B,), offset_floats=1), G.Carved((B,), offset_floats=3, fill=torch.tensor([0.7, 1.3])), G.Carved((B, 2, 6), offset_floats=2)
+        loss, gloss, gp = G.Carved((B,), offset_floats=1), G.Carved((B,), offset_floats=3, fill=torch.tensor(WEIGHTS_OF[B])), G.Carved((B, 2, 6), offset_floats=2)
         st = _lib.stream_ptr()
         beta = ctypes.c_float(0.5)
         _lib.check(lib.dfe_pnp_loss_fwd(*[P(c.ptr) for c in ins], P(loss.ptr), B, beta, st), "fwd")

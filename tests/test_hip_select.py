@@ -1,6 +1,9 @@
 """dfe_topk_select (csrc/ops_select.hip) in guarded buffers: the pixel-ordered top-k set of every plane against torch.topk and
 against the numpy restatement of its tie rule, at plane sizes that are no multiple of the wave, the block or the ordered pass's
-chunk (247: one partial chunk; 4099: one chunk of 4096 and three scores), k at both ends and at the training ratio."""
+chunk (247: one partial chunk; 4099: one chunk of 4096 and three scores; 8193: three rounds of the ordered pass, a single score
+in the third, where the double-buffered wave totals are first reused; 12301: four rounds, 13 scores in the last), k at both ends
+and at the training ratio; planes of one repeated value (the largest packed tie count), sets that lie wholly in the first or the
+last round, and 1 and 8 planes."""
 import ctypes
 
 import numpy as np
@@ -12,7 +15,8 @@ from tests import guarded as G
 pytestmark = pytest.mark.gpu
 
 PLANES = 3
-SIZES = (247, 4099)
+SIZES = (247, 4099, 8193, 12301)
+ROUND = 4096                    # scores per round of the ordered pass (SEL_THREADS x SEL_ITEMS)
 
 
 def ks(n):
@@ -99,6 +103,53 @@ def test_nan_and_infinities_rank_as_topk_ranks_them(n):
         got = torch.gather(scores, 1, idx.long()).sort(1)[0]
         want = torch.topk(scores.cuda(), k, dim=1)[0].sort(1)[0].cpu()
         assert torch.equal(torch.isnan(got), torch.isnan(want)) and torch.equal(got.nan_to_num(0.0), want.nan_to_num(0.0)), (n, k)
+
+
+@pytest.mark.parametrize("n", [ROUND, 12301])
+def test_a_plane_of_one_repeated_value_takes_the_first_k(n):
+    """Every score ties: nothing lies above the threshold, a full round counts 4096 equal scores in the packed upper half, and
+    the set is the first k pixels."""
+    value = 0.375
+    scores = torch.full((PLANES, n), value)
+    key = int(np.float32(value).view(np.uint32)) | 0x80000000            # the order-preserving key of a positive score
+    for k in ks(n):
+        idx, rec = run_select(scores, k)
+        assert torch.equal(idx, torch.arange(k, dtype=torch.int32).expand(PLANES, k)), (n, k)
+        want = torch.tensor([key, 0, k, 0], dtype=torch.int64).expand(PLANES, 4)
+        assert torch.equal(rec.long() & 0xffffffff, want), (n, k)
+
+
+@pytest.mark.parametrize("where", ["first", "last"])
+def test_a_set_that_lies_wholly_in_one_round(where):
+    """n = 12301, four rounds: the k largest scores all in the first round (the three later rounds add nothing and must not
+    disturb the positions) or all in the last (every base count stays 0 until then)."""
+    n = 12301
+    g = torch.Generator().manual_seed(13)
+    scores = torch.randperm(PLANES * n, generator=g).float().view(PLANES, n) / 7.0 - 100.0      # distinct, all below 5200
+    lo, hi = (0, ROUND) if where == "first" else (3 * ROUND, n)
+    for k in (1, 7, hi - lo):
+        boosted = scores.clone()
+        for p in range(PLANES):
+            at = lo + torch.randperm(hi - lo, generator=g)[:k]
+            boosted[p, at] += 1.0e4
+        idx, rec = run_select(boosted, k)
+        assert ascending(idx)
+        assert int(idx.min()) >= lo and int(idx.max()) < hi
+        want = torch.topk(boosted.cuda(), k, dim=1)[1].sort(1)[0].cpu().int()
+        assert torch.equal(idx, want), (where, k)
+        assert np.array_equal(idx.numpy(), restated(boosted, k))
+
+
+@pytest.mark.parametrize("planes", [1, 8])
+def test_one_plane_and_eight(planes):
+    n = 8193
+    g = torch.Generator().manual_seed(17 * planes)
+    scores = torch.randint(0, 64, (planes, n), generator=g).float() * 0.25 - 4.0               # ties at every level
+    for k in (int(0.3 * n), n - 1):
+        idx, rec = run_select(scores, k)
+        assert tuple(idx.shape) == (planes, k) and ascending(idx)
+        assert np.array_equal(idx.numpy(), restated(scores, k)), (planes, k)
+        assert bool((rec[:, 1] + rec[:, 2] == k).all())
 
 
 def test_two_runs_give_identical_bits():

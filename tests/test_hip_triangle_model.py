@@ -85,6 +85,40 @@ def test_the_term_equals_the_torch_composition_on_its_own_draw():
     assert ek <= 4.0 * max(ey, 2.0 ** -24), (ek, ey)
 
 
+def test_the_terms_gradients_equal_float64_autograd_on_its_own_draw():
+    """The same rule for the gradients, at the product's own draw: num = 6000 is 24 blocks of points per plane, k = 3993 pixels, so
+    most pixels are drawn more than once.  Reference: float64 autograd on the CPU of ``triangle_term_torch`` behind the oracle's
+    ``pose_vec2mat``; yardstick: the fp32 composition on the device behind ``PoseMatsFn``, as the term itself is; a different
+    cotangent per sample."""
+    from oracle import loss_stack_oracle as O
+    m, x, on = _run_stack(True)
+    idx, pick = m.triangle_draw
+    assert pick.unique().numel() < idx.shape[1] < pick.numel()
+    w = torch.tensor([0.7, 1.3])
+    leaves = dict(flow_bwd=x["fb"][0], flow_fwd=x["ff"][0], disp_l=x["disps"][0][0], disp_t=x["disps"][1][0], disp_r=x["disps"][2][0],
+                  pose=x["pose"])
+    names = list(leaves)
+    got = torch.autograd.grad((on["loss_triangle"] * w.cuda()).sum(), [leaves[n] for n in names])
+
+    def composition(dtype, device, pose_mats):
+        t = {n: leaves[n].detach().to(device=device, dtype=dtype).requires_grad_(True) for n in names}
+        T34 = pose_mats(t["pose"].reshape(4, 6)).view(2, 2, 3, 4)
+        loss = m.triangle_term_torch(t["disp_l"], t["disp_t"], t["disp_r"], T34, t["flow_bwd"], t["flow_fwd"],
+                                     x["K"].to(device=device, dtype=dtype), x["Ki"].to(device=device, dtype=dtype), idx.to(device),
+                                     pick.to(device))
+        return torch.autograd.grad((loss * w.to(device=device, dtype=dtype)).sum(), [t[n] for n in names])
+    yard = composition(torch.float32, dev(), lambda v: ops.PoseMatsFn.apply(v)[0])
+    ref = composition(torch.float64, "cpu", O.pose_vec2mat)
+    torch.cuda.synchronize()
+    for n, g, y, r in zip(names, got, yard, ref):
+        assert g.shape == r.shape and bool(torch.isfinite(g).all()), n
+        scale = float(r.abs().max())
+        ek = float((g.double().cpu() - r).abs().max()) / scale
+        ey = float((y.double().cpu() - r).abs().max()) / scale
+        print("EBOUND triangle_term 2x64x208 d%s kernel %.3e yardstick %.3e (max |ref| %.3e)" % (n, ek, ey, scale))
+        assert scale > 0 and ek <= 4.0 * max(ey, 2.0 ** -24), (n, ek, ey)
+
+
 def test_gradients_reach_every_input_and_repeat_bit_for_bit():
     def grads():
         _, x, lp = _run_stack(True)

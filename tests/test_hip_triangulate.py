@@ -1,7 +1,9 @@
 """The triangulation operator (triangulate.TriangulateFn over csrc/ops_triangulate.hip) against float64 autograd of
 ``Model_geometry.triangle_term_torch`` on the same ``idx`` / ``pick``, on the well-conditioned cases of tests/triangle_cases.py:
 B = 2, planes 12 x 20 and 13 x 19, num = 50 and num = 150 with k = 72 (guaranteed repeats), both align_corners settings, inputs
-in guarded buffers.
+in guarded buffers; and on its edge cases: num = 257, 601 and 51 (one point in a second block of TRI_THREADS = 256; three blocks
+and an odd median rank; an odd rank inside one block), B = 1 and B = 3, samples that the reflection folds twice, and a NaN in
+one sample's flow.
 
 Bound: per tensor the error is normalised by that tensor's largest float64 magnitude, and the kernels are held to
 4 x max(error of the same torch composition in fp32 on the device, 2^-24) -- the margin guarded.check_bound uses for "another
@@ -20,6 +22,8 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = ((12, 20), (13, 19))
 WEIGHTS = (0.7, 1.3)            # d(sum w_b loss_b): a different cotangent per sample
+WEIGHTS_OF = {1: (0.7,), 2: WEIGHTS, 3: (0.7, 1.3, 0.9)}
+BLOCK_EDGES = ((12, 20, False, 257), (13, 19, True, 601), (12, 20, False, 51))
 
 
 def carve(case, name, offset):
@@ -37,16 +41,29 @@ def reference(H, W, ac, num, constant=None):
     return case, pick, ref, yard
 
 
-def run_operator(case, pick, ac, offsets=(0, 1, 2, 3, 1, 2, 3)):
-    """loss [B] and the gradients of sum(w * loss) through TriangulateFn, every fp32 input a view inside a guarded buffer."""
+@functools.lru_cache(maxsize=None)
+def edge_reference(key, num):
+    """``reference`` for a case of TC.EDGE_SEEDS, key = (B, H, W, ac, depth_lo), with B cotangent weights."""
+    case = TC.make_edge_case(key)
+    pick = TC.make_pick(case, num)
+    w = torch.tensor(WEIGHTS_OF[key[0]])
+    ref = TC.torch_term(case, pick, key[3], torch.float64, weights=w)
+    yard = TC.torch_term(case, pick, key[3], torch.float32, device="cuda", weights=w)
+    return case, pick, ref, yard
+
+
+def run_operator(case, pick, ac, offsets=(0, 1, 2, 3, 1, 2, 3), replace=None):
+    """loss [B] and the gradients of sum(w * loss) through TriangulateFn, every fp32 input a view inside a guarded buffer;
+    ``replace``: tensors that stand in for the case's own."""
     from unsupervised_depth_opticalflow_egomotion_amd import triangulate
     names = TC.GRAD_NAMES + ("K",)
+    case = dict(case, **(replace or {}))
     bufs = {n: carve(case, n, o) for n, o in zip(names, offsets)}
     bufs["K_inv"] = carve(case, "K_inv", 0)
     t = {n: bufs[n].view.requires_grad_(n in TC.GRAD_NAMES) for n in bufs}
     loss = triangulate.triangulate_loss(t["flow_bwd"], t["flow_fwd"], t["disp_t"], t["disp_l"], t["disp_r"], t["T34"], t["K"],
                                         t["K_inv"], case["idx"].cuda(), pick.cuda(), ac)
-    grads = torch.autograd.grad((loss * torch.tensor(WEIGHTS, device="cuda")).sum(), [t[n] for n in TC.GRAD_NAMES])
+    grads = torch.autograd.grad((loss * torch.tensor(WEIGHTS_OF[case["B"]], device="cuda")).sum(), [t[n] for n in TC.GRAD_NAMES])
     torch.cuda.synchronize()
     assert all(b.intact() for b in bufs.values())
     return loss.detach(), dict(zip(TC.GRAD_NAMES, (g.detach() for g in grads)))
@@ -74,6 +91,65 @@ def test_forward_and_backward_against_float64(hw, ac, num):
     for n in TC.GRAD_NAMES:
         assert grads[n].shape == g64[n].shape
         ebound(tag + " d" + n, grads[n], g32[n], g64[n])
+
+
+def _against_float64(tag, case, pick, ac, ref, yard):
+    (l64, g64), (l32, g32) = ref, yard
+    loss, grads = run_operator(case, pick, ac)
+    ebound(tag + " loss", loss, l32, l64)
+    for n in TC.GRAD_NAMES:
+        assert grads[n].shape == g64[n].shape
+        ebound(tag + " d" + n, grads[n], g32[n], g64[n])
+
+
+@pytest.mark.parametrize("edge", BLOCK_EDGES)
+def test_block_edges_against_float64(edge):
+    """num = 257: one point in the second block, whose T34 partial sums are otherwise zeros; 601: three blocks per plane (the
+    per-block partials and the finisher's loop over them, three elements per thread in the statistics) and the median of an odd
+    count; 51: an odd count inside one block."""
+    H, W, ac, num = edge
+    case, pick, ref, yard = reference(H, W, ac, num)
+    if num > case["k"]:
+        assert pick.unique().numel() < num                 # guaranteed repeats
+    assert num % 2 == 1                                    # the lower median of an odd count is the median
+    _against_float64("tri %dx%d ac%d num%d" % (H, W, ac, num), case, pick, ac, ref, yard)
+
+
+@pytest.mark.parametrize("key", [k for k in TC.EDGE_SHAPES if k[0] != 2])
+def test_one_sample_and_three_against_float64(key):
+    B, H, W, ac, _ = key
+    case, pick, ref, yard = edge_reference(key, 150)
+    assert case["B"] == B and tuple(ref[0].shape) == (B,) and pick.unique().numel() < 150
+    _against_float64("tri B%d %dx%d ac%d num150" % (B, H, W, ac), case, pick, ac, ref, yard)
+
+
+@pytest.mark.parametrize("key", [k for k in TC.EDGE_SHAPES if k[4] < 2.0])
+def test_samples_folded_twice_against_float64(key):
+    """A depth floor of 0.5: some reprojections lie two and more plane sizes outside the plane (counted in float64 by
+    tests/test_triangle_cpu.py), so the reflection's fold parity decides the sample and the sign of its derivative."""
+    B, H, W, ac, lo = key
+    case, pick, ref, yard = edge_reference(key, 150)
+    assert TC.folds(case, ac, pick)[1] >= 1
+    _against_float64("tri far %dx%d ac%d num150" % (H, W, ac), case, pick, ac, ref, yard)
+
+
+def test_a_nan_in_one_samples_flow():
+    """Run once: NaN at one drawn pixel of sample 1's backward flow.  Sample 0's loss and its T34 gradient keep their bits, and so
+    does sample 1's forward direction's; sample 1's loss and its backward direction's T34 gradient are non-finite.  The dense
+    gradients share one scatter bound per call, which the NaN wins (k_tri_bwd_points): every element of all five, both
+    samples', is NaN -- the step is lost, never silently wrong."""
+    ac = False
+    case, pick, _, _ = reference(12, 20, ac, 150)
+    good_loss, good = run_operator(case, pick, ac)
+    fb = case["flow_bwd"].clone()
+    pix = int(case["idx"][1, pick[3]])                      # plane d = 0, b = 1, draw 3
+    fb[1, 0].view(-1)[pix] = float("nan")
+    loss, grads = run_operator(case, pick, ac, replace={"flow_bwd": fb})
+    assert G.bits_equal(loss[0:1], good_loss[0:1]) and not bool(torch.isfinite(loss[1]))
+    assert G.bits_equal(grads["T34"][0], good["T34"][0]) and G.bits_equal(grads["T34"][1, 1], good["T34"][1, 1])
+    assert not bool(torch.isfinite(grads["T34"][1, 0]).any())
+    for n in TC.GRAD_NAMES[:5]:
+        assert bool(torch.isnan(grads[n]).all()), n
 
 
 @pytest.mark.parametrize("ac", [False, True])
@@ -115,12 +191,22 @@ def test_two_runs_give_the_same_bits(ac):
 
 
 def test_outputs_and_workspace_in_guarded_buffers():
+    _raw_entry_points(150)
+
+
+def test_outputs_and_workspace_with_three_blocks_per_plane():
+    """num = 601: three blocks per plane in the workspace's last section, three rounds of every strided loop of the statistics."""
+    _raw_entry_points(601)
+
+
+def _raw_entry_points(num):
     """The raw entry points with every output and workspace carved: guards intact, every element of the outputs written, and the
     same bits as through the autograd wrapper."""
     from unsupervised_depth_opticalflow_egomotion_amd import _lib
     lib = _lib.get_lib()
-    ac, num = 0, 150
-    case, pick, _, _ = reference(13, 19, False, num)
+    ac = 0
+    case = TC.make_case(13, 19, False)
+    pick = TC.make_pick(case, num)
     B, H, W, k = case["B"], case["H"], case["W"], case["k"]
     P = ctypes.c_void_p
     ins = [carve(case, n, o) for n, o in zip(("flow_bwd", "flow_fwd", "disp_t", "disp_l", "disp_r", "T34", "K", "K_inv"), (1, 2, 3, 0, 1, 2, 3, 0))]

@@ -97,3 +97,64 @@ def test_the_header_declares_the_new_entries():
         assert lib.dfe_pnp_ws_bytes(B, num, hyp) == sec["bytes"]
         assert all(sec[n] % 16 == 0 for n in sec)
     assert lib.dfe_pnp_ws_bytes(0, 6, 6) == 0
+
+
+def _crc(case, names):
+    import zlib
+    c = 0
+    for n in names:
+        c = zlib.crc32(case[n].contiguous().numpy().tobytes(), c)
+    return c
+
+
+def test_the_new_keyword_leaves_the_existing_cases_bits():
+    """``rot`` defaults to the former constant; SHAPES and FALLBACK keep their entries; the generator-only tensors of every
+    existing case (the camera matrices: the first draws; idx, pick and sets: the last) carry the checksums taken before the
+    keyword existed, and the default equals the explicit 0.02 in every tensor."""
+    import inspect
+    assert inspect.signature(PC.build).parameters["rot"].default == 0.02
+    want = {(2, 12, 20, 72, 64, 32, False): (0, 2477022648), (2, 12, 20, 72, 64, 32, True): (0, 2812100972),
+            (2, 13, 19, 72, 70, 33, True): (0, 4139742225), (2, 20, 24, 320, 300, 70, True): (0, 998629082)}
+    assert PC.SHAPES == tuple(sorted(want)) and PC.SEEDS == {k: v[0] for k, v in want.items()}
+    assert PC.FALLBACK == ((2, 13, 19, 72, 70, 33, True), 1)
+    for key, (seed, crc) in want.items():
+        case = PC.build(seed, *key)
+        assert _crc(case, ("K", "idx", "pick", "sets")) == crc, key
+        explicit = PC.build(seed, *key, rot=0.02)
+        assert all(torch.equal(case[n], explicit[n]) for n in case if torch.is_tensor(case[n]))
+
+
+@pytest.mark.parametrize("name", PC.EDGE_SHAPES)
+def test_the_edge_cases_meet_their_conditions(name):
+    (B, H, W, k, num, hyp, noisy), seed, fallback, rot = PC.EDGE_SEEDS[name]
+    case = PC.make_edge_case(name)                                  # asserts (a)-(d), and (e) or "some plane falls back"
+    f, c = case["figures"], case["comp"]
+    assert f["api_equal"] and f["margin"] >= PC.MARGIN and f["zmargin"] >= PC.MARGIN and f["route_free"] and f["same_set"]
+    assert PC.well_conditioned(f, fallback) and not PC.well_conditioned(f, not fallback)
+    assert case["idx"].dtype == torch.int32 and tuple(case["idx"].shape) == (2 * B, k)
+    assert case["pick"].unique().numel() == num and tuple(case["sets"].shape) == (B, hyp, 6)
+    assert all(row.unique().numel() == 6 for row in case["sets"].reshape(-1, 6))
+    first, second = (c["n1raw"] < 6).tolist(), (c["n2raw"] < 6).tolist()
+    norms = c["P"][:, 3:].norm(dim=1)
+    y = ((PC.composition_of(case, case["x"], case["X"], iterations=2 * PC.ITERS)["P"] - c["P"]).abs().amax(1) / c["P"].abs().amax(1))
+    tiles = "num %d = %g match tiles, hyp %d = %g hypothesis tiles" % (num, num / PC.MATCH_TILE, hyp, hyp / PC.HYP_TILE)
+    print("EDGE pnp %s seed %d: n1raw %s n2raw %s; first fall-back on planes %s, second on %s; %s; axis-angle norms %.3e to %.3e; "
+          "y per plane %s" % (name, seed, [int(v) for v in c["n1raw"]], [int(v) for v in c["n2raw"]],
+                              [p for p, v in enumerate(first) if v], [p for p, v in enumerate(second) if v], tiles,
+                              float(norms.min()), float(norms.max()), ["%.2e" % float(v) for v in y]))
+    if name == "zero":
+        assert first == [True, False, True, False] and second == first
+        for plane in (0, 2):                                        # not one vote: argmax of zeros is slot 0
+            assert int(c["counts"][plane].max()) == 0 and int(c["best"][plane]) == 0
+            assert bool((c["w1"][plane] == 1).all()) and bool((c["w2"][plane] == 1).all())
+    else:
+        assert f["consensus"] >= 6 and not any(first) and not any(second)
+    if name == "rot0.3":
+        assert float(norms.min()) > 0.1 and float(norms.max()) < 0.6 and float(case["P_true"][:, 3:].norm(dim=1).max()) > 0.3
+    if name == "rot0":                                              # so3_log's series branch (th <= 1e-6)
+        assert float(norms.max()) < 1e-6 and float(case["P_true"][:, 3:].abs().max()) == 0.0
+        assert float((c["P"] - case["P_true"]).abs().max()) < 2e-6
+    if name == "tiles":
+        assert num == PC.MATCH_TILE and hyp == 2 * PC.HYP_TILE
+    if name in ("b1", "b3"):
+        assert B == int(name[1]) and tuple(c["P"].shape) == (2 * B, 6)

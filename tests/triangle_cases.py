@@ -21,6 +21,18 @@ import torch
 NOISE_PX = 0.3
 # (H, W, align_corners) -> seed; found with find_seed(H, W, ac), B = 2, k = 72
 SEEDS = {(12, 20, False): 4, (12, 20, True): 16, (13, 19, False): 3, (13, 19, True): 15}
+# The edge cases, (B, H, W, align_corners, depth_lo) -> seed, found with find_seed(H, W, ac, B=B, depth_lo=depth_lo): B = 1 and an
+# odd B, and a depth floor of 0.5 -- near points under the same baseline reproject two and more plane sizes outside the plane, so
+# the reflection folds them more than once (``folds``).  No (3, 13, 19, True) seed exists below 400: 12 x 20 stands in.
+EDGE_SEEDS = {
+    (1, 12, 20, False, 2.0): 11,
+    (1, 13, 19, True, 2.0): 12,
+    (3, 12, 20, False, 2.0): 4,
+    (3, 12, 20, True, 2.0): 103,
+    (2, 12, 20, False, 0.5): 4,
+    (2, 12, 20, True, 0.5): 170,
+}
+EDGE_SHAPES = tuple(sorted(EDGE_SEEDS))
 
 
 def _smooth(rng, h, w, lo, hi):
@@ -42,8 +54,9 @@ def _rotation(r):
     return Rx @ Ry @ Rz
 
 
-def build(seed, B, H, W, k):
-    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them."""
+def build(seed, B, H, W, k, depth_lo=2.0):
+    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them.  ``depth_lo``: the floor of the
+    synthetic depth (the default draws today's cases bit for bit)."""
     rng = np.random.default_rng(seed)
     K = np.zeros((B, 3, 3))
     T34 = np.zeros((B, 2, 3, 4))
@@ -53,7 +66,7 @@ def build(seed, B, H, W, k):
         f = 0.9 * W * rng.uniform(0.95, 1.05)
         K[b] = [[f, 0, (W - 1) / 2.0 + rng.uniform(-0.5, 0.5)], [0, f * rng.uniform(0.97, 1.03), (H - 1) / 2.0 + rng.uniform(-0.5, 0.5)],
                 [0, 0, 1]]
-        depth = _smooth(rng, H, W, 2.0, 20.0)
+        depth = _smooth(rng, H, W, depth_lo, 20.0)
         Ki = np.linalg.inv(K[b])
         X = depth[None] * np.einsum("ij,jhw->ihw", Ki, np.stack([xs, ys, np.ones_like(xs)]))
         for d in range(2):
@@ -73,12 +86,13 @@ def build(seed, B, H, W, k):
                 idx=torch.from_numpy(idx))
 
 
-def conditions(case, ac):
-    """(min z / median z, min cross-product norm, min distance of a sampling coordinate to an integer or a fold) over every pixel of
-    the idx sets, in float64."""
-    B, H, W, k = case["B"], case["H"], case["W"], case["k"]
+def _reprojections(case):
+    """Per direction and view: (cross-product norms [B,k], z [B,k], reprojected pixel coordinates [B,k,2]) over every pixel of the
+    idx sets, in float64."""
+    from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers
+    B, H, W = case["B"], case["H"], case["W"]
     K, Ki, T34 = case["K"].double(), case["K_inv"].double(), case["T34"].double()
-    zmin, cmin, dmin = np.inf, np.inf, np.inf
+    m = GeometrySolvers()
     for d, flow in enumerate((case["flow_bwd"], case["flow_fwd"])):
         pix = case["idx"][d * B:(d + 1) * B].long()
         x, y = (pix % W).double(), torch.div(pix, W, rounding_mode="floor").double()
@@ -87,24 +101,57 @@ def conditions(case, ac):
         r0 = Ki.bmm(torch.stack([x, y, one], 1))
         r1 = T34[:, d, :, :3].transpose(1, 2).bmm(Ki.bmm(torch.stack([x + uv[:, 0], y + uv[:, 1], one], 1)))
         r0, r1 = r0 / r0.norm(dim=1, keepdim=True), r1 / r1.norm(dim=1, keepdim=True)
-        cmin = min(cmin, float(torch.cross(r0, r1, dim=1).norm(dim=1).min()))
-        from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers
-        m = GeometrySolvers()
+        cross = torch.cross(r0, r1, dim=1).norm(dim=1)
         eye = torch.zeros(B, 3, 4, dtype=torch.float64)
         eye[:, 0, 0] = eye[:, 1, 1] = eye[:, 2, 2] = 1.0
         P1, P2 = K.bmm(eye), K.bmm(T34[:, d])
         pts = m.midpoint_triangulate(torch.stack([x, y, x + uv[:, 0], y + uv[:, 1]], 1), K, Ki, P1, P2)
         for P in (P1, P2):
             c, z = m.reproject(P, pts)
-            zmin = min(zmin, float((z.squeeze(-1) / z.squeeze(-1).median(1, keepdim=True)[0]).min()))
-            for axis, size in ((0, W), (1, H)):
-                g = 2.0 * c[:, :, axis] / (size - 1.0) - 1.0
-                ix = (g + 1.0) / 2.0 * (size - 1.0) if ac else ((g + 1.0) * size - 1.0) / 2.0
-                dmin = min(dmin, float((ix - ix.round()).abs().min()))
-                if not ac:      # folds at -0.5 + m * size
-                    fold = (ix + 0.5) / size
-                    dmin = min(dmin, float(((fold - fold.round()).abs() * size).min()))
+            yield cross, z.squeeze(-1), c
+
+
+def _unnormalised(c, axis, size, ac):
+    """grid_sample's pixel coordinate of the reprojected coordinate ``c[..., axis]`` (before the reflection)."""
+    g = 2.0 * c[:, :, axis] / (size - 1.0) - 1.0
+    return (g + 1.0) / 2.0 * (size - 1.0) if ac else ((g + 1.0) * size - 1.0) / 2.0
+
+
+def conditions(case, ac):
+    """(min z / median z, min cross-product norm, min distance of a sampling coordinate to an integer or a fold) over every pixel of
+    the idx sets, in float64."""
+    H, W = case["H"], case["W"]
+    zmin, cmin, dmin = np.inf, np.inf, np.inf
+    for cross, z, c in _reprojections(case):
+        cmin = min(cmin, float(cross.min()))
+        zmin = min(zmin, float((z / z.median(1, keepdim=True)[0]).min()))
+        for axis, size in ((0, W), (1, H)):
+            ix = _unnormalised(c, axis, size, ac)
+            dmin = min(dmin, float((ix - ix.round()).abs().min()))
+            if not ac:      # folds at -0.5 + m * size
+                fold = (ix + 0.5) / size
+                dmin = min(dmin, float(((fold - fold.round()).abs() * size).min()))
     return zmin, cmin, dmin
+
+
+def folds(case, ac, pick=None):
+    """(samples folded once, samples folded twice or more) over every pixel of the idx sets -- with ``pick``, over the pixels it
+    draws, each once -- in float64: a sample counts with the
+    larger of its two axes' fold counts floor(|ix - lo| / span) -- span = size, lo = -0.5 without align_corners, size - 1 and 0
+    with it (``reflect_axis``).  Twice or more is a reprojection two and more plane widths or heights outside the plane."""
+    H, W = case["H"], case["W"]
+    once = twice = 0
+    for _, _, c in _reprojections(case):
+        n = torch.zeros(c.shape[:2], dtype=torch.float64)
+        for axis, size in ((0, W), (1, H)):
+            ix = _unnormalised(c, axis, size, ac)
+            lo, span = (0.0, size - 1.0) if ac else (-0.5, float(size))
+            n = torch.maximum(n, torch.floor((ix - lo).abs() / span))
+        if pick is not None:
+            n = n[:, pick.unique()]
+        once += int((n == 1).sum())
+        twice += int((n >= 2).sum())
+    return once, twice
 
 
 def well_conditioned(case, ac):
@@ -112,23 +159,35 @@ def well_conditioned(case, ac):
     return zmin >= 0.05 and cmin >= 1e-3 and dmin >= 1e-3
 
 
-def find_seed(H, W, ac, B=2, k=72, start=0, tries=5000):
-    """The first seed from ``start`` whose case meets the conditions (run once on the CPU; the result goes into SEEDS)."""
+def find_seed(H, W, ac, B=2, k=72, start=0, tries=5000, depth_lo=2.0):
+    """The first seed from ``start`` whose case meets the conditions (run once on the CPU; the result goes into SEEDS or
+    EDGE_SEEDS).  With a lowered depth floor the case must also fold a sample twice: that is what it is for."""
     for seed in range(start, start + tries):
-        if well_conditioned(build(seed, B, H, W, k), ac):
+        case = build(seed, B, H, W, k, depth_lo)
+        if well_conditioned(case, ac) and (depth_lo >= 2.0 or folds(case, ac)[1] > 0):
             return seed
     raise RuntimeError("no seed found")
 
 
-@functools.lru_cache(maxsize=None)
-def make_case(H, W, ac, B=2, k=72):
-    """The case of SEEDS[(H, W, ac)], its conditions asserted."""
-    case = build(SEEDS[(H, W, bool(ac))], B, H, W, k)
+def _checked(case, ac):
     zmin, cmin, dmin = conditions(case, ac)
     assert zmin >= 0.05, "a triangulated depth below 0.05 x the median (%g)" % zmin
     assert cmin >= 1e-3, "a nearly parallel ray pair (cross-product norm %g)" % cmin
     assert dmin >= 1e-3, "a sampling coordinate within 1e-3 of an integer or of the reflection fold (%g)" % dmin
     return case
+
+
+@functools.lru_cache(maxsize=None)
+def make_case(H, W, ac, B=2, k=72):
+    """The case of SEEDS[(H, W, ac)], its conditions asserted."""
+    return _checked(build(SEEDS[(H, W, bool(ac))], B, H, W, k), ac)
+
+
+@functools.lru_cache(maxsize=None)
+def make_edge_case(key, k=72):
+    """The case of EDGE_SEEDS[key], key = (B, H, W, ac, depth_lo), its conditions asserted with nothing excluded."""
+    B, H, W, ac, depth_lo = key
+    return _checked(build(EDGE_SEEDS[key], B, H, W, k, depth_lo), ac)
 
 
 def make_pick(case, num, seed=0, constant=None):
