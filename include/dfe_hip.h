@@ -213,6 +213,41 @@ typedef struct {
 int dfe_prepare_triplets_u8(const unsigned char* in_u8, const dfe_u8_desc* desc, const int* xtab, const int* ytab,
                             const float* lut, float* out, int B, int H, int W, int nvec, int rgb, void* stream);
 
+/* ---- a training set resident in device memory: the resized 8-bit frames kept, a batch gathered in one launch -------
+ * The image half above is deterministic per frame up to the resized byte; only the flip, the / 255 and the choice of sample
+ * vary per step.  dfe_resize_strips_u8 keeps the bytes (once per frame); dfe_gather_triplets_u8 makes a batch from them.
+ *
+ * dfe_resize_strips_u8: in_u8, desc (every flip must be 0), xtab, ytab, nvec, rgb as for dfe_prepare_triplets_u8, from the same
+ * device code (csrc/ops_input.hip: resized_bgr_u8), so store holds exactly the bytes u whose lut[u] that entry point writes.
+ *   slot  : long long [B][3], the destination frame of (sample b, frame f) in store; -1 = do not write (stored already)
+ *   store : uint8 [F][3 (B,G,R)][H][W]
+ * Memory contract: reads what dfe_prepare_triplets_u8 reads, plus the 3B values of slot; writes exactly the 3*H*W bytes of
+ * each slot >= 0 and nothing else (a value >= F writes nothing either: the kernel predicates on it; the host wrapper refuses
+ * it); byte accesses, no alignment needed beyond slot's 8 and the tables'; no scratch.  F <= 0, B, H, W <= 0 or nvec outside
+ * [0, 3W] is DFE_ERR_DIMS before the launch, with nothing written.
+ *
+ * dfe_gather_triplets_u8: one batch in one launch (B > 64: one launch per 64 samples).
+ *   store : as above, F frames               tri  : int [N][3], the frame slots of triplet i (left / target / right)
+ *   ktab  : fp32 [N][2][S][3][3], K_ms then K_inv_ms of triplet i            lut : the 256 floats above
+ *   idx_host  : HOST pointer, int [B], the triplet of each sample            (these two are the only host pointers of this
+ *   flip_host : HOST pointer, B bytes, non-zero = flipped; NULL = none        file's image entry points: they are read during
+ *                                                                             the call and travel in the kernel's arguments)
+ *   out : fp32 [B][3][3*H][W];  K_ms, K_inv_ms : fp32 [B][S][3][3]
+ * Result: out[b][c][f*H + y][x] = lut[store[tri[idx[b]][f]][c][y][flip[b] ? W-1-x : x]], K_ms[b] = ktab[idx[b]][0],
+ * K_inv_ms[b] = ktab[idx[b]][1].  No pinned staging buffer and no copy: nothing for the stream to wait on but the kernel.
+ * Memory contract: reads tri and ktab at the rows idx names, lut, and the 3*H*W bytes of each named frame whose slot lies in
+ * [0, F) -- a slot outside is never dereferenced (its rows are written as lut[0]); writes every element of out, K_ms and
+ * K_inv_ms and nothing else; no scratch.  With W % 16 == 0 and store, out on 16 bytes a lane moves 16 bytes per load and store;
+ * otherwise (any W, dword-aligned out, store unaligned) one element per lane, the same bits.  A NULL pointer (flip_host
+ * excepted) is DFE_ERR_NULL; F, N, B, S, H, W <= 0, S > DFE_MAX_SCALES, 9*H*W >= 2^25 or an idx_host[b] outside [0, N) is
+ * DFE_ERR_DIMS, checked on the host before the first launch, with nothing written. */
+int dfe_resize_strips_u8(const unsigned char* in_u8, const dfe_u8_desc* desc, const int* xtab, const int* ytab,
+                         const long long* slot, unsigned char* store, long F, int B, int H, int W, int nvec, int rgb,
+                         void* stream);
+int dfe_gather_triplets_u8(const unsigned char* store, long F, const int* tri, const float* ktab, int N, const float* lut,
+                           const int* idx_host, const unsigned char* flip_host, float* out, float* K_ms, float* K_inv_ms,
+                           int B, int S, int H, int W, void* stream);
+
 /* ---- forward-splat occlusion map  core/networks/model_flow.py:33-39 (get_occlusion_mask_from_flow) -----------
  * The reference calls an undefined `transformerFwd`; this is its TrianFlow meaning: out [B,1,H,W] = bilinear forward
  * warp of a ones image by flow [B,2,H,W] (optionally clamped to [0,1]).  Order-independent scatter through ws

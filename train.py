@@ -9,7 +9,8 @@ with one process per GPU over RCCL (ddp.wrap: one flat gradient all-reduce per s
 torchrun); the data source is the synthetic KITTI-shaped triplet generator by default (``data_source: synthetic``), or the
 reference's prepared KITTI tree with ``--data_source prepared --prepared_base_dir DIR`` (train.txt, stacked-triplet PNGs and
 calib files as KITTI_RAW.prepare_data_mp writes them; read by prepared_data.PreparedFeeder on ``--num_workers`` decode threads
-with the image half on the device).  Periodic KITTI evaluation (train.py:136-164) is honoured: every ``--test_interval``
+with the image half on the device), or the same tree kept in device memory with ``--data_source resident`` (prepared_data.ResidentTrainSet:
+every distinct frame resized once, a batch is one gather launch; ``--resident_cache DIR`` keeps the built set on disk).  Periodic KITTI evaluation (train.py:136-164) is honoured: every ``--test_interval``
 iterations (iteration 0 included) unless ``--no_test``, rank 0 runs KITTI flow 2012 / 2015 and / or Eigen depth by mode
 (``periodic_eval``) from device-resident sets (eval_device.Evaluator: batched inference through an InferenceSession, metric
 kernels behind each batch, one host transfer per task), prints the reference's tables and pickles the list of result packs to
@@ -140,7 +141,7 @@ def train(cfg):
     h, w = cfg.img_hw
     n_iter = cfg.num_iterations - start
     raw_pipeline = bool(getattr(cfg, "device_pipeline", False))
-    feeder = None
+    feeder, train_set = None, None
     if getattr(cfg, "data_source", "synthetic") == "prepared":     # the reference's prepared tree (train.py:100-125)
         if not getattr(cfg, "prepared_base_dir", None):
             raise ValueError("data_source 'prepared' needs prepared_base_dir (--prepared_base_dir or the YAML key)")
@@ -149,6 +150,20 @@ def train(cfg):
                                               world=world, rank=rank)
         if rank == 0:
             print("A total of {} image pairs found".format(source.count()), flush=True)
+    elif getattr(cfg, "data_source", "synthetic") == "resident":   # the same tree, resident in HBM: no decode, no copy per step
+        if not getattr(cfg, "prepared_base_dir", None):
+            raise ValueError("data_source 'resident' needs prepared_base_dir (--prepared_base_dir or the YAML key)")
+        source = prepared_data.PreparedKITTI(cfg.prepared_base_dir, cfg.num_scales, (h, w))
+        reserve = getattr(cfg, "resident_reserve_mb", None)
+        train_set = prepared_data.ResidentTrainSet(source, (h, w), dev, num_workers=cfg.num_workers,
+                                                   cache_dir=getattr(cfg, "resident_cache", None), write_cache=rank == 0,
+                                                   reserve_mb=prepared_data.RESIDENT_RESERVE_MB if reserve is None else reserve)
+        feeder = train_set.batches(cfg.batch_size, n_iter, world=world, rank=rank)      # every rank holds the whole set
+        if rank == 0:
+            print("A total of {} image pairs found".format(source.count()), flush=True)
+            print("resident set: {} frames, {} bytes, {} in {:.1f} s".format(
+                train_set.F, train_set.nbytes, "loaded from the cache" if train_set.from_cache else "built", train_set.build_seconds),
+                flush=True)
     elif raw_pipeline:   # raw uint8 triplets at KITTI's native size; resize / flip / normalise run on the device
         dataset = synthetic.SyntheticRawTriplets(n_iter * cfg.batch_size * world, (375, 1242), (h, w), cfg.num_scales, seed=1234)
     else:
@@ -162,7 +177,11 @@ def train(cfg):
     t0 = time.time()
     for it in range(start, cfg.num_iterations):
         periodic_eval(cfg, evaluator, it, log_list)
-        if feeder is not None:
+        if train_set is not None and graphed is not None:
+            # The gather runs OUTSIDE the captured graph (its arguments -- the batch's triplets and flips -- change per step) and
+            # writes straight into the graph's static inputs; graphed(...) then sees equal pointers and copies nothing.
+            inputs = train_set.fetch(it - start, out=graphed.static_inputs)
+        elif feeder is not None:
             inputs = next(feeder)      # batch it - start of the per-rank shard: idx = (it - start) * B * world + rank * B + j
         else:
             base = (it - start) * cfg.batch_size * world + rank * cfg.batch_size
@@ -196,7 +215,7 @@ def train(cfg):
 
 
 # CLI attributes that leave the YAML's value alone when they are not given
-KEEP_YAML_WHEN_UNSET = ("num_iterations", "data_source", "prepared_base_dir", "deterministic", "clip_grad_norm", "skip_nonfinite")
+KEEP_YAML_WHEN_UNSET = ("num_iterations", "data_source", "prepared_base_dir", "resident_cache", "deterministic", "clip_grad_norm", "skip_nonfinite")
 
 
 def build_parser():
@@ -214,10 +233,15 @@ def build_parser():
     ap.add_argument("--mode", type=str, default="geom", help="flow | depth | geom")
     ap.add_argument("--model_dir", type=str, default=None)
     ap.add_argument("--prepared_save_dir", type=str, default="data_s1")
-    ap.add_argument("--data_source", type=str, default=None, choices=("synthetic", "prepared"),
-                    help="synthetic triplets (the YAML's default) or the reference's prepared KITTI tree under --prepared_base_dir")
+    ap.add_argument("--data_source", type=str, default=None, choices=("synthetic", "prepared", "resident"),
+                    help="synthetic triplets (the YAML's default), the reference's prepared KITTI tree under --prepared_base_dir "
+                         "streamed from the host, or ('resident') the same tree kept in device memory: every rank holds the whole set")
     ap.add_argument("--prepared_base_dir", type=str, default=None,
                     help="directory holding train.txt, the stacked-triplet PNGs and calib files (KITTI_RAW.prepare_data_mp's output)")
+    ap.add_argument("--resident_cache", type=str, default=None,
+                    help="with --data_source resident: a directory that keeps the built set (frames.u8, tri.i32, K.f32, meta.json); "
+                         "loaded instead of decoding when its key matches the tree (also the YAML key 'resident_cache'; the reserve "
+                         "left for the step is the YAML key 'resident_reserve_mb')")
     ap.add_argument("--flow_pretrained_model", type=str, default=None)
     ap.add_argument("--depth_pretrained_model", type=str, default=None)
     ap.add_argument("--resume", action="store_true")

@@ -576,6 +576,100 @@ def u8_tables(sizes, img_hw, device):
     return dict(zip(sizes, index)), (xtab, ytab, lut)
 
 
+def _need(t, what, dtype, contiguous=True):
+    """A HIP tensor of ``dtype`` (DfeError for a host tensor, ValueError for the rest), before the library is called."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise DfeError("%s must be a tensor on a HIP device; there is no CPU fallback in the product path" % what)
+    if t.dtype != dtype:
+        raise ValueError("%s must be %s, not %s" % (what, dtype, t.dtype))
+    if contiguous and not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % what)
+    return t
+
+
+def resize_strips_u8(raw_u8, sizes, img_hw, slot, store, offsets=None, rgb=False):
+    """The resized 8-bit frames of ``prepare_triplets_u8``'s strips, kept (dfe_resize_strips_u8: the same device code up to the byte,
+    so ``lut[store]`` is what prepare_triplets_u8 returns unflipped).
+
+    raw_u8, sizes, offsets, rgb: as for ``prepare_triplets_u8``.  slot: B x 3 host integers, the frame of ``store`` (uint8 device
+    tensor [F, 3 (B,G,R), H, W], written in place) that (strip b, frame f) goes to; -1 = do not write.  Values outside [-1, F)
+    are refused here, before the library is called."""
+    import numpy as np
+    _need(raw_u8, "raw_u8", torch.uint8)
+    H, W = int(img_hw[0]), int(img_hw[1])
+    _need(store, "store", torch.uint8)
+    if store.device != raw_u8.device or store.dim() != 4 or tuple(store.shape[1:]) != (3, H, W) or store.shape[0] < 1:
+        raise ValueError("store must be uint8 [F, 3, %d, %d] on raw_u8's device" % (H, W))
+    sizes = [(int(a), int(b)) for a, b in sizes]
+    B, F = len(sizes), int(store.shape[0])
+    if B == 0 or H <= 0 or W <= 0 or any(a <= 0 or b <= 0 for a, b in sizes):
+        raise ValueError("resize_strips_u8: empty batch or a non-positive size")
+    nbytes = [9 * a * b for a, b in sizes]
+    if offsets is None:
+        offsets = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).tolist()
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != B or any(o < 0 or o + n > raw_u8.numel() for o, n in zip(offsets, nbytes)):
+        raise ValueError("resize_strips_u8: a strip lies outside raw_u8 (%d bytes)" % raw_u8.numel())
+    slot = np.ascontiguousarray(np.asarray(slot, dtype=np.int64))
+    if slot.shape != (B, 3) or bool(((slot < -1) | (slot >= F)).any()):
+        raise ValueError("resize_strips_u8: slot must be [%d, 3] integers in [-1, %d)" % (B, F))
+    index, xtab, ytab, _ = _u8_tables.get([(a, b, H, W) for a, b in sizes], raw_u8.device)
+    desc = np.zeros(B, U8_DESC)
+    desc["offset"] = offsets
+    desc["h0"], desc["w0"] = [a for a, _ in sizes], [b for _, b in sizes]
+    desc["xtab"], desc["ytab"] = [i[0] for i in index], [i[1] for i in index]
+    d_desc = torch.from_numpy(desc.view(np.uint8)).to(raw_u8.device)     # blocking uploads: this is the build, not the step
+    d_slot = torch.from_numpy(slot).to(raw_u8.device)
+    check(get_lib().dfe_resize_strips_u8(ptr(raw_u8), ptr(d_desc), ptr(xtab), ptr(ytab), ptr(d_slot), ptr(store), F, B, H, W,
+                                         resize_u8_vector_bytes(W), 1 if rgb else 0, stream_ptr()), "dfe_resize_strips_u8")
+    return store
+
+
+def gather_triplets_u8(set_tensors, idx, flip=None, out=None):
+    """One training batch from a device-resident set in one launch on the current stream (dfe_gather_triplets_u8).
+
+    set_tensors: (store uint8 [F,3,H,W], tri int32 [N,3], ktab fp32 [N,2,S,3,3], lut fp32 [256]) on one HIP device; idx: B host
+    integers in [0, N) (the triplets); flip: B host values or None.  The indices and flips travel in the kernel's arguments: no
+    staging buffer, no copy.  Returns [images fp32 [B,3,3H,W], K_ms [B,S,3,3], K_inv_ms [B,S,3,3]]: fresh tensors, or the three
+    of ``out`` (contiguous fp32 of those shapes; how a replayed graph's static inputs are fed).  Everything is checked here,
+    before the library is called."""
+    store, tri, ktab, lut = set_tensors
+    _need(store, "store", torch.uint8), _need(tri, "tri", torch.int32), _need(ktab, "ktab", torch.float32), _need(lut, "lut", torch.float32)
+    if store.dim() != 4 or store.shape[1] != 3 or tri.dim() != 2 or tri.shape[1] != 3 or ktab.dim() != 5 or \
+            tuple(ktab.shape[2:]) != (ktab.shape[2], 3, 3) or ktab.shape[:2] != (tri.shape[0], 2) or lut.numel() != 256:
+        raise ValueError("gather_triplets_u8: set tensors must be store [F,3,H,W], tri [N,3], ktab [N,2,S,3,3], lut [256]")
+    if any(t.device != store.device for t in (tri, ktab, lut)):
+        raise ValueError("gather_triplets_u8: the set's tensors must live on one device")
+    F, _, H, W = (int(v) for v in store.shape)
+    N, S = int(tri.shape[0]), int(ktab.shape[2])
+    idx = [int(i) for i in idx]
+    B = len(idx)
+    if B == 0 or F == 0 or N == 0:
+        raise ValueError("gather_triplets_u8: empty batch or empty set")
+    if any(i < 0 or i >= N for i in idx):
+        raise ValueError("gather_triplets_u8: a triplet index lies outside [0, %d)" % N)
+    c_flip = None
+    if flip is not None:
+        fl = [1 if v else 0 for v in (flip.tolist() if isinstance(flip, torch.Tensor) else flip)]
+        if len(fl) != B:
+            raise ValueError("gather_triplets_u8: flip must have one entry per sample")
+        c_flip = (ctypes.c_ubyte * B)(*fl)
+    shapes = ((B, 3, 3 * H, W), (B, S, 3, 3), (B, S, 3, 3))
+    if out is None:
+        out = [torch.empty(s, device=store.device) for s in shapes]
+    else:
+        out = list(out)
+        if len(out) != 3:
+            raise ValueError("gather_triplets_u8: out takes the three destination tensors")
+        for t, s, name in zip(out, shapes, ("out[0] (images)", "out[1] (K_ms)", "out[2] (K_inv_ms)")):
+            _need(t, name, torch.float32)
+            if tuple(t.shape) != s or t.device != store.device:
+                raise ValueError("gather_triplets_u8: %s must be %s on the set's device" % (name, list(s)))
+    check(get_lib().dfe_gather_triplets_u8(ptr(store), F, ptr(tri), ptr(ktab), N, ptr(lut), (ctypes.c_int * B)(*idx), c_flip,
+                                           ptr(out[0]), ptr(out[1]), ptr(out[2]), B, S, H, W, stream_ptr()), "dfe_gather_triplets_u8")
+    return out
+
+
 def rescale_intrinsics(K, img_hw_orig, img_hw_new, num_scales):
     """rescale_intrinsics + get_multiscale_intrinsics (kitti_prepared.py:110-130): K [3,3] float64 numpy ->
     (K_ms, K_inv_ms) float32 tensors [S,3,3] (host side: a few dozen flops per sample)."""

@@ -5,7 +5,8 @@ core/dataset/kitti_prepared.py:10-152, train.py:100-125) with a prefetching feed
 intrinsics.  The image half -- cv2.imread, the per-frame 8-bit cv2.resize, cv2.flip, / 255 -- runs on the device for a whole batch
 (``ops.prepare_triplets_u8``).  ``PreparedFeeder`` decodes PNG strips on host threads into a ring of pinned slots, uploads them on a
 side stream into a device ring, runs the prepare kernel there and hands each batch to the training stream through events, so
-batch k+1 is decoded, uploaded and prepared while step k runs.
+batch k+1 is decoded, uploaded and prepared while step k runs.  ``ResidentTrainSet`` is the same source for a tree that fits in
+device memory: the resized 8-bit frames are computed once and kept there, and a batch is one gather launch (same bits).
 
 Sample order.  The training loop asks for idx = (it - start) * B * world + rank * B + j (train.py), i.e. idx runs sequentially
 per rank.  The reference's DataLoader shuffles (unseeded) which idx comes when, but every idx already maps to a random sample
@@ -163,6 +164,282 @@ def batch_indices(k, batch_size, world=1, rank=0):
     """Training idx of batch k on ``rank``: k * B * world + rank * B + j (train.py's per-rank shard)."""
     base = int(k) * batch_size * world + rank * batch_size
     return [base + j for j in range(batch_size)]
+
+
+# ------------------------------------------------------------------------------------------------ the device-resident set
+RESIDENT_FORMAT = 1                     # meta.json's version: bumped when a cached file's layout changes
+RESIDENT_FILES = ("frames.u8", "tri.i32", "K.f32")
+MAX_BUILD_THREADS = 16                  # decode threads of the build, whatever num_workers asks for (never sized by the machine)
+# What the training step itself needs next to the set, in MB: the measured peak allocation of a B = 8 geom step at 256x832
+# (torch.cuda.max_memory_allocated = 8 516 459 520 bytes, profiles/resident_set.txt) times 1.5 -- the allocator's cached blocks
+# (10 393 485 312 bytes reserved in the same run), MIOpen workspaces, a graph's private pool -- rounded up to a GB: 13 GB.
+RESIDENT_RESERVE_MB = 13312
+_CHUNK_BYTES = 64 << 20                 # decoded strips uploaded per resize launch / store bytes per pinned cache chunk
+
+
+def resident_bytes(F, N, S, img_hw):
+    """Device bytes of a resident set: F frames uint8 [3, H, W], the int32 [N, 3] triplet table, the fp32 [N, 2, S, 3, 3]
+    intrinsics table and the 256-float lut."""
+    H, W = int(img_hw[0]), int(img_hw[1])
+    return int(F) * 3 * H * W + int(N) * 3 * 4 + int(N) * 2 * int(S) * 9 * 4 + 256 * 4
+
+
+def frame_keys(strip, h0, w0):
+    """The dedup keys of a decoded strip's three frames: (h0, w0, blake2b-128 of the frame's decoded RGB bytes)."""
+    import hashlib
+    rows = np.asarray(strip, np.uint8).reshape(-1, w0, 3)
+    return [(h0, w0, hashlib.blake2b(rows[f * h0:(f + 1) * h0].tobytes(), digest_size=16).digest()) for f in range(3)]
+
+
+def _ordered_map(fn, items, num_workers):
+    """fn over items in order, on up to min(num_workers, MAX_BUILD_THREADS) threads a chunk at a time (a chunk's results are
+    held, never the whole list's); 0 workers: in the calling thread."""
+    items = list(items)
+    workers = min(max(int(num_workers), 0), MAX_BUILD_THREADS)
+    if not workers:
+        for it in items:
+            yield fn(it)
+        return
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(workers) as ex:           # joined on exit: no thread outlives the build
+        for a in range(0, len(items), 4 * workers):
+            for r in ex.map(fn, items[a:a + 4 * workers]):
+                yield r
+
+
+def plan_frames(source, num_workers=0):
+    """The host half of the build: decode every strip once, key its frames and give each distinct frame a slot, in data-list
+    order on the calling thread (the layout is the same for any worker count).  Returns (tri int32 [N, 3]: the slots of
+    triplet i's frames; slot int64 [N, 3]: the same where triplet i is the FIRST holder of the frame, else -1; F)."""
+    n = source.count()
+    tri, slot, seen = np.empty((n, 3), np.int32), np.full((n, 3), -1, np.int64), {}
+
+    def keys(i):
+        return frame_keys(source.decode(i), *source.frame_hw(i))
+    for i, ks in enumerate(_ordered_map(keys, range(n), num_workers)):
+        for f, k in enumerate(ks):
+            s = seen.get(k)
+            if s is None:
+                s = seen[k] = len(seen)
+                slot[i, f] = s
+            tri[i, f] = s
+    return tri, slot, len(seen)
+
+
+def intrinsics_table(source):
+    """fp32 [N, 2, S, 3, 3]: K_ms then K_inv_ms of every data-list entry."""
+    return np.stack([np.stack(source.intrinsics(i)) for i in range(source.count())]).astype(np.float32)
+
+
+def cache_key(source):
+    """SHA-256 over train.txt's bytes and every strip's (size, mtime_ns, IHDR triple)."""
+    import hashlib
+    h = hashlib.sha256()
+    with open(os.path.join(source.data_dir, "train.txt"), "rb") as fh:
+        h.update(fh.read())
+    for (img, _), hdr in zip(source.data_list, source.headers):
+        st = os.stat(img)
+        h.update(struct.pack("<qq3i", st.st_size, st.st_mtime_ns, *hdr))
+    return h.hexdigest()
+
+
+def cache_open(cache_dir, key, N, S, img_hw):
+    """(frames memmap uint8 [F, 3, H, W], tri, ktab) of a complete cache whose meta.json matches, else None: a missing or
+    short file, another key, size, scale count or format all mean 'absent' (temporary files of an interrupted write are
+    never looked at: meta.json is written last)."""
+    import json
+    H, W = int(img_hw[0]), int(img_hw[1])
+    try:
+        with open(os.path.join(cache_dir, "meta.json")) as fh:
+            meta = json.load(fh)
+        want = {"format": RESIDENT_FORMAT, "img_hw": [H, W], "num_scales": int(S), "N": int(N), "key": key}
+        if any(meta.get(k) != v for k, v in want.items()):
+            return None
+        F = int(meta["F"])
+        sizes = (F * 3 * H * W, N * 12, N * 2 * S * 36)
+        if F < 1 or any(os.path.getsize(os.path.join(cache_dir, f)) != s for f, s in zip(RESIDENT_FILES, sizes)):
+            return None
+        frames = np.memmap(os.path.join(cache_dir, "frames.u8"), np.uint8, "r", shape=(F, 3, H, W))
+        tri = np.fromfile(os.path.join(cache_dir, "tri.i32"), np.int32).reshape(N, 3)
+        ktab = np.fromfile(os.path.join(cache_dir, "K.f32"), np.float32).reshape(N, 2, S, 3, 3)
+    except (OSError, ValueError, KeyError, TypeError):
+        return None
+    if tri.size and (tri.min() < 0 or tri.max() >= F):
+        return None
+    return frames, tri, ktab
+
+
+def cache_write(cache_dir, key, img_hw, write_frames, F, tri, ktab):
+    """Write the cache: every file under a temporary name renamed into place, meta.json last (and removed first, so that a
+    half-overwritten directory is never taken for a cache).  ``write_frames(fh)`` streams the store's bytes."""
+    import json
+    os.makedirs(cache_dir, exist_ok=True)
+    meta_path = os.path.join(cache_dir, "meta.json")
+    if os.path.exists(meta_path):
+        os.remove(meta_path)
+
+    def put(name, writer):
+        tmp = os.path.join(cache_dir, name + ".tmp")
+        with open(tmp, "wb") as fh:
+            writer(fh)
+        os.replace(tmp, os.path.join(cache_dir, name))
+    put("frames.u8", write_frames)
+    put("tri.i32", lambda fh: fh.write(np.ascontiguousarray(tri, np.int32).tobytes()))
+    put("K.f32", lambda fh: fh.write(np.ascontiguousarray(ktab, np.float32).tobytes()))
+    meta = {"format": RESIDENT_FORMAT, "img_hw": [int(img_hw[0]), int(img_hw[1])], "num_scales": int(ktab.shape[2]), "F": int(F),
+            "N": int(tri.shape[0]), "key": key}
+    put("meta.json", lambda fh: fh.write(json.dumps(meta, indent=1).encode()))
+
+
+class _HipStore:
+    """The device steps of ResidentTrainSet (injectable: the host half -- plan, budget, cache -- is tested without a device)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def alloc(self, F, img_hw):
+        return torch.empty(F, 3, int(img_hw[0]), int(img_hw[1]), dtype=torch.uint8, device=self.device)
+
+    def resize(self, store, raw, sizes, offsets, slot, img_hw):
+        """raw: packed decoded strips (host uint8, R, G, B) -> the frames of ``slot`` >= 0 in store"""
+        ops.resize_strips_u8(torch.from_numpy(raw).to(self.device), sizes, img_hw, slot, store, offsets, rgb=True)
+
+    def load(self, store, frames):
+        """host frames (a memmap) -> store, through one pinned chunk"""
+        flat, src = store.view(-1), frames.reshape(-1)
+        pin = torch.empty(min(_CHUNK_BYTES, flat.numel()), dtype=torch.uint8).pin_memory()
+        for a in range(0, flat.numel(), pin.numel()):
+            n = min(pin.numel(), flat.numel() - a)
+            pin.numpy()[:n] = src[a:a + n]
+            flat[a:a + n].copy_(pin[:n])                  # blocking: the chunk is free again when it returns
+
+    def save(self, store, fh):
+        flat = store.view(-1)
+        for a in range(0, flat.numel(), _CHUNK_BYTES):
+            fh.write(flat[a:a + _CHUNK_BYTES].cpu().numpy().tobytes())
+
+    def finish(self, store, tri, ktab, sizes, img_hw):
+        """the set's tensors for ``gather``: (store, tri, ktab, lut)"""
+        lut = ops.u8_tables(sizes, img_hw, self.device)[1][2]
+        return (store, torch.from_numpy(np.ascontiguousarray(tri, np.int32)).to(self.device),
+                torch.from_numpy(np.ascontiguousarray(ktab, np.float32)).to(self.device), lut)
+
+    def gather(self, tensors, idx, flip, out):
+        return ops.gather_triplets_u8(tensors, idx, flip, out)
+
+
+class ResidentTrainSet:
+    """The prepared tree's training set kept in device memory: every distinct frame resized ONCE to its 8-bit ``img_hw`` bytes
+    (dfe_resize_strips_u8, the image half of ``PreparedFeeder`` up to the byte), a batch made by one gather launch
+    (dfe_gather_triplets_u8: frame slots -> flip -> lut -> CHW) with no decode, no host-to-device copy and no thread.  The bits
+    are ``PreparedFeeder``'s.  Built over a ``PreparedKITTI``: the sample map, the flip draw and the intrinsics stay its.
+
+    Build: strips are decoded on up to ``num_workers`` threads (at most 16), keyed per frame by (h0, w0, blake2b-128 of the decoded
+    RGB bytes) and given slots in data-list order on the building thread -- consecutive strips of a drive share two frames, so a
+    set holds about a third of its triplets' frames; then decoded again a chunk at a time, uploaded and resized into the store
+    (the number of frames must be known before the store is allocated, and the decoded set does not fit in host memory).
+    Before allocating, ``resident_bytes`` + ``reserve_mb`` (what the step needs) is compared with the device's free memory; a set
+    that does not fit raises DfeError.  EVERY RANK HOLDS THE WHOLE SET: the sample map draws over the whole list.
+    ``cache_dir``: frames.u8 / tri.i32 / K.f32 / meta.json; a cache whose key matches the tree is loaded through np.memmap in
+    pinned chunks and nothing is decoded; anything else rebuilds and overwrites (``write_cache=False``: rebuilds only -- the
+    ranks of a job other than the first, which would write the same files at the same time).
+
+    ``batches(B, n, world, rank)`` then iterates like ``PreparedFeeder`` (same ``batch_indices``); ``fetch(k, out=None)`` launches
+    batch k's gather on the CURRENT stream and returns [images, K_ms, K_inv_ms]: fresh tensors (models.py keeps a closure over
+    images[0]), or the tensors of ``out`` (a captured graph's static inputs)."""
+
+    def __init__(self, source, img_hw, device, num_workers=0, cache_dir=None, reserve_mb=RESIDENT_RESERVE_MB, device_ops=None,
+                 write_cache=True):
+        import time
+        t0 = time.perf_counter()
+        self.src, self.hw, self.device = source, (int(img_hw[0]), int(img_hw[1])), device
+        self.dev = device_ops if device_ops is not None else _HipStore(device)
+        self.N = source.count()
+        self.S = int(source.intrinsics(0)[0].shape[0])
+        self.decoded = 0                               # strips decoded by this build (0: loaded from the cache)
+        key = cache_key(source) if cache_dir else None
+        cached = cache_open(cache_dir, key, self.N, self.S, self.hw) if cache_dir else None
+        sizes = sorted(set(source.frame_hw(i) for i in range(self.N)))
+        if cached is not None:
+            frames, self.tri, self.ktab = cached
+            self.F = int(frames.shape[0])
+            store = self._alloc(reserve_mb)
+            self.dev.load(store, frames)
+            del frames
+        else:
+            self.tri, slot, self.F = plan_frames(source, num_workers)
+            self.decoded += self.N
+            self.ktab = intrinsics_table(source)
+            store = self._alloc(reserve_mb)
+            self._fill(store, slot, num_workers)
+            if cache_dir and write_cache:
+                cache_write(cache_dir, key, self.hw, lambda fh: self.dev.save(store, fh), self.F, self.tri, self.ktab)
+        self.from_cache = cached is not None
+        self.tensors = self.dev.finish(store, self.tri, self.ktab, sizes, self.hw)
+        self.nbytes = resident_bytes(self.F, self.N, self.S, self.hw)
+        self.build_seconds = time.perf_counter() - t0
+        self.B = self.n = None
+        self.world, self.rank, self.k = 1, 0, 0
+
+    def _alloc(self, reserve_mb):
+        need, reserve = resident_bytes(self.F, self.N, self.S, self.hw), int(float(reserve_mb) * (1 << 20))
+        free = int(torch.cuda.mem_get_info(self.device)[0])
+        if need + reserve > free:
+            raise ops.DfeError("ResidentTrainSet: the set needs %d bytes (%d frames of %dx%d for %d triplets) plus a reserve of %d "
+                               "bytes for the training step, but only %d bytes are free on %s: train with --data_source prepared "
+                               "instead (it streams the tree from the host)"
+                               % (need, self.F, self.hw[0], self.hw[1], self.N, reserve, free, self.device))
+        return self.dev.alloc(self.F, self.hw)
+
+    def _fill(self, store, slot, num_workers):
+        """Second pass: the strips that hold a frame's first occurrence, decoded into packed chunks and resized into the store."""
+        todo = [i for i in range(self.N) if (slot[i] >= 0).any()]
+        stride = (self.src.max_strip_bytes + 255) // 256 * 256
+        per = max(_CHUNK_BYTES // stride, 1)
+        for a in range(0, len(todo), per):
+            part = todo[a:a + per]
+            raw = np.zeros(len(part) * stride, np.uint8)
+
+            def fill(j):
+                h, w, _ = self.src.headers[part[j]]
+                self.src.decode(part[j], raw[j * stride:j * stride + 3 * h * w])
+            for _ in _ordered_map(fill, range(len(part)), num_workers):
+                pass
+            self.decoded += len(part)
+            self.dev.resize(store, raw, [self.src.frame_hw(i) for i in part], [j * stride for j in range(len(part))],
+                            slot[part], self.hw)
+
+    # ---------------------------------------------------------------------------------------------------- batches
+    def batches(self, batch_size, num_batches, world=1, rank=0):
+        """Iterate batches 0 .. num_batches-1 of ``batch_indices(k, batch_size, world, rank)``; returns self."""
+        self.B, self.n, self.world, self.rank, self.k = int(batch_size), int(num_batches), int(world), int(rank), 0
+        return self
+
+    def draw(self, k):
+        """(data-list entries, flips) of batch k: ``source.sample`` of its training indices, on the host."""
+        if self.B is None:
+            raise ValueError("ResidentTrainSet: call batches(batch_size, num_batches, world, rank) first")
+        picks = [self.src.sample(i) for i in batch_indices(k, self.B, self.world, self.rank)]
+        return [p[0] for p in picks], [p[1] for p in picks]
+
+    def fetch(self, k, out=None):
+        idx, flip = self.draw(k)
+        return self.dev.gather(self.tensors, idx, flip, out)
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return self.n
+
+    def __next__(self):
+        if self.n is None or self.k >= self.n:
+            raise StopIteration
+        self.k += 1
+        return self.fetch(self.k - 1)
+
+    def close(self):
+        """Nothing runs behind the set (no thread, no side stream): kept for PreparedFeeder's interface."""
 
 
 class _Slot:
