@@ -125,6 +125,15 @@ def ptr(t, strided=False):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def ptr_any(t):
+    """Device pointer of a contiguous HIP tensor of any of the dtypes the entry points take (fp32, fp64, int32, int64, uint8)."""
+    if t.dtype == torch.float64:
+        if not (t.is_cuda and t.is_contiguous()):
+            raise ValueError("a contiguous fp64 HIP tensor expected")
+        return ctypes.c_void_p(t.data_ptr())
+    return ptr(t)
+
+
 def raw_stream():
     """The current HIP stream's handle as an integer.  ``torch.cuda.current_stream()`` builds a Stream object and resolves the
     device index through four Python frames (~9 us under cProfile, ~180 calls per training step: 1.6 ms of the ~17 ms the host

@@ -1,15 +1,15 @@
 // Per-plane arithmetic of the eight-point term (ops_eight_point.hip): Hartley normalisation, a row of the 9-column system, the
-// null direction of the 9x9 normal matrix (cyclic Jacobi), rank 2 (one-sided Jacobi on the 3x3), un-normalisation, OpenCV's
+// null direction of the 9x9 normal matrix and rank 2 (the two iterations of dfe_jacobi.h), un-normalisation, OpenCV's
 // residual.  All in double, as GeometrySolvers.compute_fundmental_mat evaluates it; host and device compile the same text.
 // Every loop has a fixed upper bound: with NaN or inf in the matrix the sweeps run out and the result is non-finite.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "dfe_jacobi.h"
 
 namespace dfe {
 namespace ep {
 
 constexpr int JACOBI9_SWEEPS = 20;     // cyclic sweeps over the 36 pairs; convergence is quadratic, 6-9 sweeps in practice
-constexpr int JACOBI3_SWEEPS = 12;
 constexpr double SQRT2 = 1.4142135623730951;    // 2.0 ** 0.5
 
 struct Norm { double s, tx, ty; };     // T = [[s, 0, tx], [0, s, ty], [0, 0, 1]], tx = -s cx, ty = -s cy
@@ -28,82 +28,12 @@ __host__ __device__ inline void row9(const Norm& n1, const Norm& n2, double x1, 
     for (int j = 0; j < 3; ++j) a[3 * i + j] = p2[i] * p1[j];
 }
 
-// Eigenvectors of the symmetric 9x9 matrix A (row-major, both halves stored; destroyed) by cyclic Jacobi rotations; V receives
-// them as columns.  Element i of either matrix lives at [i * S]: the kernels keep them in LDS, interleaved over the threads of a
-// block (S = threads) or dense (S = 1) -- never in private memory, which would index them dynamically through scratch.  Returns
-// the column of the smallest eigenvalue.
-__host__ __device__ inline int jacobi9(double* A, double* V, int S) {
-  for (int i = 0; i < 81; ++i) V[i * S] = (i % 10 == 0) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < JACOBI9_SWEEPS; ++sweep) {
-    double off = 0.0, tot = 0.0;
-    for (int i = 0; i < 81; ++i) {
-      const double v = A[i * S] * A[i * S];
-      tot += v;
-      if (i % 10 != 0) off += v;
-    }
-    if (off <= 1e-32 * tot) break;          // false for NaN: the sweeps run out
-    for (int p = 0; p < 8; ++p)
-      for (int q = p + 1; q < 9; ++q) {
-        const double apq = A[(9 * p + q) * S];
-        if (apq == 0.0) continue;
-        const double theta = (A[10 * q * S] - A[10 * p * S]) / (2.0 * apq);
-        const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        A[10 * p * S] -= t * apq;
-        A[10 * q * S] += t * apq;
-        A[(9 * p + q) * S] = 0.0;
-        A[(9 * q + p) * S] = 0.0;
-        for (int k = 0; k < 9; ++k) {
-          if (k != p && k != q) {
-            const double akp = A[(9 * k + p) * S], akq = A[(9 * k + q) * S];
-            const double np = c * akp - s * akq, nq = s * akp + c * akq;
-            A[(9 * k + p) * S] = np; A[(9 * p + k) * S] = np;
-            A[(9 * k + q) * S] = nq; A[(9 * q + k) * S] = nq;
-          }
-          const double vkp = V[(9 * k + p) * S], vkq = V[(9 * k + q) * S];
-          V[(9 * k + p) * S] = c * vkp - s * vkq;
-          V[(9 * k + q) * S] = s * vkp + c * vkq;
-        }
-      }
-  }
-  int best = 0;
-  for (int i = 1; i < 9; ++i)
-    if (A[10 * i * S] < A[10 * best * S]) best = i;
-  return best;
-}
-
-// F <- F with its smallest singular value set to zero: one-sided Jacobi makes the columns of G = F W orthogonal (F = G W^T);
-// the column of the smallest norm is sigma_3 u_3 and that column of W is v_3.
+// F <- F with its smallest singular value set to zero: with the columns of G = F W orthogonal (F = G W^T), the column of the
+// smallest norm is sigma_3 u_3 and that column of W is v_3.
 __host__ __device__ inline void rank2(double* F) {
   double G[9], W[9];
-  for (int i = 0; i < 9; ++i) { G[i] = F[i]; W[i] = 0.0; }
-  W[0] = W[4] = W[8] = 1.0;
-  for (int sweep = 0; sweep < JACOBI3_SWEEPS; ++sweep) {
-    int rotated = 0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-        for (int k = 0; k < 3; ++k) {
-          alpha += G[3 * k + p] * G[3 * k + p];
-          beta += G[3 * k + q] * G[3 * k + q];
-          gamma += G[3 * k + p] * G[3 * k + q];
-        }
-        if (!(fabs(gamma) > 1e-17 * sqrt(alpha * beta))) continue;       // orthogonal already (or NaN)
-        ++rotated;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int k = 0; k < 3; ++k) {
-          const double gp = G[3 * k + p], gq = G[3 * k + q];
-          G[3 * k + p] = c * gp - s * gq;
-          G[3 * k + q] = s * gp + c * gq;
-          const double wp = W[3 * k + p], wq = W[3 * k + q];
-          W[3 * k + p] = c * wp - s * wq;
-          W[3 * k + q] = s * wp + c * wq;
-        }
-      }
-    if (!rotated) break;
-  }
+  for (int i = 0; i < 9; ++i) G[i] = F[i];
+  orthogonalize3(G, W);
   double nrm[3];
   for (int j = 0; j < 3; ++j) nrm[j] = G[j] * G[j] + G[3 + j] * G[3 + j] + G[6 + j] * G[6 + j];
   // the column of the smallest norm, picked by comparisons (a run-time column index would put G and W into private memory)
@@ -117,7 +47,7 @@ __host__ __device__ inline void rank2(double* F) {
 // _eight_point after its normal matrix M (destroyed; V: 81 more doubles; both with element stride S): null direction, rank 2,
 // F = T2^T Fn T1
 __host__ __device__ inline void solve_normal(double* M, double* V, int S, const Norm& n1, const Norm& n2, double* F) {
-  const int col = jacobi9(M, V, S);
+  const int col = jacobi_sym<9>(M, V, S, JACOBI9_SWEEPS);
   double Fn[9], X[9];
   for (int i = 0; i < 9; ++i) Fn[i] = V[(9 * i + col) * S];
   rank2(Fn);

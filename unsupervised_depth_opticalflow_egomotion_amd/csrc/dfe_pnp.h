@@ -1,17 +1,17 @@
 // Per-plane arithmetic of the PnP term (ops_pnp.hip): the back-projected point, the six-point DLT's 12x12 normal matrix and its
-// null direction (cyclic Jacobi, as dfe_eight_point.h's jacobi9 -- that one is fixed at 9x9, this one takes the size), the
-// projection onto SO(3) (one-sided Jacobi on the 3x3, as ep::rank2 uses it), the reprojection test, one match's share of the
+// null direction (dfe_jacobi.h's cyclic Jacobi), the projection onto SO(3) (its one-sided Jacobi on the 3x3, as ep::rank2 uses
+// it), the reprojection test, one match's share of the
 // Levenberg-Marquardt sums, the 6x6 solve, exp and log on SO(3).  All in double, as GeometrySolvers.pnp evaluates it; host and
 // device compile the same text.  Every loop has a fixed upper bound: with NaN or inf the sweeps run out and the result is
 // non-finite.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "dfe_jacobi.h"
 
 namespace dfe {
 namespace pnp {
 
 constexpr int JACOBI12_SWEEPS = 24;    // cyclic sweeps over the 66 pairs; 8-11 in practice
-constexpr int JACOBI3_SWEEPS = 12;
 constexpr int LM_SUMS = 28;            // 21 of H (upper triangle, row-major), 6 of g, the cost
 
 struct Cam { double fx, fy, cx, cy; };     // K[0][0], K[1][1], K[0][2], K[1][2] as GeometrySolvers.pnp reads them
@@ -48,84 +48,13 @@ __host__ __device__ inline void dlt_normal(const double* S, const double* Su, co
     }
 }
 
-// Eigenvectors of the symmetric 12x12 matrix A (row-major, both halves stored; destroyed) by cyclic Jacobi rotations; V receives
-// them as columns.  Element i of either matrix lives at [i * S]: LDS, interleaved over the threads of a block, never private
-// memory.  Returns the column of the smallest eigenvalue.
-__host__ __device__ inline int jacobi12(double* A, double* V, int S) {
-  constexpr int N = 12;
-  for (int i = 0; i < N * N; ++i) V[i * S] = (i % (N + 1) == 0) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < JACOBI12_SWEEPS; ++sweep) {
-    double off = 0.0, tot = 0.0;
-    for (int i = 0; i < N * N; ++i) {
-      const double v = A[i * S] * A[i * S];
-      tot += v;
-      if (i % (N + 1) != 0) off += v;
-    }
-    if (off <= 1e-32 * tot) break;          // false for NaN: the sweeps run out
-    for (int p = 0; p < N - 1; ++p)
-      for (int q = p + 1; q < N; ++q) {
-        const double apq = A[(N * p + q) * S];
-        if (apq == 0.0) continue;
-        const double theta = (A[(N + 1) * q * S] - A[(N + 1) * p * S]) / (2.0 * apq);
-        const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        A[(N + 1) * p * S] -= t * apq;
-        A[(N + 1) * q * S] += t * apq;
-        A[(N * p + q) * S] = 0.0;
-        A[(N * q + p) * S] = 0.0;
-        for (int k = 0; k < N; ++k) {
-          if (k != p && k != q) {
-            const double akp = A[(N * k + p) * S], akq = A[(N * k + q) * S];
-            const double np = c * akp - s * akq, nq = s * akp + c * akq;
-            A[(N * k + p) * S] = np; A[(N * p + k) * S] = np;
-            A[(N * k + q) * S] = nq; A[(N * q + k) * S] = nq;
-          }
-          const double vkp = V[(N * k + p) * S], vkq = V[(N * k + q) * S];
-          V[(N * k + p) * S] = c * vkp - s * vkq;
-          V[(N * k + q) * S] = s * vkp + c * vkq;
-        }
-      }
-  }
-  int best = 0;
-  for (int i = 1; i < N; ++i)
-    if (A[(N + 1) * i * S] < A[(N + 1) * best * S]) best = i;
-  return best;
-}
-
 // _pnp_hypotheses after the null direction P [3,4]: R = U W^T sign(det), T = P[:, 3] sign / mean(singular values), from the SVD of
 // P[:, :3] by a one-sided Jacobi: the columns of G = A W are made orthogonal, their norms are the singular values.
 __host__ __device__ inline void pose_from_dlt(const double* P, double* R, double* T) {
   double G[9], W[9];
   for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) { G[3 * i + j] = P[4 * i + j]; W[3 * i + j] = i == j ? 1.0 : 0.0; }
-  for (int sweep = 0; sweep < JACOBI3_SWEEPS; ++sweep) {
-    int rotated = 0;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-        for (int k = 0; k < 3; ++k) {
-          alpha += G[3 * k + p] * G[3 * k + p];
-          beta += G[3 * k + q] * G[3 * k + q];
-          gamma += G[3 * k + p] * G[3 * k + q];
-        }
-        if (!(fabs(gamma) > 1e-17 * sqrt(alpha * beta))) continue;       // orthogonal already (or NaN)
-        ++rotated;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int k = 0; k < 3; ++k) {
-          const double gp = G[3 * k + p], gq = G[3 * k + q];
-          G[3 * k + p] = c * gp - s * gq;
-          G[3 * k + q] = s * gp + c * gq;
-          const double wp = W[3 * k + p], wq = W[3 * k + q];
-          W[3 * k + p] = c * wp - s * wq;
-          W[3 * k + q] = s * wp + c * wq;
-        }
-      }
-    if (!rotated) break;
-  }
+    for (int j = 0; j < 3; ++j) G[3 * i + j] = P[4 * i + j];
+  orthogonalize3(G, W);
   double sv[3];
   for (int j = 0; j < 3; ++j) sv[j] = sqrt(G[j] * G[j] + G[3 + j] * G[3 + j] + G[6 + j] * G[6 + j]);
   for (int i = 0; i < 3; ++i)

@@ -5,60 +5,41 @@
 //
 //   k_ep_matches    one thread per match: (x, y, x + u, y + v), the sums in fp32, widened -> ws
 //   k_ep_hyp        one thread per (plane, hypothesis): normalised eight-point on its 8 matches, its 9x9 matrices in LDS -> ws
-//   k_ep_score      a tile of EP_MATCH_TILE matches per block (one per thread), hypotheses in tiles of EP_HYP_TILE through LDS:
+//   k_ep_score      a tile of MATCH_TILE matches per block (one per thread), hypotheses in tiles of HYP_TILE through LDS:
 //                   inlier counts by wave ballots, integer atomics
 //   k_ep_consensus  one block per plane: best hypothesis (ties: lowest index), its inlier set, two weighted refits, F / F[2][2]
 //   k_ep_loss_fwd / k_ep_loss_bwd   one thread per sample / per (sample, direction)
+// The draw, the workspace, scoring, the consensus skeleton and the launch sequence are dfe_ransac.h's, shared with ops_pnp.hip;
+// here: the model, the hypothesis kernel, the refit, the loss.
 // No float atomics: every float sum has an order fixed by thread index; same bits run after run.
 #include "dfe_internal.h"
 #include "dfe_eight_point.h"
+#include "dfe_ransac.h"
 
 namespace dfe {
 namespace {
 
-constexpr int EP_THREADS = 256;
-constexpr int EP_MATCH_TILE = 256;     // matches per block of k_ep_score
-constexpr int EP_HYP_TILE = 64;        // hypotheses staged in LDS at a time
-constexpr int EP_HYP_THREADS = 32;        // k_ep_hyp: 2 x 81 doubles of LDS per thread, 40.5 KiB per block
-constexpr int EP_MAX_NUM = 16384;      // the draw's limit of the triangulation term, kept here
-constexpr int EP_MAX_HYP = 4096;
+using ransac::THREADS;
+constexpr int EP_HYP_THREADS = 32;     // k_ep_hyp: 2 x 81 doubles of LDS per thread, 40.5 KiB per block
 constexpr int EP_RED = 15;             // sums reduced side by side (the 45 entries of the normal matrix in three rounds)
 
-__host__ __device__ inline long round16(long v) { return (v + 15) & ~15L; }
-
-struct EpWs {
-  double* m;        // [2B, num, 4]
-  double* Fh;       // [2B, hyp, 9]
-  int* counts;      // [2B, hyp]
-  int* w1;          // [2B, num]
-  int* w2;          // [2B, num]
+struct EpModel {
+  static constexpr int PT = 4, HP = 9, MIN = 8;     // (x1, y1, x2, y2); F row-major; the eight-point algorithm's set
+  struct Ctx {};
+  static __device__ __forceinline__ bool inlier(const Ctx&, const double* F, const double* m, double thr2) {
+    return ep::inlier(F, m[0], m[1], m[2], m[3], thr2);
+  }
 };
-inline long ep_off_fh(int B, int num) { return 32L * 2 * B * num; }
-inline long ep_off_counts(int B, int num, int hyp) { return ep_off_fh(B, num) + round16(72L * 2 * B * hyp); }
-inline long ep_off_w1(int B, int num, int hyp) { return ep_off_counts(B, num, hyp) + round16(4L * 2 * B * hyp); }
-inline long ep_off_w2(int B, int num, int hyp) { return ep_off_w1(B, num, hyp) + round16(4L * 2 * B * num); }
-inline long ep_ws_bytes(int B, int num, int hyp) { return ep_off_w2(B, num, hyp) + round16(4L * 2 * B * num); }
-inline EpWs ep_ws(void* ws, int B, int num, int hyp) {
-  char* p = static_cast<char*>(ws);
-  return EpWs{reinterpret_cast<double*>(p), reinterpret_cast<double*>(p + ep_off_fh(B, num)),
-              reinterpret_cast<int*>(p + ep_off_counts(B, num, hyp)), reinterpret_cast<int*>(p + ep_off_w1(B, num, hyp)),
-              reinterpret_cast<int*>(p + ep_off_w2(B, num, hyp))};
-}
 
-__global__ void __launch_bounds__(EP_THREADS) k_ep_matches(const float* __restrict__ flow_bwd, const float* __restrict__ flow_fwd,
-                                                            const int* __restrict__ idx, const long long* __restrict__ pick,
-                                                            double* __restrict__ m, int B, int H, int W, int k, int num) {
-  const int j = blockIdx.x * EP_THREADS + threadIdx.x;
+__global__ void __launch_bounds__(THREADS) k_ep_matches(const float* __restrict__ flow_bwd, const float* __restrict__ flow_fwd,
+                                                         const int* __restrict__ idx, const long long* __restrict__ pick,
+                                                         double* __restrict__ m, int B, int H, int W, int k, int num) {
+  const int j = blockIdx.x * THREADS + threadIdx.x;
   const int plane = blockIdx.y, d = plane / B, b = plane - d * B;
   if (j >= num) return;
-  long long p = pick[j];
-  p = p < 0 ? 0 : (p > k - 1 ? k - 1 : p);
-  const int HW = H * W;
-  int pix = idx[static_cast<long>(plane) * k + p];
-  pix = pix < 0 ? 0 : (pix > HW - 1 ? HW - 1 : pix);
-  const float* fl = (d ? flow_fwd : flow_bwd) + static_cast<long>(b) * 2 * HW;
-  const float y = static_cast<float>(pix / W), x = static_cast<float>(pix - (pix / W) * W);
-  const float x2 = x + fl[pix], y2 = y + fl[HW + pix];
+  const ransac::Match mt = ransac::load_match(d ? flow_fwd : flow_bwd, idx, pick, plane, b, j, k, H, W);
+  const float y = static_cast<float>(mt.y), x = static_cast<float>(mt.x);
+  const float x2 = x + mt.u, y2 = y + mt.v;
   double* o = m + (static_cast<long>(plane) * num + j) * 4;
   o[0] = x; o[1] = y; o[2] = x2; o[3] = y2;
 }
@@ -105,84 +86,35 @@ __global__ void __launch_bounds__(EP_HYP_THREADS) k_ep_hyp(const double* __restr
   for (int i = 0; i < 9; ++i) o[i] = F[i];
 }
 
-__global__ void __launch_bounds__(EP_MATCH_TILE) k_ep_score(const double* __restrict__ m, const double* __restrict__ Fh,
-                                                             int* __restrict__ counts, int num, int hyp, double thr2) {
-  __shared__ double sF[EP_HYP_TILE * 9];
-  __shared__ int sC[EP_HYP_TILE];
-  const int j = blockIdx.x * EP_MATCH_TILE + threadIdx.x;
-  const int plane = blockIdx.y;
-  const bool live = j < num;
-  double x1 = 0.0, y1 = 0.0, x2 = 0.0, y2 = 0.0;
-  if (live) {
-    const double* p = m + (static_cast<long>(plane) * num + j) * 4;
-    x1 = p[0]; y1 = p[1]; x2 = p[2]; y2 = p[3];
-  }
-  for (int h0 = 0; h0 < hyp; h0 += EP_HYP_TILE) {
-    const int nh = hyp - h0 < EP_HYP_TILE ? hyp - h0 : EP_HYP_TILE;
-    for (int i = threadIdx.x; i < nh * 9; i += EP_MATCH_TILE) sF[i] = Fh[(static_cast<long>(plane) * hyp + h0) * 9 + i];
-    if (threadIdx.x < EP_HYP_TILE) sC[threadIdx.x] = 0;
-    __syncthreads();
-    for (int hh = 0; hh < nh; ++hh) {
-      const bool in = live && ep::inlier(sF + hh * 9, x1, y1, x2, y2, thr2);
-      const unsigned long long bal = __ballot(in);
-      if ((threadIdx.x & 63) == 0 && bal != 0ull) atomicAdd(&sC[hh], __popcll(bal));
-    }
-    __syncthreads();
-    if (static_cast<int>(threadIdx.x) < nh && sC[threadIdx.x] != 0)
-      atomicAdd(&counts[static_cast<long>(plane) * hyp + h0 + threadIdx.x], sC[threadIdx.x]);
-    __syncthreads();
-  }
-}
-
-// EP_RED sums side by side, each in a fixed order: every thread's strided partial, then a tree over the threads.  v <- the sums.
-__device__ void block_sum_n(double* v, double* red) {
-  for (int i = 0; i < EP_RED; ++i) red[i * EP_THREADS + threadIdx.x] = v[i];
-  __syncthreads();
-  for (int s = EP_THREADS / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s)
-      for (int i = 0; i < EP_RED; ++i) red[i * EP_THREADS + threadIdx.x] += red[i * EP_THREADS + threadIdx.x + s];
-    __syncthreads();
-  }
-  for (int i = 0; i < EP_RED; ++i) v[i] = red[i * EP_THREADS];
-  __syncthreads();
-}
-
-__device__ int block_sum_int(int v, int* ired) {
-  ired[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = EP_THREADS / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) ired[threadIdx.x] += ired[threadIdx.x + s];
-    __syncthreads();
-  }
-  const int r = ired[0];
-  __syncthreads();
-  return r;
+__global__ void __launch_bounds__(ransac::MATCH_TILE) k_ep_score(const double* __restrict__ m, const double* __restrict__ Fh,
+                                                                  int* __restrict__ counts, int num, int hyp, double thr2) {
+  ransac::score_body<EpModel>(EpModel::Ctx{}, m, Fh, counts, num, hyp, thr2);
 }
 
 // _eight_point(m, w) of one plane by the whole block: weighted Hartley sums, the normal matrix, thread 0 solves -> sF (LDS)
 __device__ void refit(const double* __restrict__ mp, const int* __restrict__ w, int num, double* red, double* sM, double* sV, double* sF) {
   double v[EP_RED];
   for (int i = 0; i < EP_RED; ++i) v[i] = 0.0;
-  for (int j = threadIdx.x; j < num; j += EP_THREADS) {
+  for (int j = threadIdx.x; j < num; j += THREADS) {
     const double wj = w[j];
     v[0] += mp[4 * j] * wj; v[1] += mp[4 * j + 1] * wj; v[2] += mp[4 * j + 2] * wj; v[3] += mp[4 * j + 3] * wj;
     v[4] += wj;
   }
-  block_sum_n(v, red);
+  ransac::block_sum<EP_RED>(v, red);
   const double cnt = v[4] < 1.0 ? 1.0 : v[4];
   const double cx1 = v[0] / cnt, cy1 = v[1] / cnt, cx2 = v[2] / cnt, cy2 = v[3] / cnt;
   for (int i = 0; i < EP_RED; ++i) v[i] = 0.0;
-  for (int j = threadIdx.x; j < num; j += EP_THREADS) {
+  for (int j = threadIdx.x; j < num; j += THREADS) {
     const double wj = w[j];
     const double ax = mp[4 * j] - cx1, ay = mp[4 * j + 1] - cy1, bx = mp[4 * j + 2] - cx2, by = mp[4 * j + 3] - cy2;
     v[0] += sqrt(ax * ax + ay * ay) * wj;
     v[1] += sqrt(bx * bx + by * by) * wj;
   }
-  block_sum_n(v, red);
+  ransac::block_sum<EP_RED>(v, red);
   const ep::Norm n1 = ep::make_norm(cx1, cy1, v[0] / cnt), n2 = ep::make_norm(cx2, cy2, v[1] / cnt);
   double acc[45];
   for (int i = 0; i < 45; ++i) acc[i] = 0.0;
-  for (int j = threadIdx.x; j < num; j += EP_THREADS) {
+  for (int j = threadIdx.x; j < num; j += THREADS) {
     const double wj = w[j];
     double a[9];
     ep::row9(n1, n2, mp[4 * j], mp[4 * j + 1], mp[4 * j + 2], mp[4 * j + 3], a);
@@ -190,9 +122,9 @@ __device__ void refit(const double* __restrict__ mp, const int* __restrict__ w, 
     for (int r = 0; r < 9; ++r)
       for (int c = r; c < 9; ++c) acc[e++] += a[r] * wj * a[c];
   }
-  block_sum_n(acc, red);
-  block_sum_n(acc + EP_RED, red);
-  block_sum_n(acc + 2 * EP_RED, red);
+  ransac::block_sum<EP_RED>(acc, red);
+  ransac::block_sum<EP_RED>(acc + EP_RED, red);
+  ransac::block_sum<EP_RED>(acc + 2 * EP_RED, red);
   if (threadIdx.x == 0) {
     int e = 0;
     for (int r = 0; r < 9; ++r)
@@ -202,68 +134,24 @@ __device__ void refit(const double* __restrict__ mp, const int* __restrict__ w, 
   __syncthreads();
 }
 
-__global__ void __launch_bounds__(EP_THREADS) k_ep_consensus(const double* __restrict__ m, const double* __restrict__ Fh,
-                                                              const int* __restrict__ counts, int* __restrict__ w1,
-                                                              int* __restrict__ w2, double* __restrict__ F64, float* __restrict__ F32,
-                                                              int* __restrict__ info, int num, int hyp, double thr2) {
-  __shared__ double red[EP_RED * EP_THREADS];
+__global__ void __launch_bounds__(THREADS) k_ep_consensus(const double* __restrict__ m, const double* __restrict__ Fh,
+                                                           const int* __restrict__ counts, int* __restrict__ w1,
+                                                           int* __restrict__ w2, double* __restrict__ F64, float* __restrict__ F32,
+                                                           int* __restrict__ info, int num, int hyp, double thr2) {
+  __shared__ double red[EP_RED * THREADS];
   __shared__ double sM[81], sV[81], sF[9];
-  __shared__ int ired[EP_THREADS], ibest[EP_THREADS];
   const int plane = blockIdx.x;
   const double* mp = m + static_cast<long>(plane) * num * 4;
-  const int* cp = counts + static_cast<long>(plane) * hyp;
-  int* w1p = w1 + static_cast<long>(plane) * num;
-  int* w2p = w2 + static_cast<long>(plane) * num;
-  // the hypothesis with the most inliers, ties to the lowest index
-  int bc = -1, bh = 0;
-  for (int h = threadIdx.x; h < hyp; h += EP_THREADS)
-    if (cp[h] > bc) { bc = cp[h]; bh = h; }
-  ired[threadIdx.x] = bc;
-  ibest[threadIdx.x] = bh;
-  __syncthreads();
-  for (int s = EP_THREADS / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) {
-      const int oc = ired[threadIdx.x + s], oh = ibest[threadIdx.x + s];
-      if (oc > ired[threadIdx.x] || (oc == ired[threadIdx.x] && oh < ibest[threadIdx.x])) { ired[threadIdx.x] = oc; ibest[threadIdx.x] = oh; }
-    }
-    __syncthreads();
-  }
-  const int best = ibest[0], best_count = ired[0];
-  __syncthreads();
-  if (threadIdx.x < 9) sF[threadIdx.x] = Fh[(static_cast<long>(plane) * hyp + best) * 9 + threadIdx.x];
-  __syncthreads();
-  int c = 0;
-  for (int j = threadIdx.x; j < num; j += EP_THREADS) {
-    const int in = ep::inlier(sF, mp[4 * j], mp[4 * j + 1], mp[4 * j + 2], mp[4 * j + 3], thr2) ? 1 : 0;
-    w1p[j] = in;
-    c += in;
-  }
-  int n1 = block_sum_int(c, ired);
-  if (n1 < 8) {                           // no consensus: all matches
-    for (int j = threadIdx.x; j < num; j += EP_THREADS) w1p[j] = 1;
-    n1 = num;
-  }
-  refit(mp, w1p, num, red, sM, sV, sF);   // every thread reads back only the weights it wrote
-  c = 0;
-  for (int j = threadIdx.x; j < num; j += EP_THREADS) {
-    const int in = ep::inlier(sF, mp[4 * j], mp[4 * j + 1], mp[4 * j + 2], mp[4 * j + 3], thr2) ? 1 : 0;
-    w2p[j] = in;
-    c += in;
-  }
-  int n2 = block_sum_int(c, ired);
-  if (n2 < 8) {                           // keep the previous set
-    for (int j = threadIdx.x; j < num; j += EP_THREADS) w2p[j] = w1p[j];
-    n2 = n1;
-  }
-  refit(mp, w2p, num, red, sM, sV, sF);
-  if (threadIdx.x < 9) {
-    const double f = sF[threadIdx.x] / sF[8];
-    F64[plane * 9 + threadIdx.x] = f;
-    F32[plane * 9 + threadIdx.x] = static_cast<float>(f);
-  }
-  if (threadIdx.x == 0) {
-    info[plane * 4] = best; info[plane * 4 + 1] = best_count; info[plane * 4 + 2] = n1; info[plane * 4 + 3] = n2;
-  }
+  ransac::consensus_body<EpModel>(
+      EpModel::Ctx{}, m, Fh, counts, w1, w2, info, num, hyp, thr2, sF,
+      [&](const int* w, int) { refit(mp, w, num, red, sM, sV, sF); },
+      [&]() {
+        if (threadIdx.x < 9) {
+          const double f = sF[threadIdx.x] / sF[8];
+          F64[plane * 9 + threadIdx.x] = f;
+          F32[plane * 9 + threadIdx.x] = static_cast<float>(f);
+        }
+      });
 }
 
 // ---------------------------------------------------------------------------------------------- loss
@@ -323,31 +211,24 @@ using namespace dfe;
 
 extern "C" long dfe_eight_point_ws_bytes(int B, int num, int hyp) {
   if (B <= 0 || num <= 0 || hyp <= 0) return 0;
-  return ep_ws_bytes(B, num, hyp);
+  return ransac::ws_offsets(EpModel::PT, EpModel::HP, B, num, hyp).bytes;
 }
 
 extern "C" int dfe_fundamental_ransac(const float* flow_bwd, const float* flow_fwd, const int* idx, const long long* pick,
                                       const int* sets, double* F64, float* F32, int* info, void* ws, int B, int H, int W, int k,
                                       int num, int hyp, double thresh, void* stream) {
-  if (!flow_bwd || !flow_fwd || !idx || !pick || !sets || !F64 || !F32 || !info || !ws) return DFE_ERR_NULL;
-  if (B <= 0 || B > 16384 || H < 1 || W < 1 || k <= 0 || num < 8 || hyp < 1) return DFE_ERR_DIMS;
-  if (static_cast<long>(H) * W >= (1L << 28) || k > H * W) return DFE_ERR_DIMS;
-  if (num > EP_MAX_NUM || hyp > EP_MAX_HYP) return DFE_ERR_UNSUPPORTED;
-  if (!aligned16(ws) || !aligned8(F64)) return DFE_ERR_DIMS;
+  const bool have_all = flow_bwd && flow_fwd && idx && pick && sets && F64 && F32 && info && ws;
+  const int rc = ransac::check_args(have_all, B, H, W, k, num, hyp, EpModel::MIN, ws, F64);
+  if (rc != DFE_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const EpWs w = ep_ws(ws, B, num, hyp);
+  const ransac::Ws w = ransac::ws_sections(ws, ransac::ws_offsets(EpModel::PT, EpModel::HP, B, num, hyp));
   const double thr2 = thresh * thresh;
-  // the counts start at zero; everything else in ws is written before it is read
-  if (hipMemsetAsync(w.counts, 0, static_cast<size_t>(4L * 2 * B * hyp), st) != hipSuccess) return DFE_ERR_LAUNCH;
-  const dim3 gm(static_cast<unsigned>((num + EP_THREADS - 1) / EP_THREADS), 2 * B);
-  k_ep_matches<<<gm, EP_THREADS, 0, st>>>(flow_bwd, flow_fwd, idx, pick, w.m, B, H, W, k, num);
-  DFE_LAUNCH_CHECK();
-  k_ep_hyp<<<dim3(static_cast<unsigned>((hyp + EP_HYP_THREADS - 1) / EP_HYP_THREADS), 2 * B), EP_HYP_THREADS, 0, st>>>(w.m, sets, w.Fh, B, num, hyp);
-  DFE_LAUNCH_CHECK();
-  k_ep_score<<<dim3(static_cast<unsigned>((num + EP_MATCH_TILE - 1) / EP_MATCH_TILE), 2 * B), EP_MATCH_TILE, 0, st>>>(w.m, w.Fh, w.counts, num, hyp, thr2);
-  DFE_LAUNCH_CHECK();
-  k_ep_consensus<<<2 * B, EP_THREADS, 0, st>>>(w.m, w.Fh, w.counts, w.w1, w.w2, F64, F32, info, num, hyp, thr2);
-  return launch_status();
+  return ransac::launch_all(
+      w.counts, B, num, hyp, EP_HYP_THREADS, st,
+      [&](dim3 g) { k_ep_matches<<<g, THREADS, 0, st>>>(flow_bwd, flow_fwd, idx, pick, w.m, B, H, W, k, num); },
+      [&](dim3 g) { k_ep_hyp<<<g, EP_HYP_THREADS, 0, st>>>(w.m, sets, w.hyps, B, num, hyp); },
+      [&](dim3 g) { k_ep_score<<<g, ransac::MATCH_TILE, 0, st>>>(w.m, w.hyps, w.counts, num, hyp, thr2); },
+      [&](dim3 g) { k_ep_consensus<<<g, THREADS, 0, st>>>(w.m, w.hyps, w.counts, w.w1, w.w2, F64, F32, info, num, hyp, thr2); });
 }
 
 extern "C" int dfe_eight_point_loss_fwd(const float* E, const float* Kt_inv, const float* K_inv, const float* F32, float* loss,

@@ -5,73 +5,53 @@
 //
 //   k_pnp_points     one thread per match: the point K_inv (x, y, 1) disp_t formed in double, (x + u, y + v) in fp32, widened -> ws
 //   k_pnp_hyp        one thread per (plane, hypothesis): six-point DLT on its 6 matches, its two 12x12 matrices in LDS -> ws
-//   k_pnp_score      a tile of PNP_MATCH_TILE matches per block (one per thread), hypotheses in tiles of PNP_HYP_TILE through
-//                    LDS: inlier counts by wave ballots, integer atomics
+//   k_pnp_score      a tile of MATCH_TILE matches per block (one per thread), hypotheses in tiles of HYP_TILE through LDS:
+//                    inlier counts by wave ballots, integer atomics
 //   k_pnp_consensus  one block per plane: best hypothesis (ties: lowest index), its inlier set, Levenberg-Marquardt on SE(3),
 //                    the re-scored set, Levenberg-Marquardt again, so3 log
 //   k_pnp_loss_fwd / k_pnp_loss_bwd   one thread per sample / per (sample, direction)
+// The draw, the workspace, scoring, the consensus skeleton and the launch sequence are dfe_ransac.h's, shared with
+// ops_eight_point.hip; here: the model, the hypothesis kernel, the refinement, the loss.
 // No float atomics: every float sum has an order fixed by thread index; same bits run after run.
 #include "dfe_internal.h"
 #include "dfe_pnp.h"
+#include "dfe_ransac.h"
 
 namespace dfe {
 namespace {
 
-constexpr int PNP_THREADS = 256;
-constexpr int PNP_WAVES = PNP_THREADS / 64;
-constexpr int PNP_MATCH_TILE = 256;    // matches per block of k_pnp_score
-constexpr int PNP_HYP_TILE = 64;       // hypotheses staged in LDS at a time
+using ransac::THREADS;
+constexpr int PNP_WAVES = THREADS / 64;
 constexpr int PNP_HYP_THREADS = 32;    // k_pnp_hyp: 2 x 144 doubles of LDS per thread, 72 KiB per block
-constexpr int PNP_MAX_NUM = 16384;     // the draw's limit of the triangulation term, kept here
-constexpr int PNP_MAX_HYP = 4096;
-constexpr int PNP_PT = 5;              // doubles per match: X, Y, Z, x2, y2
-constexpr int PNP_POSE = 12;           // doubles per hypothesis: R row-major, T
 
-__host__ __device__ inline long pnp_round16(long v) { return (v + 15) & ~15L; }
-
-struct PnpWs {
-  double* m;        // [2B, num, 5]
-  double* Ph;       // [2B, hyp, 12]
-  int* counts;      // [2B, hyp]
-  int* w1;          // [2B, num]
-  int* w2;          // [2B, num]
+struct PnpModel {
+  static constexpr int PT = 5, HP = 12, MIN = 6;    // X, Y, Z, x2, y2; R row-major, T; the six-point DLT's set
+  using Ctx = pnp::Cam;
+  static __device__ __forceinline__ bool inlier(const Ctx& cam, const double* P, const double* m, double thr2) {
+    return pnp::inlier(cam, P, P + 9, m, thr2);
+  }
 };
-inline long pnp_off_ph(int B, int num) { return 8L * PNP_PT * 2 * B * num; }
-inline long pnp_off_counts(int B, int num, int hyp) { return pnp_off_ph(B, num) + 8L * PNP_POSE * 2 * B * hyp; }
-inline long pnp_off_w1(int B, int num, int hyp) { return pnp_off_counts(B, num, hyp) + pnp_round16(4L * 2 * B * hyp); }
-inline long pnp_off_w2(int B, int num, int hyp) { return pnp_off_w1(B, num, hyp) + pnp_round16(4L * 2 * B * num); }
-inline long pnp_ws_bytes(int B, int num, int hyp) { return pnp_off_w2(B, num, hyp) + pnp_round16(4L * 2 * B * num); }
-inline PnpWs pnp_ws(void* ws, int B, int num, int hyp) {
-  char* p = static_cast<char*>(ws);
-  return PnpWs{reinterpret_cast<double*>(p), reinterpret_cast<double*>(p + pnp_off_ph(B, num)),
-               reinterpret_cast<int*>(p + pnp_off_counts(B, num, hyp)), reinterpret_cast<int*>(p + pnp_off_w1(B, num, hyp)),
-               reinterpret_cast<int*>(p + pnp_off_w2(B, num, hyp))};
-}
 
 __device__ __forceinline__ pnp::Cam load_cam(const float* __restrict__ K, int b) {
   return pnp::Cam{static_cast<double>(K[b * 9]), static_cast<double>(K[b * 9 + 4]), static_cast<double>(K[b * 9 + 2]),
                   static_cast<double>(K[b * 9 + 5])};
 }
 
-__global__ void __launch_bounds__(PNP_THREADS) k_pnp_points(const float* __restrict__ flow_bwd, const float* __restrict__ flow_fwd,
-                                                             const float* __restrict__ disp_t, const int* __restrict__ idx,
-                                                             const long long* __restrict__ pick, const float* __restrict__ K_inv,
-                                                             double* __restrict__ m, int B, int H, int W, int k, int num) {
-  const int j = blockIdx.x * PNP_THREADS + threadIdx.x;
+__global__ void __launch_bounds__(THREADS) k_pnp_points(const float* __restrict__ flow_bwd, const float* __restrict__ flow_fwd,
+                                                         const float* __restrict__ disp_t, const int* __restrict__ idx,
+                                                         const long long* __restrict__ pick, const float* __restrict__ K_inv,
+                                                         double* __restrict__ m, int B, int H, int W, int k, int num) {
+  const int j = blockIdx.x * THREADS + threadIdx.x;
   const int plane = blockIdx.y, d = plane / B, b = plane - d * B;
   if (j >= num) return;
-  long long p = pick[j];
-  p = p < 0 ? 0 : (p > k - 1 ? k - 1 : p);
-  const int HW = H * W;
-  int pix = idx[static_cast<long>(plane) * k + p];
-  pix = pix < 0 ? 0 : (pix > HW - 1 ? HW - 1 : pix);
-  const float* fl = (d ? flow_fwd : flow_bwd) + static_cast<long>(b) * 2 * HW;
-  const float y = static_cast<float>(pix / W), x = static_cast<float>(pix - (pix / W) * W);
-  const float x2 = x + fl[pix], y2 = y + fl[HW + pix];
+  const ransac::Match mt = ransac::load_match(d ? flow_fwd : flow_bwd, idx, pick, plane, b, j, k, H, W);
+  const int pix = mt.pix, HW = H * W;
+  const float y = static_cast<float>(mt.y), x = static_cast<float>(mt.x);
+  const float x2 = x + mt.u, y2 = y + mt.v;
   const double depth = disp_t[static_cast<long>(b) * HW + pix];
   const float* Ki = K_inv + b * 9;
   const double xd = x, yd = y;
-  double* o = m + (static_cast<long>(plane) * num + j) * PNP_PT;
+  double* o = m + (static_cast<long>(plane) * num + j) * PnpModel::PT;
   for (int i = 0; i < 3; ++i)
     o[i] = ((static_cast<double>(Ki[3 * i]) * xd + static_cast<double>(Ki[3 * i + 1]) * yd) + static_cast<double>(Ki[3 * i + 2])) * depth;
   o[3] = x2; o[4] = y2;
@@ -84,7 +64,7 @@ __global__ void __launch_bounds__(PNP_HYP_THREADS) k_pnp_hyp(const double* __res
   const int h = blockIdx.x * PNP_HYP_THREADS + threadIdx.x;
   const int plane = blockIdx.y, b = plane % B;
   if (h >= hyp) return;             // no barrier below: every thread works on its own slice of sMV
-  const double* mp = m + static_cast<long>(plane) * num * PNP_PT;
+  const double* mp = m + static_cast<long>(plane) * num * PnpModel::PT;
   double Kd[9], Kinv[9];
   for (int i = 0; i < 9; ++i) Kd[i] = K[b * 9 + i];
   pnp::inverse3(Kd, Kinv);
@@ -95,7 +75,7 @@ __global__ void __launch_bounds__(PNP_HYP_THREADS) k_pnp_hyp(const double* __res
   for (int i = 0; i < 6; ++i) {
     int s = sets[(static_cast<long>(b) * hyp + h) * 6 + i];
     s = s < 0 ? 0 : (s > num - 1 ? num - 1 : s);
-    const double* q = mp + static_cast<long>(s) * PNP_PT;
+    const double* q = mp + static_cast<long>(s) * PnpModel::PT;
     const double Xh[4] = {q[0], q[1], q[2], 1.0};
     const double u = (Kinv[0] * q[3] + Kinv[1] * q[4]) + Kinv[2], v = (Kinv[3] * q[3] + Kinv[4] * q[4]) + Kinv[5];
     const double uv2 = u * u + v * v;
@@ -113,44 +93,19 @@ __global__ void __launch_bounds__(PNP_HYP_THREADS) k_pnp_hyp(const double* __res
   double* M = sMV + threadIdx.x;
   double* V = sMV + 144 * PNP_HYP_THREADS + threadIdx.x;
   pnp::dlt_normal(S, Su, Sv, Sq, M, PNP_HYP_THREADS);
-  const int col = pnp::jacobi12(M, V, PNP_HYP_THREADS);
+  const int col = jacobi_sym<12>(M, V, PNP_HYP_THREADS, pnp::JACOBI12_SWEEPS);
   double P[12], R[9], T[3];
   for (int i = 0; i < 12; ++i) P[i] = V[(12 * i + col) * PNP_HYP_THREADS];
   pnp::pose_from_dlt(P, R, T);
-  double* o = Ph + (static_cast<long>(plane) * hyp + h) * PNP_POSE;
+  double* o = Ph + (static_cast<long>(plane) * hyp + h) * PnpModel::HP;
   for (int i = 0; i < 9; ++i) o[i] = R[i];
   for (int i = 0; i < 3; ++i) o[9 + i] = T[i];
 }
 
-__global__ void __launch_bounds__(PNP_MATCH_TILE) k_pnp_score(const double* __restrict__ m, const double* __restrict__ Ph,
-                                                               const float* __restrict__ K, int* __restrict__ counts, int B, int num,
-                                                               int hyp, double thr2) {
-  __shared__ double sP[PNP_HYP_TILE * PNP_POSE];
-  __shared__ int sC[PNP_HYP_TILE];
-  const int j = blockIdx.x * PNP_MATCH_TILE + threadIdx.x;
-  const int plane = blockIdx.y;
-  const pnp::Cam cam = load_cam(K, plane % B);
-  const bool live = j < num;
-  double pt[PNP_PT] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  if (live) {
-    const double* p = m + (static_cast<long>(plane) * num + j) * PNP_PT;
-    for (int i = 0; i < PNP_PT; ++i) pt[i] = p[i];
-  }
-  for (int h0 = 0; h0 < hyp; h0 += PNP_HYP_TILE) {
-    const int nh = hyp - h0 < PNP_HYP_TILE ? hyp - h0 : PNP_HYP_TILE;
-    for (int i = threadIdx.x; i < nh * PNP_POSE; i += PNP_MATCH_TILE) sP[i] = Ph[(static_cast<long>(plane) * hyp + h0) * PNP_POSE + i];
-    if (threadIdx.x < PNP_HYP_TILE) sC[threadIdx.x] = 0;
-    __syncthreads();
-    for (int hh = 0; hh < nh; ++hh) {
-      const bool in = live && pnp::inlier(cam, sP + hh * PNP_POSE, sP + hh * PNP_POSE + 9, pt, thr2);
-      const unsigned long long bal = __ballot(in);
-      if ((threadIdx.x & 63) == 0 && bal != 0ull) atomicAdd(&sC[hh], __popcll(bal));
-    }
-    __syncthreads();
-    if (static_cast<int>(threadIdx.x) < nh && sC[threadIdx.x] != 0)
-      atomicAdd(&counts[static_cast<long>(plane) * hyp + h0 + threadIdx.x], sC[threadIdx.x]);
-    __syncthreads();
-  }
+__global__ void __launch_bounds__(ransac::MATCH_TILE) k_pnp_score(const double* __restrict__ m, const double* __restrict__ Ph,
+                                                                   const float* __restrict__ K, int* __restrict__ counts, int B, int num,
+                                                                   int hyp, double thr2) {
+  ransac::score_body<PnpModel>(load_cam(K, blockIdx.y % B), m, Ph, counts, num, hyp, thr2);
 }
 
 // v[0..LM_SUMS) summed over the block in an order fixed by thread index: lanes of a wave by shuffles (a tree over the lane
@@ -172,21 +127,9 @@ __device__ void block_sum_lm(double* v, double* red) {
   }
 }
 
-__device__ int block_sum_int(int v, int* ired) {
-  ired[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = PNP_THREADS / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) ired[threadIdx.x] += ired[threadIdx.x + s];
-    __syncthreads();
-  }
-  const int r = ired[0];
-  __syncthreads();
-  return r;
-}
-
 // the state of one refinement, kept by thread 0 in LDS: the pose, the candidate every thread evaluates, the sums at the pose
 struct LmState {
-  double R[9], T[3];
+  double pose[12];          // R row-major, T
   double cand[12];
   double sums[pnp::LM_SUMS];
   double lam;
@@ -201,23 +144,22 @@ __device__ void lm_sums_at_candidate(const pnp::Cam& cam, const LmState& st, con
   for (int i = 0; i < 3; ++i) T[i] = st.cand[9 + i];
 #pragma unroll
   for (int i = 0; i < pnp::LM_SUMS; ++i) acc[i] = 0.0;
-  for (int j = threadIdx.x; j < num; j += PNP_THREADS) {
-    double pt[PNP_PT];
-    for (int i = 0; i < PNP_PT; ++i) pt[i] = mp[static_cast<long>(j) * PNP_PT + i];
+  for (int j = threadIdx.x; j < num; j += THREADS) {
+    double pt[PnpModel::PT];
+    for (int i = 0; i < PnpModel::PT; ++i) pt[i] = mp[static_cast<long>(j) * PnpModel::PT + i];
     pnp::lm_accumulate(cam, R, T, pt, static_cast<double>(w[j]), acc);
   }
   block_sum_lm(acc, red);
 }
 
-// _pnp_refine over the matches of weight 1 from the pose in st.R / st.T, iters iterations; st.R / st.T receive the result.
+// _pnp_refine over the matches of weight 1 from the pose in st.pose, iters iterations; st.pose receives the result.
 // Each iteration reduces the LM_SUMS sums at the candidate pose once: its cost decides the accept test, its H and g serve the
 // next iteration if it is accepted.
 __device__ void refine(const pnp::Cam& cam, LmState& st, const double* __restrict__ mp, const int* __restrict__ w, int num, int iters,
                        double* red) {
   double acc[pnp::LM_SUMS];
   if (threadIdx.x == 0) {
-    for (int i = 0; i < 9; ++i) st.cand[i] = st.R[i];
-    for (int i = 0; i < 3; ++i) st.cand[9 + i] = st.T[i];
+    for (int i = 0; i < 12; ++i) st.cand[i] = st.pose[i];
     st.lam = 1e-3;
   }
   __syncthreads();
@@ -230,15 +172,14 @@ __device__ void refine(const pnp::Cam& cam, LmState& st, const double* __restric
     if (threadIdx.x == 0) {
       double step[6];
       pnp::lm_solve(st.sums, st.lam, st.A, step);
-      pnp::apply_step(step, st.R, st.T, st.cand, st.cand + 9);
+      pnp::apply_step(step, st.pose, st.pose + 9, st.cand, st.cand + 9);
     }
     __syncthreads();          // the candidate is published; red is free again (thread 0 read it before this barrier)
     lm_sums_at_candidate(cam, st, mp, w, num, acc, red);
     if (threadIdx.x == 0) {
       const bool ok = acc[27] < st.sums[27];          // cn < cost: false for NaN
       if (ok) {
-        for (int i = 0; i < 9; ++i) st.R[i] = st.cand[i];
-        for (int i = 0; i < 3; ++i) st.T[i] = st.cand[9 + i];
+        for (int i = 0; i < 12; ++i) st.pose[i] = st.cand[i];
 #pragma unroll
         for (int i = 0; i < pnp::LM_SUMS; ++i) st.sums[i] = acc[i];
       }
@@ -250,83 +191,33 @@ __device__ void refine(const pnp::Cam& cam, LmState& st, const double* __restric
   __syncthreads();
 }
 
-__global__ void __launch_bounds__(PNP_THREADS) k_pnp_consensus(const double* __restrict__ m, const double* __restrict__ Ph,
-                                                                const int* __restrict__ counts, const float* __restrict__ K,
-                                                                int* __restrict__ w1, int* __restrict__ w2, double* __restrict__ P64,
-                                                                float* __restrict__ P32, int* __restrict__ info, int B, int num, int hyp,
-                                                                int iters, double thr2) {
+__global__ void __launch_bounds__(THREADS) k_pnp_consensus(const double* __restrict__ m, const double* __restrict__ Ph,
+                                                            const int* __restrict__ counts, const float* __restrict__ K,
+                                                            int* __restrict__ w1, int* __restrict__ w2, double* __restrict__ P64,
+                                                            float* __restrict__ P32, int* __restrict__ info, int B, int num, int hyp,
+                                                            int iters, double thr2) {
   __shared__ LmState st;
   __shared__ double red[pnp::LM_SUMS * PNP_WAVES];
-  __shared__ int ired[PNP_THREADS], ibest[PNP_THREADS];
   const int plane = blockIdx.x;
   const pnp::Cam cam = load_cam(K, plane % B);
-  const double* mp = m + static_cast<long>(plane) * num * PNP_PT;
-  const int* cp = counts + static_cast<long>(plane) * hyp;
-  int* w1p = w1 + static_cast<long>(plane) * num;
-  int* w2p = w2 + static_cast<long>(plane) * num;
-  // the hypothesis with the most inliers, ties to the lowest index
-  int bc = -1, bh = 0;
-  for (int h = threadIdx.x; h < hyp; h += PNP_THREADS)
-    if (cp[h] > bc) { bc = cp[h]; bh = h; }
-  ired[threadIdx.x] = bc;
-  ibest[threadIdx.x] = bh;
-  __syncthreads();
-  for (int s = PNP_THREADS / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) {
-      const int oc = ired[threadIdx.x + s], oh = ibest[threadIdx.x + s];
-      if (oc > ired[threadIdx.x] || (oc == ired[threadIdx.x] && oh < ibest[threadIdx.x])) { ired[threadIdx.x] = oc; ibest[threadIdx.x] = oh; }
-    }
-    __syncthreads();
-  }
-  const int best = ibest[0], best_count = ired[0];
-  __syncthreads();
-  if (threadIdx.x < 9) st.R[threadIdx.x] = Ph[(static_cast<long>(plane) * hyp + best) * PNP_POSE + threadIdx.x];
-  else if (threadIdx.x < 12) st.T[threadIdx.x - 9] = Ph[(static_cast<long>(plane) * hyp + best) * PNP_POSE + threadIdx.x];
-  __syncthreads();
-  double R[9], T[3], pt[PNP_PT];
-  for (int i = 0; i < 9; ++i) R[i] = st.R[i];
-  for (int i = 0; i < 3; ++i) T[i] = st.T[i];
-  int c = 0;
-  for (int j = threadIdx.x; j < num; j += PNP_THREADS) {
-    for (int i = 0; i < PNP_PT; ++i) pt[i] = mp[static_cast<long>(j) * PNP_PT + i];
-    const int in = pnp::inlier(cam, R, T, pt, thr2) ? 1 : 0;
-    w1p[j] = in;
-    c += in;
-  }
-  int n1 = block_sum_int(c, ired);
-  if (n1 < 6) {                           // no consensus: all matches
-    for (int j = threadIdx.x; j < num; j += PNP_THREADS) w1p[j] = 1;
-    n1 = num;
-  }
-  refine(cam, st, mp, w1p, num, iters, red);      // every thread reads back only the weights it wrote
-  for (int i = 0; i < 9; ++i) R[i] = st.R[i];
-  for (int i = 0; i < 3; ++i) T[i] = st.T[i];
-  c = 0;
-  for (int j = threadIdx.x; j < num; j += PNP_THREADS) {
-    for (int i = 0; i < PNP_PT; ++i) pt[i] = mp[static_cast<long>(j) * PNP_PT + i];
-    const int in = pnp::inlier(cam, R, T, pt, thr2) ? 1 : 0;
-    w2p[j] = in;
-    c += in;
-  }
-  int n2 = block_sum_int(c, ired);
-  if (n2 < 6) {                           // keep the previous set
-    for (int j = threadIdx.x; j < num; j += PNP_THREADS) w2p[j] = w1p[j];
-    n2 = n1;
-  }
-  const int more = iters / 2 > 1 ? iters / 2 : 1;
-  refine(cam, st, mp, w2p, num, more, red);
-  if (threadIdx.x == 0) {
-    double v[3];
-    for (int i = 0; i < 9; ++i) R[i] = st.R[i];
-    pnp::so3_log(R, v);
-    for (int i = 0; i < 3; ++i) {
-      P64[plane * 6 + i] = st.T[i];
-      P32[plane * 6 + i] = static_cast<float>(st.T[i]);
-      P64[plane * 6 + 3 + i] = v[i];
-      P32[plane * 6 + 3 + i] = static_cast<float>(v[i]);
-    }
-    info[plane * 4] = best; info[plane * 4 + 1] = best_count; info[plane * 4 + 2] = n1; info[plane * 4 + 3] = n2;
-  }
+  const double* mp = m + static_cast<long>(plane) * num * PnpModel::PT;
+  // iters iterations over the first set, max(iters / 2, 1) over the second; then (T, log R)
+  ransac::consensus_body<PnpModel>(
+      cam, m, Ph, counts, w1, w2, info, num, hyp, thr2, st.pose,
+      [&](const int* w, int fit) { refine(cam, st, mp, w, num, fit == 0 ? iters : (iters / 2 > 1 ? iters / 2 : 1), red); },
+      [&]() {
+        if (threadIdx.x == 0) {
+          double R[9], v[3];
+          for (int i = 0; i < 9; ++i) R[i] = st.pose[i];
+          pnp::so3_log(R, v);
+          for (int i = 0; i < 3; ++i) {
+            P64[plane * 6 + i] = st.pose[9 + i];
+            P32[plane * 6 + i] = static_cast<float>(st.pose[9 + i]);
+            P64[plane * 6 + 3 + i] = v[i];
+            P32[plane * 6 + 3 + i] = static_cast<float>(v[i]);
+          }
+        }
+      });
 }
 
 // ---------------------------------------------------------------------------------------------- loss
@@ -367,31 +258,27 @@ using namespace dfe;
 
 extern "C" long dfe_pnp_ws_bytes(int B, int num, int hyp) {
   if (B <= 0 || num <= 0 || hyp <= 0) return 0;
-  return pnp_ws_bytes(B, num, hyp);
+  return ransac::ws_offsets(PnpModel::PT, PnpModel::HP, B, num, hyp).bytes;
 }
 
 extern "C" int dfe_pnp_ransac(const float* flow_bwd, const float* flow_fwd, const float* disp_t, const int* idx, const long long* pick,
                               const int* sets, const float* K, const float* K_inv, double* P64, float* P32, int* info, void* ws,
                               int B, int H, int W, int k, int num, int hyp, int iters, double thresh, void* stream) {
-  if (!flow_bwd || !flow_fwd || !disp_t || !idx || !pick || !sets || !K || !K_inv || !P64 || !P32 || !info || !ws) return DFE_ERR_NULL;
-  if (B <= 0 || B > 16384 || H < 1 || W < 1 || k <= 0 || num < 6 || hyp < 1 || iters < 1) return DFE_ERR_DIMS;
-  if (static_cast<long>(H) * W >= (1L << 28) || k > H * W) return DFE_ERR_DIMS;
-  if (num > PNP_MAX_NUM || hyp > PNP_MAX_HYP) return DFE_ERR_UNSUPPORTED;
-  if (!aligned16(ws) || !aligned8(P64)) return DFE_ERR_DIMS;
+  const bool have_all = flow_bwd && flow_fwd && disp_t && idx && pick && sets && K && K_inv && P64 && P32 && info && ws;
+  if (have_all && iters < 1) return DFE_ERR_DIMS;
+  const int rc = ransac::check_args(have_all, B, H, W, k, num, hyp, PnpModel::MIN, ws, P64);
+  if (rc != DFE_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const PnpWs w = pnp_ws(ws, B, num, hyp);
+  const ransac::Ws w = ransac::ws_sections(ws, ransac::ws_offsets(PnpModel::PT, PnpModel::HP, B, num, hyp));
   const double thr2 = thresh * thresh;
-  // the counts start at zero; everything else in ws is written before it is read
-  if (hipMemsetAsync(w.counts, 0, static_cast<size_t>(4L * 2 * B * hyp), st) != hipSuccess) return DFE_ERR_LAUNCH;
-  const dim3 gm(static_cast<unsigned>((num + PNP_THREADS - 1) / PNP_THREADS), 2 * B);
-  k_pnp_points<<<gm, PNP_THREADS, 0, st>>>(flow_bwd, flow_fwd, disp_t, idx, pick, K_inv, w.m, B, H, W, k, num);
-  DFE_LAUNCH_CHECK();
-  k_pnp_hyp<<<dim3(static_cast<unsigned>((hyp + PNP_HYP_THREADS - 1) / PNP_HYP_THREADS), 2 * B), PNP_HYP_THREADS, 0, st>>>(w.m, sets, K, w.Ph, B, num, hyp);
-  DFE_LAUNCH_CHECK();
-  k_pnp_score<<<dim3(static_cast<unsigned>((num + PNP_MATCH_TILE - 1) / PNP_MATCH_TILE), 2 * B), PNP_MATCH_TILE, 0, st>>>(w.m, w.Ph, K, w.counts, B, num, hyp, thr2);
-  DFE_LAUNCH_CHECK();
-  k_pnp_consensus<<<2 * B, PNP_THREADS, 0, st>>>(w.m, w.Ph, w.counts, K, w.w1, w.w2, P64, P32, info, B, num, hyp, iters, thr2);
-  return launch_status();
+  return ransac::launch_all(
+      w.counts, B, num, hyp, PNP_HYP_THREADS, st,
+      [&](dim3 g) { k_pnp_points<<<g, THREADS, 0, st>>>(flow_bwd, flow_fwd, disp_t, idx, pick, K_inv, w.m, B, H, W, k, num); },
+      [&](dim3 g) { k_pnp_hyp<<<g, PNP_HYP_THREADS, 0, st>>>(w.m, sets, K, w.hyps, B, num, hyp); },
+      [&](dim3 g) { k_pnp_score<<<g, ransac::MATCH_TILE, 0, st>>>(w.m, w.hyps, K, w.counts, B, num, hyp, thr2); },
+      [&](dim3 g) {
+        k_pnp_consensus<<<g, THREADS, 0, st>>>(w.m, w.hyps, w.counts, K, w.w1, w.w2, P64, P32, info, B, num, hyp, iters, thr2);
+      });
 }
 
 extern "C" int dfe_pnp_loss_fwd(const float* pose, const float* P32, float* loss, int B, float beta, void* stream) {

@@ -10,13 +10,14 @@
 //                          fixed-point accumulators (points repeat); T34's gradient from per-block partial sums added in block order
 // Every sum has an order fixed by thread and block index; the only atomics are integer ones: same bits run after run.
 #include "dfe_internal.h"
+#include "dfe_ransac.h"
 #include "dfe_scatter.h"
 #include "dfe_triangulate.h"
 
 namespace dfe {
 namespace {
 
-constexpr int TRI_THREADS = 256;
+constexpr int TRI_THREADS = ransac::THREADS;     // the shared block sum is over a block of this size
 constexpr int STATS_DOUBLES = 4;     // per (b, d, view): scale, a, a / (scale + eps), loss
 
 struct TriIn {
@@ -41,17 +42,12 @@ __device__ __forceinline__ PointCtx load_point(const TriIn& a, int d, int b, int
   PointCtx c;
   for (int i = 0; i < 9; ++i) { c.K[i] = a.K[b * 9 + i]; c.Kinv[i] = a.Kinv[b * 9 + i]; }
   for (int i = 0; i < 12; ++i) c.T[i] = a.T34[(b * 2 + d) * 12 + i];
-  long long p = a.pick[j];
-  p = p < 0 ? 0 : (p > a.k - 1 ? a.k - 1 : p);
-  int pix = a.idx[static_cast<long>(d * a.B + b) * a.k + p];
-  const int HW = a.H * a.W;
-  pix = pix < 0 ? 0 : (pix > HW - 1 ? HW - 1 : pix);
-  c.pix = pix;
-  c.y = pix / a.W;
-  c.x = pix - (pix / a.W) * a.W;
-  const float* fl = a.flow[d] + static_cast<long>(b) * 2 * HW;
-  c.u = fl[pix];
-  c.v = fl[HW + pix];
+  const ransac::Match mt = ransac::load_match(a.flow[d], a.idx, a.pick, d * a.B + b, b, j, a.k, a.H, a.W);
+  c.pix = mt.pix;
+  c.y = mt.y;
+  c.x = mt.x;
+  c.u = mt.u;
+  c.v = mt.v;
   return c;
 }
 
@@ -121,19 +117,6 @@ __device__ unsigned long long select_rank(const unsigned long long* keys, int n,
   return prefix;
 }
 
-// block sum in a fixed order: every thread's strided partial, then a tree over the threads
-__device__ double block_sum_fixed(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = TRI_THREADS / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ void __launch_bounds__(TRI_THREADS) k_tri_stats(const double* __restrict__ rec, double* __restrict__ stats, int B, int num) {
   extern __shared__ unsigned long long tri_keys[];     // num keys
   __shared__ int hist[256];
@@ -156,8 +139,8 @@ __global__ void __launch_bounds__(TRI_THREADS) k_tri_stats(const double* __restr
     A += (is * is) / (z * z + tri::EPS);
     C += is / (z + tri::EPS);
   }
-  A = block_sum_fixed(A, red);
-  C = block_sum_fixed(C, red);
+  ransac::block_sum<1>(&A, red);     // a fixed order: every thread's strided partial, then a tree over the threads
+  ransac::block_sum<1>(&C, red);
   const double aa = C / (A + tri::EPS);
   double L = 0.0;
   for (int i = threadIdx.x; i < num; i += TRI_THREADS) {
@@ -165,7 +148,8 @@ __global__ void __launch_bounds__(TRI_THREADS) k_tri_stats(const double* __restr
     const double e = 1.0 - aa * is / (z + tri::EPS);
     L += e * e;
   }
-  L = block_sum_fixed(L, red) / num;
+  ransac::block_sum<1>(&L, red);
+  L = L / num;
   if (threadIdx.x == 0) {
     double* s = stats + static_cast<long>(blockIdx.x) * STATS_DOUBLES;
     s[0] = scale; s[1] = aa; s[2] = aa / (scale + tri::EPS); s[3] = L;
@@ -253,7 +237,8 @@ __global__ void __launch_bounds__(TRI_THREADS) k_tri_bwd_points(TriIn a, const d
   if (threadIdx.x < 2 && bmax[threadIdx.x] != 0u) atomicMax(w.header + threadIdx.x, bmax[threadIdx.x]);
   double* part = w.part + (static_cast<long>(plane) * gridDim.x + blockIdx.x) * 12;
   for (int i = 0; i < 12; ++i) {
-    const double s = block_sum_fixed(gT[i], red);
+    double s = gT[i];
+    ransac::block_sum<1>(&s, red);
     if (threadIdx.x == 0) part[i] = s;
   }
 }

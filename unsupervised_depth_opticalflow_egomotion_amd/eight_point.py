@@ -20,22 +20,14 @@ Fidelity:
   adjugate over the determinant instead (``inverse_transposed``)."""
 import torch
 
-from ._lib import check, f32c, get_lib, ptr, stream_ptr
-from .triangulate import ptr_any
-
-MAX_NUM = 16384
-MAX_HYP = 4096
+from . import _ransac
+from ._lib import check, f32c, get_lib, ptr, ptr_any, stream_ptr
 
 
 def workspace_sections(B, num, hyp):
     """Byte offsets of the sections of dfe_fundamental_ransac's workspace, as include/dfe_hip.h states them: dict(matches, Fh,
     counts, w1, w2, bytes)."""
-    r16 = lambda v: (v + 15) // 16 * 16   # noqa: E731
-    fh = 64 * B * num
-    counts = fh + r16(144 * B * hyp)
-    w1 = counts + r16(8 * B * hyp)
-    w2 = w1 + r16(8 * B * num)
-    return dict(matches=0, Fh=fh, counts=counts, w1=w1, w2=w2, bytes=w2 + r16(8 * B * num))
+    return _ransac.workspace_sections(B, num, hyp, 4, 9, "matches", "Fh")
 
 
 def fundamental_ransac(flow_bwd0, flow_fwd0, idx, pick, sets, thresh=0.1, return_ws=False):
@@ -44,20 +36,8 @@ def fundamental_ransac(flow_bwd0, flow_fwd0, idx, pick, sets, thresh=0.1, return
     ``return_ws``: also the workspace (uint8; ``workspace_sections`` gives the offsets of the counts and the weights)."""
     lib = get_lib()
     flow_bwd0, flow_fwd0 = f32c(flow_bwd0.detach()), f32c(flow_fwd0.detach())
-    if flow_bwd0.dim() != 4 or flow_bwd0.shape[1] != 2 or flow_fwd0.shape != flow_bwd0.shape:
-        raise ValueError("fundamental_ransac: two flows [B,2,H,W] of one scale expected")
-    B, _, H, W = flow_bwd0.shape
-    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != 2 * B or pick.dtype != torch.int64 or pick.dim() != 1:
-        raise ValueError("fundamental_ransac: idx int32 [2B,k] and pick int64 [num] expected")
-    if sets.dtype != torch.int32 or sets.dim() != 3 or sets.shape[0] != B or sets.shape[2] != 8:
-        raise ValueError("fundamental_ransac: sets int32 [B,hyp,8] expected")
-    k, num, hyp = idx.shape[1], pick.shape[0], sets.shape[1]
-    if num < 8:
-        raise ValueError("the eight-point algorithm needs at least 8 matches (got %d)" % num)
-    if num > MAX_NUM or hyp > MAX_HYP or hyp < 1:
-        raise ValueError("fundamental_ransac: at most %d matches and 1 to %d hypotheses (got %d, %d)" % (MAX_NUM, MAX_HYP, num, hyp))
-    if k > H * W or k < 1:
-        raise ValueError("fundamental_ransac: 1 <= k <= H*W expected")
+    B, H, W, k, num, hyp = _ransac.check_draw(flow_bwd0, flow_fwd0, idx, pick, sets, 8, "fundamental_ransac",
+                                              "the eight-point algorithm")
     idx, pick, sets = idx.contiguous(), pick.contiguous(), sets.contiguous()
     dev = flow_bwd0.device
     F64 = torch.empty(2 * B, 3, 3, device=dev, dtype=torch.float64)

@@ -155,22 +155,9 @@ class GeometrySolvers:
 
     # ------------------------------------------------------------------ eight-point (model_geometry.py:532-566)
     @staticmethod
-    def _hartley(xy):
-        """Similarity that moves the centroid of [b,2,n] points to the origin and their mean distance to sqrt(2)."""
-        c = xy.mean(2, keepdim=True)
-        d = torch.sqrt(((xy - c) ** 2).sum(1)).mean(1)
-        s = (2.0 ** 0.5) / (d + 1e-12)
-        T = torch.zeros(xy.shape[0], 3, 3, device=xy.device, dtype=xy.dtype)
-        T[:, 0, 0] = s
-        T[:, 1, 1] = s
-        T[:, 0, 2] = -s * c[:, 0, 0]
-        T[:, 1, 2] = -s * c[:, 1, 0]
-        T[:, 2, 2] = 1.0
-        return T
-
-    @staticmethod
     def _weighted_hartley(xy, w):
-        """_hartley over the matches with weight 1 (w [b,n] in {0,1}; at least one per sample)."""
+        """Similarity that moves the centroid of the [b,2,n] points of weight 1 to the origin and their mean distance to sqrt(2)
+        (w [b,n] in {0,1}; at least one per sample)."""
         cnt = w.sum(1).clamp_min(1.0)
         c = (xy * w.unsqueeze(1)).sum(2, keepdim=True) / cnt.view(-1, 1, 1)
         d = (torch.sqrt(((xy - c) ** 2).sum(1)) * w).sum(1) / cnt

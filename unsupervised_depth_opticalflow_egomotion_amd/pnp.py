@@ -21,22 +21,14 @@ Fidelity:
   composition (``GeometrySolvers.pnp``) on the same sets, plus the analytic pose of synthetic two-view problems."""
 import torch
 
-from ._lib import check, f32c, get_lib, ptr, stream_ptr
-from .triangulate import ptr_any
-
-MAX_NUM = 16384
-MAX_HYP = 4096
+from . import _ransac
+from ._lib import check, f32c, get_lib, ptr, ptr_any, stream_ptr
 
 
 def workspace_sections(B, num, hyp):
     """Byte offsets of the sections of dfe_pnp_ransac's workspace, as include/dfe_hip.h states them: dict(points, Ph, counts, w1,
     w2, bytes)."""
-    r16 = lambda v: (v + 15) // 16 * 16   # noqa: E731
-    ph = 80 * B * num
-    counts = ph + 192 * B * hyp
-    w1 = counts + r16(8 * B * hyp)
-    w2 = w1 + r16(8 * B * num)
-    return dict(points=0, Ph=ph, counts=counts, w1=w1, w2=w2, bytes=w2 + r16(8 * B * num))
+    return _ransac.workspace_sections(B, num, hyp, 5, 12, "points", "Ph")
 
 
 def pnp_ransac(flow_bwd0, flow_fwd0, disp_t0, idx, pick, sets, K, K_inv, iters=20, thresh=1.0, return_ws=False):
@@ -46,25 +38,12 @@ def pnp_ransac(flow_bwd0, flow_fwd0, disp_t0, idx, pick, sets, K, K_inv, iters=2
     offsets of the counts and the weights)."""
     lib = get_lib()
     flow_bwd0, flow_fwd0, disp_t0 = f32c(flow_bwd0.detach()), f32c(flow_fwd0.detach()), f32c(disp_t0.detach())
-    if flow_bwd0.dim() != 4 or flow_bwd0.shape[1] != 2 or flow_fwd0.shape != flow_bwd0.shape:
-        raise ValueError("pnp_ransac: two flows [B,2,H,W] of one scale expected")
-    B, _, H, W = flow_bwd0.shape
+    B, H, W, k, num, hyp = _ransac.check_draw(flow_bwd0, flow_fwd0, idx, pick, sets, 6, "pnp_ransac", "the six-point DLT")
     if disp_t0.numel() != B * H * W:
         raise ValueError("pnp_ransac: disp_t0 [B,1,H,W] of the flows' scale expected")
-    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != 2 * B or pick.dtype != torch.int64 or pick.dim() != 1:
-        raise ValueError("pnp_ransac: idx int32 [2B,k] and pick int64 [num] expected")
-    if sets.dtype != torch.int32 or sets.dim() != 3 or sets.shape[0] != B or sets.shape[2] != 6:
-        raise ValueError("pnp_ransac: sets int32 [B,hyp,6] expected")
     K, K_inv = f32c(K.detach()), f32c(K_inv.detach())
     if tuple(K.shape) != (B, 3, 3) or tuple(K_inv.shape) != (B, 3, 3):
         raise ValueError("pnp_ransac: K and K_inv [B,3,3] expected")
-    k, num, hyp = idx.shape[1], pick.shape[0], sets.shape[1]
-    if num < 6:
-        raise ValueError("the six-point DLT needs at least 6 matches (got %d)" % num)
-    if num > MAX_NUM or hyp > MAX_HYP or hyp < 1:
-        raise ValueError("pnp_ransac: at most %d matches and 1 to %d hypotheses (got %d, %d)" % (MAX_NUM, MAX_HYP, num, hyp))
-    if k > H * W or k < 1:
-        raise ValueError("pnp_ransac: 1 <= k <= H*W expected")
     if int(iters) < 1:
         raise ValueError("pnp_ransac: at least one refinement iteration expected")
     idx, pick, sets = idx.contiguous(), pick.contiguous(), sets.contiguous()

@@ -7,7 +7,7 @@ from the scale-0 flows, the three scale-0 disparities and the pose matrices, giv
 the term can be captured in a hipGraph; every output is bitwise reproducible."""
 import torch
 
-from ._lib import check, f32c, get_lib, ptr, stream_ptr
+from ._lib import check, f32c, get_lib, ptr, ptr_any, stream_ptr
 
 MAX_NUM = 16384        # dfe_triangulate_stats stages ``num`` 8-byte keys in LDS
 
@@ -77,16 +77,6 @@ class TriangulateFn(torch.autograd.Function):
         g_fb, g_ff = grads[:2 * n].view(B, 2, H, W), grads[2 * n:4 * n].view(B, 2, H, W)
         g_t, g_l, g_r = (grads[(4 + i) * n:(5 + i) * n].view(B, 1, H, W) for i in range(3))
         return g_fb, g_ff, g_t, g_l, g_r, gT, None, None, None, None, None
-
-
-def ptr_any(t):
-    """Device pointer of a contiguous HIP tensor of any of the dtypes the entry points take (fp32, fp64, int32, int64, uint8)."""
-    import ctypes
-    if t.dtype == torch.float64:
-        if not (t.is_cuda and t.is_contiguous()):
-            raise ValueError("a contiguous fp64 HIP tensor expected")
-        return ctypes.c_void_p(t.data_ptr())
-    return ptr(t)
 
 
 def triangulate_loss(flow_bwd, flow_fwd, disp_t, disp_l, disp_r, T34, K, K_inv, idx, pick, align_corners):
