@@ -63,18 +63,21 @@ def solvers(sets=None):
 
 
 def build(seed, B, H, W, k, num, hyp, noisy):
-    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them."""
+    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them.  ``disp_t``: the depth map the flows
+    were rendered from (what the model-level tests hand the draw as the disparity)."""
     rng = np.random.default_rng(seed)
     K = np.zeros((B, 3, 3))
     flows = np.zeros((2, B, 2, H, W))
     F_true = np.zeros((2, B, 3, 3))
     pose = np.zeros((B, 2, 3, 4))
+    depths = np.zeros((B, 1, H, W))
     ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
     for b in range(B):
         f = 0.9 * W * rng.uniform(0.95, 1.05)
         K[b] = [[f, 0, (W - 1) / 2.0 + rng.uniform(-0.5, 0.5)], [0, f * rng.uniform(0.97, 1.03), (H - 1) / 2.0 + rng.uniform(-0.5, 0.5)],
                 [0, 0, 1]]
         depth = _smooth(rng, H, W, 2.0, 20.0)
+        depths[b, 0] = depth
         Ki = np.linalg.inv(K[b])
         X = depth[None] * np.einsum("ij,jhw->ihw", Ki, np.stack([xs, ys, np.ones_like(xs)]))
         for d in range(2):
@@ -100,8 +103,8 @@ def build(seed, B, H, W, k, num, hyp, noisy):
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.float32)))   # noqa: E731
     K32 = f32(K)
     return dict(B=B, H=H, W=W, k=k, num=num, hyp=hyp, noisy=noisy, seed=seed, K=K32, K_inv=torch.inverse(K32.double()).float(),
-                flow_bwd=f32(flows[0]), flow_fwd=f32(flows[1]), idx=torch.from_numpy(idx), pick=torch.from_numpy(pick),
-                sets=torch.from_numpy(sets), F_true=torch.from_numpy(F_true).reshape(2 * B, 3, 3), T34=torch.from_numpy(pose))
+                flow_bwd=f32(flows[0]), flow_fwd=f32(flows[1]), disp_t=f32(depths), idx=torch.from_numpy(idx),
+                pick=torch.from_numpy(pick), sets=torch.from_numpy(sets), F_true=torch.from_numpy(F_true).reshape(2 * B, 3, 3), T34=torch.from_numpy(pose))
 
 
 def matches_of(case, flow_bwd=None, flow_fwd=None):
@@ -149,6 +152,14 @@ def _composition(matches, sets, thresh):
     h = idx.shape[1]
     pts = torch.gather(m.unsqueeze(1).expand(p, h, 4, n), 3, idx.unsqueeze(2).expand(p, h, 4, 8))
     Fh = S._eight_point(pts.reshape(p * h, 4, 8)).reshape(p, h, 3, 3)
+    return _continue(m, Fh, thresh)
+
+
+def _continue(m, Fh, thresh):
+    """``_composition`` from its hypothesis table on: m [p,4,n] float64, Fh [p,h,3,3] float64 (any table, non-finite entries
+    included: their residuals count as infinite, as in the class)."""
+    from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers as S
+    p, _, n = m.shape
     err = S._epipolar_residual(Fh, m)
     err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
     inl = err <= thresh * thresh
@@ -261,3 +272,256 @@ def pose_vectors(case, seed=0):
     p = torch.randn(case["B"], 2, 6, generator=g) * 0.1
     p[:, :, :3] += torch.tensor([1.0, 0.5, 0.1])
     return p
+
+
+# ------------------------------------------------------------------------------------------------ the product's own draws
+# ``pick`` drawn with replacement (``Model_geometry.geometric_draw``) and ``sets`` by the class's own ``_minimal_sets``: a
+# hypothesis whose 8 matches are not 8 distinct pixels has a null space of two or more dimensions, and which of its vectors
+# ``eigh`` or the kernel's Jacobi returns is decided by rounding.  Such a slot is ILL-DEFINED: its F_h, its count, and -- where it
+# wins -- everything after it can only be checked from the kernel's own table on (``continued``).
+# key -> seed, found with find_drawn_seed(*key).  Asserted on every host (``_drawn_checked``): every plane has at least hyp / 4
+# well-defined and 4 ill-defined slots, no residual of a well-defined slot or of a refit lies within MARGIN of the threshold, every
+# consensus has 8 members and the null direction of BOTH refits' normal matrices is isolated (``continued`` needs the first's as
+# well).  Steering the search only, NOT asserted: the reference's winner is well-defined and leads every ill-defined slot's count by
+# LEAD.  Those counts rest on vectors that the host's LAPACK picks by rounding (one host polls 8 below the winner where another
+# polls 6), so the figure is printed by the CPU test and LEAD is twice the 8 first asked for; what is asserted in its place is the
+# composition without the ill-defined slots (``without_ill_defined``), which every host agrees on and the kernel must reproduce.
+# The last shape has hyp = 70: the hypothesis kernel's second and third block and the scoring kernel's second LDS round, for the
+# slots 0, 31, 32, 63, 64 and 69 of the isolation tests.
+LEAD = 16
+DRAWN_SEEDS = {
+    (2, 12, 20, 72, 64, 64, True): 11,
+    (3, 13, 19, 72, 70, 33, True): 162,
+    (2, 20, 24, 320, 300, 70, True): 0,
+}
+DRAWN_SHAPES = tuple(sorted(DRAWN_SEEDS))
+# one more case, found with find_drawn_seed(*key, ill_winner=True): on some plane the reference's winner is ill-defined.  Seeds 0
+# and 3 meet that too and were passed over after one run on the device: at 0 the kernel elects another ill-defined slot of plane 1
+# than ``eigh`` does, whose second refit keeps 9 matches of fewer than 8 distinct pixels (its normal matrix has no isolated null
+# direction: inconclusive); at 3 the kernel's own winners all have 8 distinct pixels (ill-defined by the isolation figures only)
+ILL_WINNER = ((2, 12, 20, 72, 64, 64, True), 5)
+# the slots the isolation tests overwrite: the first and last thread of the hypothesis kernel's first two blocks (32 threads
+# each), the first thread of the third and the last slot; 63 / 64 are also the end of the scoring kernel's first LDS round and
+# the start of its second
+CRAFTED_SLOTS = (0, 31, 32, 63, 64, 69)
+
+
+def build_drawn(seed, B, H, W, k, num, hyp, noisy):
+    """``build`` with ``pick`` drawn with replacement from a generator seeded with ``seed`` and ``sets`` the class's own
+    ``_minimal_sets(B, num, 8, "cpu")`` at ``ransac_iters = hyp`` (a function of the shape alone)."""
+    case = build(seed, B, H, W, k, num, hyp, noisy)
+    g = torch.Generator().manual_seed(seed)
+    case["pick"] = torch.randint(0, k, (num,), generator=g)
+    m = solvers()
+    m.ransac_iters = hyp
+    case["sets"] = m._minimal_sets(B, num, 8, "cpu").to(torch.int32)
+    return case
+
+
+def distinct_pixels(case, sets=None):
+    """bool [B,hyp]: the 8 matches of the set are 8 distinct pixels (``idx`` is duplicate-free, so of either direction's plane)."""
+    sets = case["sets"] if sets is None else sets
+    px = case["pick"][sets.long()].sort(2)[0]
+    return (px[:, :, 1:] != px[:, :, :-1]).all(2)
+
+
+def isolation(M):
+    """(gap, sep) of symmetric matrices [...,9,9] in float64: the second-smallest eigenvalue over the smallest, and their
+    distance over the largest -- the figures ``_checked`` asserts of the final normal matrix."""
+    ev = torch.linalg.eigvalsh(M)
+    return ev[..., 1] / ev[..., 0].clamp_min(1e-300), (ev[..., 1] - ev[..., 0]) / ev[..., 8]
+
+
+def well_defined(case, sets=None):
+    """bool [2B,hyp]: the slot's 8 matches are pairwise distinct pixels of its plane and the null direction of its float64
+    normal matrix is isolated (GAP, 1e-7).  Everything else is ill-defined."""
+    B = case["B"]
+    sets = case["sets"] if sets is None else sets
+    m = matches_of(case).double()
+    p, _, n = m.shape
+    idx = torch.cat([sets, sets], 0).long()
+    h = idx.shape[1]
+    pts = torch.gather(m.unsqueeze(1).expand(p, h, 4, n), 3, idx.unsqueeze(2).expand(p, h, 4, 8)).reshape(p * h, 4, 8)
+    gap, sep = isolation(normal_matrix(pts, torch.ones(p * h, 8, dtype=torch.float64)))
+    iso = ((gap >= GAP) & (sep >= 1e-7)).reshape(p, h)
+    return iso & torch.cat([distinct_pixels(case, sets)] * 2, 0)
+
+
+def rel_margin(e, keep=None, thresh=THRESH):
+    """The smallest relative distance of a finite residual to the threshold (inf if there is none); ``keep``: a mask."""
+    t = thresh * thresh
+    e = e if keep is None else e[keep]
+    e = e[torch.isfinite(e)]
+    return float(((e - t).abs() / t).min()) if e.numel() else float("inf")
+
+
+def continued(case, Fh):
+    """The float64 composition CONTINUED FROM A GIVEN HYPOTHESIS TABLE Fh [2B,hyp,3,3] (float64; the kernel's own, say): every
+    hypothesis recounted from that table, argmax (ties: the lowest index), w1, the fall-back, the refit, w2, its fall-back, the
+    second refit -- ``_continue``, the very code ``composition`` runs after its own table.  Added: ``margin`` (the smallest
+    relative distance to the threshold of any residual it used: every recount and both refits'), and ``gap1`` / ``sep1`` /
+    ``gap2`` / ``sep2`` [2B], the isolation figures of the two refits' normal matrices."""
+    B = case["B"]
+    m = matches_of(case).double()
+    halves = [_continue(m[d * B:(d + 1) * B], Fh[d * B:(d + 1) * B].double(), THRESH) for d in range(2)]
+    c = {k: torch.cat([h[k] for h in halves], 0) for k in halves[0]}
+    c["margin"] = min(rel_margin(c[k]) for k in ("err", "e1", "e2"))
+    c["gap1"], c["sep1"] = isolation(normal_matrix(m, c["w1"]))
+    c["gap2"], c["sep2"] = isolation(normal_matrix(m, c["w2"]))
+    return c
+
+
+def conclusive(c):
+    """``continued``'s own conditions: no residual within MARGIN of the threshold, both refits' null directions isolated."""
+    return bool(c["margin"] >= MARGIN and (c["gap1"] >= GAP).all() and (c["sep1"] >= 1e-7).all() and (c["gap2"] >= GAP).all()
+                and (c["sep2"] >= 1e-7).all())
+
+
+def drawn_conditions(case):
+    """dict of the figures a drawn case is chosen by -- the reference's alone -- and the composition's results."""
+    B, hyp = case["B"], case["hyp"]
+    m32 = matches_of(case)
+    c = composition(m32, case["sets"])
+    s = solvers(case["sets"])
+    F_api = torch.cat([s.compute_fundmental_mat(m32[:B].double()), s.compute_fundmental_mat(m32[B:].double())], 0)
+    wd = well_defined(case)
+    top = c["counts"].max(1)[0]
+    ill_top = torch.where(wd, torch.full_like(c["counts"], -10 ** 6), c["counts"]).max(1)[0]
+    margin = min(rel_margin(c["err"], wd.unsqueeze(2).expand_as(c["err"])), rel_margin(c["e1"]), rel_margin(c["e2"]))
+    gap, sep = (torch.minimum(a, b) for a, b in zip(isolation(normal_matrix(m32.double(), c["w1"])),
+                                                    isolation(normal_matrix(m32.double(), c["w2"]))))
+    return dict(comp=c, matches=m32, well=wd, api_equal=torch.equal(F_api, c["F"]), n_well=int(wd.sum(1).min()),
+                n_ill=int((~wd).sum(1).min()), margin=margin, winner_well=torch.gather(wd, 1, c["best"].view(-1, 1)).squeeze(1),
+                lead=int((top - ill_top).min()), consensus=int(min(c["n1raw"].min(), c["n2raw"].min())), gap=float(gap.min()),
+                sep=float(sep.min()))
+
+
+def drawn_ok(f, case, ill_winner=False):
+    ok = f["api_equal"] and 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4 and f["margin"] >= MARGIN and f["consensus"] >= 8
+    ok = ok and f["gap"] >= GAP and f["sep"] >= 1e-7
+    if ill_winner:
+        return ok and not bool(f["winner_well"].all())
+    return ok and bool(f["winner_well"].all()) and f["lead"] >= LEAD
+
+
+def find_drawn_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, ill_winner=False):
+    """The first seed from ``start`` whose drawn case meets the conditions (run once on the CPU; the result goes into DRAWN_SEEDS
+    or ILL_WINNER)."""
+    for seed in range(start, start + tries):
+        case = build_drawn(seed, B, H, W, k, num, hyp, noisy)
+        if drawn_ok(drawn_conditions(case), case, ill_winner):
+            return seed
+    raise RuntimeError("no seed found")
+
+
+def without_ill_defined(case, comp, well):
+    """The composition with the ill-defined slots refused a vote: ``continued`` from the reference's table with those slots made
+    non-finite.  Nothing in it rests on a vector that rounding picked, so it is the same on every host."""
+    Fh = comp["Fh"].clone()
+    Fh[~well] = float("nan")
+    return continued(case, Fh)
+
+
+def _drawn_checked(case, with_ref=True):
+    """Asserts what does not depend on the host: the figures of the well-defined slots and of the refits.  ``winner_well`` and
+    ``lead`` rest on the counts of ill-defined slots, which the host's LAPACK decides (one host polls 8 below the winner where
+    another polls 6): they steer ``find_drawn_seed`` and are kept in ``figures``, not asserted.  ``ref``: the composition without
+    the ill-defined slots -- what the kernel must arrive at whenever none of its own ill-defined slots out-polls the winner."""
+    f = drawn_conditions(case)
+    assert f["api_equal"], "the restated composition is not compute_fundmental_mat"
+    assert 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4, "a plane with %d well-defined, %d ill-defined slots" % (f["n_well"], f["n_ill"])
+    assert f["margin"] >= MARGIN, "a residual within a relative %g of the threshold (%g)" % (MARGIN, f["margin"])
+    assert f["consensus"] >= 8, "a consensus of %d" % f["consensus"]
+    assert f["gap"] >= GAP and f["sep"] >= 1e-7, "the null direction of a refit's normal matrix is not isolated (%g, %g)" % (f["gap"], f["sep"])
+    case.update(comp=f["comp"], matches=f["matches"], well=f["well"], figures={k: v for k, v in f.items() if k not in ("comp", "matches", "well")})
+    if with_ref:
+        case["ref"] = without_ill_defined(case, f["comp"], f["well"])
+        assert conclusive(case["ref"]) and int(min(case["ref"]["n1raw"].min(), case["ref"]["n2raw"].min())) >= 8
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def make_drawn_case(key):
+    """The drawn case of DRAWN_SEEDS[key] with its float64 composition, ``well`` [2B,hyp] and matches; conditions asserted."""
+    return _drawn_checked(build_drawn(DRAWN_SEEDS[key], *key))
+
+
+@functools.lru_cache(maxsize=None)
+def ill_winner_case():
+    """The drawn case of ILL_WINNER: where it was searched, the reference's winner is ill-defined on some plane."""
+    return _drawn_checked(build_drawn(ILL_WINNER[1], *ILL_WINNER[0]), with_ref=False)
+
+
+def crafted_sets(case, slots=CRAFTED_SLOTS):
+    """``sets`` with the given slots of sample 0 overwritten by degenerate sets, one kind per slot, cycling: eight copies of one
+    index; two indices four times each; four indices twice each.  Every index stays inside [0, num)."""
+    num = case["num"]
+    sets = case["sets"].clone()
+    for i, slot in enumerate(slots):
+        a = [(7 * i + 3 + 11 * j) % num for j in range(4)]
+        rows = ([a[0]] * 8, [a[0]] * 4 + [a[1]] * 4, [a[0], a[0], a[1], a[1], a[2], a[2], a[3], a[3]])
+        sets[0, slot] = torch.tensor(rows[i % 3], dtype=sets.dtype)
+    assert int(sets.min()) >= 0 and int(sets.max()) < num
+    return sets
+
+
+def _own_sets(case, sets):
+    """(pts [2B*hyp,4,8] float64, T1, T2, A [2B*hyp,8,9]): every slot's own 8 matches, their Hartley normalisations (as
+    ``_eight_point`` forms them, repeated matches included) and the design matrix in normalised coordinates."""
+    from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers as S
+    sets = case["sets"] if sets is None else sets
+    m = matches_of(case).double()
+    p, _, n = m.shape
+    idx = torch.cat([sets, sets], 0).long()
+    h = idx.shape[1]
+    pts = torch.gather(m.unsqueeze(1).expand(p, h, 4, n), 3, idx.unsqueeze(2).expand(p, h, 4, 8)).reshape(p * h, 4, 8)
+    w = torch.ones(p * h, 8, dtype=torch.float64)
+    ones = torch.ones(p * h, 1, 8, dtype=torch.float64)
+    T1, T2 = S._weighted_hartley(pts[:, :2], w), S._weighted_hartley(pts[:, 2:], w)
+    p1, p2 = T1.bmm(torch.cat([pts[:, :2], ones], 1)), T2.bmm(torch.cat([pts[:, 2:], ones], 1))
+    return pts, T1, T2, (p2.unsqueeze(2) * p1.unsqueeze(1)).reshape(p * h, 9, 8).transpose(1, 2)
+
+
+def svd_route_hypotheses(case, sets=None):
+    """The reference's hypothesis table [2B,hyp,3,3] with the null vector taken the other way: the last right singular vector
+    of the 8x9 design matrix instead of ``eigh`` of the normal matrix; then rank 2 and the un-normalisation as in the class."""
+    sets = case["sets"] if sets is None else sets
+    _, T1, T2, A = _own_sets(case, sets)
+    _, _, Vh = torch.linalg.svd(A, full_matrices=True)
+    U, sv, Wh = torch.linalg.svd(Vh[:, -1, :].reshape(-1, 3, 3))
+    sv = sv.clone()
+    sv[:, 2] = 0.0
+    Fh = T2.transpose(1, 2).bmm(U.bmm(torch.diag_embed(sv)).bmm(Wh)).bmm(T1)
+    return Fh.reshape(2 * case["B"], sets.shape[1], 3, 3)
+
+
+def null_space_figures(case, Fh, sets=None):
+    """Of a table Fh [2B,hyp,3,3] (float64): (res, det, fit) [2B,hyp], NaN where F is not finite.
+    res: max |x2^T F x1| over the slot's own 8 matches, over max |F| and the square of the coordinates' scale (the largest
+    |coordinate| of the plane, at least 1) -- not at rounding level for any table, since rank 2 is enforced after the null vector
+    is taken; det: |det F| / max |F|^3.
+    fit: what res cannot see.  In normalised coordinates G = T2^-T F T1^-1 is the null vector less its smallest singular triple,
+    so G + c u3 v3^T (u3, v3: G's own null directions) must lie in the null space of the slot's design matrix A for the best c:
+    min_c |A vec(G + c u3 v3^T)| / (|A| |G|), at rounding level for a member of the null space and of order 1 for anything
+    else of rank 2."""
+    B = case["B"]
+    sets = case["sets"] if sets is None else sets
+    pts, T1, T2, A = _own_sets(case, sets)
+    p, h = 2 * B, sets.shape[1]
+    Fh = Fh.double()
+    F = Fh.reshape(p * h, 3, 3)
+    G = torch.linalg.solve(T2.transpose(1, 2), torch.nan_to_num(F)).bmm(torch.inverse(T1))
+    U, _, Vh = torch.linalg.svd(G)
+    N = U[:, :, 2].unsqueeze(2) * Vh[:, 2, :].unsqueeze(1)
+    g, a = A.bmm(G.reshape(-1, 9, 1)).squeeze(2), A.bmm(N.reshape(-1, 9, 1)).squeeze(2)
+    c = -(a * g).sum(1) / (a * a).sum(1).clamp_min(1e-300)
+    fit = (g + c.unsqueeze(1) * a).norm(dim=1) / (A.reshape(p * h, -1).norm(dim=1) * G.reshape(p * h, -1).norm(dim=1)).clamp_min(1e-300)
+    fit = torch.where(torch.isfinite(F).all(2).all(1), fit, torch.full_like(fit, float("nan"))).reshape(p, h)
+    m = matches_of(case).double()
+    pts = pts.reshape(p, h, 4, 8)
+    ones = torch.ones(p, h, 1, 8, dtype=torch.float64)
+    x1, x2 = torch.cat([pts[:, :, :2], ones], 2), torch.cat([pts[:, :, 2:], ones], 2)                 # [p,h,3,8]
+    r = (x2 * Fh.matmul(x1)).sum(2).abs().amax(2)
+    fmax = Fh.abs().amax((2, 3))
+    scale = m.abs().amax((1, 2)).clamp_min(1.0).view(p, 1)
+    return r / (fmax * scale * scale), torch.det(Fh).abs() / fmax ** 3, fit

@@ -131,6 +131,16 @@ def points_of(case, flow_bwd=None, flow_fwd=None, disp_t=None):
     return torch.cat(xs, 0), torch.cat(Xs, 0)
 
 
+def _dlt_system(xs, Xs, Kinv):
+    """The 12x12 system of ``_pnp_hypotheses`` for the gathered sets xs [b,h,6,2], Xs [b,h,6,3]."""
+    b, h = Xs.shape[0], Xs.shape[1]
+    ones = torch.ones(b, h, 6, 1, dtype=Xs.dtype, device=Xs.device)
+    xn = torch.cat([xs, ones], 3).matmul(Kinv.t())
+    Xh = torch.cat([Xs, ones], 3)
+    zero = torch.zeros_like(Xh)
+    return torch.cat([torch.cat([Xh, zero, -xn[..., 0:1] * Xh], 3), torch.cat([zero, Xh, -xn[..., 1:2] * Xh], 3)], 2)
+
+
 def hypotheses(x, X, Kd, idx, route="svd"):
     """``_pnp_hypotheses`` restated for the sets ``idx`` [b,h,6]; ``route``: the null vector of the 12x12 system from ``svd(A)``
     (the class's own) or from ``eigh(A^T A)``."""
@@ -139,11 +149,7 @@ def hypotheses(x, X, Kd, idx, route="svd"):
     Xs = torch.gather(X.unsqueeze(1).expand(b, h, n, 3), 2, idx.unsqueeze(3).expand(b, h, 6, 3))
     xs = torch.gather(x.unsqueeze(1).expand(b, h, n, 2), 2, idx.unsqueeze(3).expand(b, h, 6, 2))
     Kinv = torch.inverse(Kd)
-    ones = torch.ones(b, h, 6, 1, dtype=X.dtype, device=X.device)
-    xn = torch.cat([xs, ones], 3).matmul(Kinv.t())
-    Xh = torch.cat([Xs, ones], 3)
-    zero = torch.zeros_like(Xh)
-    A = torch.cat([torch.cat([Xh, zero, -xn[..., 0:1] * Xh], 3), torch.cat([zero, Xh, -xn[..., 1:2] * Xh], 3)], 2)
+    A = _dlt_system(xs, Xs, Kinv)
     if route == "svd":
         _, _, Vh = torch.linalg.svd(A)
         P = Vh[..., -1, :].reshape(b, h, 3, 4)
@@ -171,14 +177,21 @@ def composition(x, X, K, sets, iterations=ITERS, thresh=THRESH, route="svd", vot
     """The robust branch of ``GeometrySolvers.pnp`` (geometry_solvers.py) for the planes of ONE sample -- x [p,n,2], X [p,n,3]
     float64, K [3,3], sets [hyp,6] shared by the planes -- from the class's own pieces.  dict: err [p,hyp,n] (non-finite -> inf),
     zh, counts [p,hyp], best [p], w1, w2 [p,n] (after the fall-backs), n1raw / n2raw (before them), e1 / z1 (the re-score), e2 / z2
-    (the final pose's, not used by the estimate), P [p,6] float64."""
+    (the final pose's, not used by the estimate), P [p,6] float64, Rh / Th (the hypothesis table)."""
+    Kd = K.detach().double()
+    idx = sets.long().unsqueeze(0).expand(X.shape[0], -1, -1)
+    Rh, Th = hypotheses(x, X, Kd, idx, route)
+    return _continue(x, X, K, Rh, Th, iterations, thresh, votes_only)
+
+
+def _continue(x, X, K, Rh, Th, iterations=ITERS, thresh=THRESH, votes_only=False):
+    """``composition`` from its hypothesis table on: Rh [p,hyp,3,3], Th [p,hyp,3] float64 (any table, non-finite entries included:
+    a NaN residual fails both comparisons, as in the class)."""
     m = solvers()
     Kd = K.detach().double()
     p, n = X.shape[0], X.shape[1]
     cam = (Kd[0, 0], Kd[1, 1], Kd[0, 2], Kd[1, 2])
     fx, fy, cx, cy = cam
-    idx = sets.long().unsqueeze(0).expand(p, -1, -1)
-    Rh, Th = hypotheses(x, X, Kd, idx, route)
     Yh = X.unsqueeze(1).matmul(Rh.transpose(2, 3)) + Th.unsqueeze(2)
     zh = Yh[..., 2]
     eu = fx * Yh[..., 0] / zh.clamp_min(1e-9) + cx - x[:, :, 0].unsqueeze(1)
@@ -187,7 +200,8 @@ def composition(x, X, K, sets, iterations=ITERS, thresh=THRESH, route="svd", vot
     inl = (err <= thresh * thresh) & (zh > 0)
     counts = inl.sum(2)
     best = counts.argmax(1)
-    out = dict(err=torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf"))), zh=zh, inl=inl, counts=counts, best=best)
+    out = dict(err=torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf"))), zh=zh, inl=inl, counts=counts, best=best,
+               Rh=Rh, Th=Th)
     if votes_only:
         return out
     R = torch.gather(Rh, 1, best.view(p, 1, 1, 1).expand(p, 1, 3, 3)).squeeze(1)
@@ -296,3 +310,251 @@ def pose_vectors(case, seed=0, scale=1.0):
     p = torch.randn(case["B"], 2, 6, generator=g) * 0.1
     p[:, :, :3] += torch.tensor([1.0, 0.5, 0.1])
     return p * scale
+
+
+# ------------------------------------------------------------------------------------------------ the product's own draws
+# As in tests/eight_point_cases.py: ``pick`` drawn with replacement and ``sets`` by the class's own ``_minimal_sets(.., 6, ..)``.  A
+# slot whose 6 matches are not 6 distinct pixels, or whose 12x12 DLT normal matrix has no isolated null direction, is ILL-DEFINED:
+# which vector of its null space ``svd`` or the kernel's Jacobi returns is decided by rounding.
+# key -> seed, found with find_drawn_seed(*key).  Asserted on every host (``_drawn_checked``): every plane has at least hyp / 4
+# well-defined and 4 ill-defined slots, no residual of a well-defined slot or of a re-score lies within MARGIN of the threshold (no
+# depth within MARGIN of zero), every consensus has 6 members, the votes of the well-defined slots do not depend on the route to the
+# null vector, and both refinements' 6x6 normal matrices are well conditioned (LM_COND).  Steering the search only, NOT asserted: the
+# reference's winner is well-defined and leads every ill-defined slot's count by LEAD -- those counts rest on vectors that the
+# host's LAPACK picks by rounding; asserted in its place is the composition without the ill-defined slots
+# (``without_ill_defined``), which every host agrees on and the kernel must reproduce.  Seed 1 of the first shape meets all of that
+# and was passed over after one run on the device: slot 24 of plane 2 repeats a pixel, polls 1 vote under ``svd`` and 43 under the
+# kernel's Jacobi -- the winner's count -- and, being the lower slot, is elected (the poses agree to 6.5e-10 all the same: its
+# inlier set is the winner's).
+GAP = 10.0
+LEAD = 16
+LM_COND = 1e-7       # smallest over largest eigenvalue of J^T J: a float64 solve leaves the step a relative 1e-9, below P_BOUND
+DRAWN_SEEDS = {
+    (2, 12, 20, 72, 64, 64, True): 8,
+    (3, 13, 19, 72, 70, 33, True): 33,
+    (2, 20, 24, 320, 300, 70, True): 1,
+}
+DRAWN_SHAPES = tuple(sorted(DRAWN_SEEDS))
+# one more case, found with find_drawn_seed(*key, ill_winner=True): on some plane the reference's winner is ill-defined.  Seeds 0, 2
+# and 3 meet that too and were passed over after one run on the device: the kernel's own winners there all have 6 distinct pixels
+# (ill-defined by the isolation figures only), and the case is for a winner that repeats a match
+ILL_WINNER = ((2, 12, 20, 72, 64, 64, True), 5)
+CRAFTED_SLOTS = (0, 31, 32, 63, 64, 69)          # see tests/eight_point_cases.py
+COINCIDENT = (5, 50, 95, 140, 185, 230)          # the matches whose ``pick`` the fourth kind of crafted set moves onto one pixel
+
+
+def build_drawn(seed, B, H, W, k, num, hyp, noisy):
+    """``build`` with ``pick`` drawn with replacement from a generator seeded with ``seed`` and ``sets`` the class's own
+    ``_minimal_sets(B, num, 6, "cpu")`` at ``ransac_iters = hyp`` (a function of the shape alone)."""
+    case = build(seed, B, H, W, k, num, hyp, noisy)
+    g = torch.Generator().manual_seed(seed)
+    case["pick"] = torch.randint(0, k, (num,), generator=g)
+    m = solvers()
+    m.ransac_iters = hyp
+    case["sets"] = m._minimal_sets(B, num, 6, "cpu").to(torch.int32)
+    return case
+
+
+def distinct_pixels(case, sets=None):
+    """bool [B,hyp]: the 6 matches of the set are 6 distinct pixels (``idx`` is duplicate-free, so of either direction's plane)."""
+    sets = case["sets"] if sets is None else sets
+    px = case["pick"][sets.long()].sort(2)[0]
+    return (px[:, :, 1:] != px[:, :, :-1]).all(2)
+
+
+def _plane_sets(case, sets):
+    B = case["B"]
+    return torch.stack([sets[p % B] for p in range(2 * B)], 0).long()
+
+
+def well_defined(case, sets=None):
+    """bool [2B,hyp]: the slot's 6 matches are pairwise distinct pixels of its plane and the null direction of its float64
+    normal matrix A^T A is isolated (the smallest eigenvalue at most 1 / GAP of the next, the two at least 1e-7 of the largest
+    apart).  Everything else is ill-defined."""
+    B = case["B"]
+    sets = case["sets"] if sets is None else sets
+    x, X = points_of(case)
+    idx = _plane_sets(case, sets)
+    p, h, n = idx.shape[0], idx.shape[1], X.shape[1]
+    Xs = torch.gather(X.unsqueeze(1).expand(p, h, n, 3), 2, idx.unsqueeze(3).expand(p, h, 6, 3))
+    xs = torch.gather(x.unsqueeze(1).expand(p, h, n, 2), 2, idx.unsqueeze(3).expand(p, h, 6, 2))
+    iso = []
+    for q in range(p):
+        A = _dlt_system(xs[q:q + 1], Xs[q:q + 1], torch.inverse(case["K"][q % B].double()))
+        ev = torch.linalg.eigvalsh(A.transpose(2, 3).matmul(A))[0]
+        iso.append((ev[:, 1] / ev[:, 0].clamp_min(1e-300) >= GAP) & ((ev[:, 1] - ev[:, 0]) / ev[:, 11] >= 1e-7))
+    return torch.stack(iso, 0) & torch.cat([distinct_pixels(case, sets)] * 2, 0)
+
+
+def rel_margin(e, keep=None, thresh=THRESH):
+    """The smallest relative distance of a finite residual to the threshold (inf if there is none); ``keep``: a mask."""
+    t = thresh * thresh
+    e = e if keep is None else e[keep]
+    e = e[torch.isfinite(e)]
+    return float(((e - t).abs() / t).min()) if e.numel() else float("inf")
+
+
+def abs_margin(z, keep=None):
+    z = z if keep is None else z[keep]
+    z = z[torch.isfinite(z)]
+    return float(z.abs().min()) if z.numel() else float("inf")
+
+
+def lm_condition(x, X, K, P, wgt):
+    """[p]: smallest over largest eigenvalue of ``_pnp_refine``'s J^T J at the pose P [p,6] = (T, axis-angle) over the matches of
+    weight 1 -- how well the refinement that ended there is posed."""
+    m = solvers()
+    Kd = K.detach().double()
+    fx, fy = Kd[0, 0], Kd[1, 1]
+    R, T = m._so3_exp(P[:, 3:]), P[:, :3]
+    p, n = X.shape[0], X.shape[1]
+    Y = X.bmm(R.transpose(1, 2)) + T.unsqueeze(1)
+    zi = 1.0 / Y[:, :, 2].clamp_min(1e-9)
+    zero = torch.zeros_like(zi)
+    du = torch.stack([fx * zi, zero, -fx * Y[:, :, 0] * zi * zi], 2)
+    dv = torch.stack([zero, fy * zi, -fy * Y[:, :, 1] * zi * zi], 2)
+    Q = Y - T.unsqueeze(1)
+    Pc = torch.stack([zero, -Q[:, :, 2], Q[:, :, 1], Q[:, :, 2], zero, -Q[:, :, 0], -Q[:, :, 1], Q[:, :, 0], zero], 2).view(p, n, 3, 3)
+    sw = wgt.unsqueeze(2)
+    J = torch.cat([torch.cat([-(du.unsqueeze(2) @ Pc).squeeze(2), du], 2) * sw, torch.cat([-(dv.unsqueeze(2) @ Pc).squeeze(2), dv], 2) * sw], 1)
+    ev = torch.linalg.eigvalsh(J.transpose(1, 2).bmm(J))
+    return ev[:, 0] / ev[:, 5]
+
+
+def continued(case, Rh, Th, iterations=ITERS):
+    """The float64 composition CONTINUED FROM A GIVEN HYPOTHESIS TABLE (Rh [2B,hyp,3,3], Th [2B,hyp,3] float64; the kernel's own,
+    say): every hypothesis recounted from that table, argmax (ties: the lowest index), w1, the fall-back, the refinement, the
+    re-score, w2, its fall-back and the second refinement -- ``_continue``, the very code ``composition`` runs after its own
+    table.  Added: ``margin`` / ``zmargin`` (the smallest relative distance to the threshold, and of a depth to zero, of anything
+    it used: every recount, the re-score and the final pose's) and ``cond2`` [2B] (``lm_condition`` of the final pose on w2;
+    ``cond1``: on w1)."""
+    B = case["B"]
+    x, X = points_of(case)
+    per = [_continue(x[b::B], X[b::B], case["K"][b], Rh[b::B].double(), Th[b::B].double(), iterations) for b in range(B)]
+    order = [(p % B, p // B) for p in range(2 * B)]
+    c = {k: torch.stack([per[b][k][d] for b, d in order], 0) for k in per[0]}
+    c["margin"] = min(rel_margin(c[k]) for k in ("err", "e1", "e2"))
+    c["zmargin"] = min(abs_margin(c[k]) for k in ("zh", "z1", "z2"))
+    c["cond1"] = torch.cat([lm_condition(x[p:p + 1], X[p:p + 1], case["K"][p % B], c["P"][p:p + 1], c["w1"][p:p + 1]) for p in range(2 * B)])
+    c["cond2"] = torch.cat([lm_condition(x[p:p + 1], X[p:p + 1], case["K"][p % B], c["P"][p:p + 1], c["w2"][p:p + 1]) for p in range(2 * B)])
+    return c
+
+
+def conclusive(c):
+    """``continued``'s own conditions."""
+    return bool(c["margin"] >= MARGIN and c["zmargin"] >= MARGIN and (c["cond1"] >= LM_COND).all() and (c["cond2"] >= LM_COND).all())
+
+
+def drawn_conditions(case):
+    """dict of the figures a drawn case is chosen by -- the reference's alone -- and the composition's results."""
+    B, hyp = case["B"], case["hyp"]
+    x, X = points_of(case)
+    c = composition_of(case, x, X)
+    api = []
+    for b in range(B):
+        s = solvers(case["sets"][b].unsqueeze(0).expand(2, -1, -1))
+        api.append(s.pnp(x[b::B], X[b::B], case["K"][b].double(), iterations=ITERS))
+    P_api = torch.stack([api[p % B][p // B] for p in range(2 * B)], 0)
+    wd = well_defined(case)
+    keep = wd.unsqueeze(2).expand_as(c["err"])
+    margin = min(rel_margin(c["err"], keep), rel_margin(c["e1"]), rel_margin(c["e2"]))
+    zmargin = min(abs_margin(c["zh"], keep), abs_margin(c["z1"]), abs_margin(c["z2"]))
+    votes = []
+    for b in range(B):
+        v = composition(x[b::B], X[b::B], case["K"][b], case["sets"][b], route="eigh", votes_only=True)
+        mine = torch.stack([c["inl"][b], c["inl"][B + b]], 0)
+        well = torch.stack([wd[b], wd[B + b]], 0)
+        votes.append(torch.equal(v["inl"][well], mine[well]))
+    top = c["counts"].max(1)[0]
+    ill_top = torch.where(wd, torch.full_like(c["counts"], -10 ** 6), c["counts"]).max(1)[0]
+    cond = torch.cat([torch.minimum(lm_condition(x[p:p + 1], X[p:p + 1], case["K"][p % B], c["P"][p:p + 1], c["w1"][p:p + 1]),
+                                    lm_condition(x[p:p + 1], X[p:p + 1], case["K"][p % B], c["P"][p:p + 1], c["w2"][p:p + 1]))
+                      for p in range(2 * B)])
+    return dict(comp=c, x=x, X=X, well=wd, api_equal=torch.equal(P_api, c["P"]), n_well=int(wd.sum(1).min()), n_ill=int((~wd).sum(1).min()),
+                margin=margin, zmargin=zmargin, route_free=all(votes), winner_well=torch.gather(wd, 1, c["best"].view(-1, 1)).squeeze(1),
+                lead=int((top - ill_top).min()), consensus=int(min(c["n1raw"].min(), c["n2raw"].min())), cond=float(cond.min()))
+
+
+def drawn_ok(f, case, ill_winner=False):
+    ok = f["api_equal"] and 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4 and f["margin"] >= MARGIN and f["zmargin"] >= MARGIN
+    ok = ok and f["route_free"] and f["consensus"] >= 6 and f["cond"] >= LM_COND
+    if ill_winner:
+        return ok and not bool(f["winner_well"].all())
+    return ok and bool(f["winner_well"].all()) and f["lead"] >= LEAD
+
+
+def find_drawn_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, ill_winner=False):
+    """The first seed from ``start`` whose drawn case meets the conditions (run once on the CPU; the result goes into DRAWN_SEEDS
+    or ILL_WINNER)."""
+    for seed in range(start, start + tries):
+        case = build_drawn(seed, B, H, W, k, num, hyp, noisy)
+        if drawn_ok(drawn_conditions(case), case, ill_winner):
+            return seed
+    raise RuntimeError("no seed found")
+
+
+def without_ill_defined(case, comp, well):
+    """The composition with the ill-defined slots refused a vote: ``continued`` from the reference's table with those slots made
+    non-finite.  Nothing in it rests on a vector that rounding picked, so it is the same on every host."""
+    Rh = comp["Rh"].clone()
+    Rh[~well] = float("nan")
+    return continued(case, Rh, comp["Th"])
+
+
+def _drawn_checked(case, with_ref=True):
+    """Asserts what does not depend on the host: the figures of the well-defined slots and of the refinements.  ``winner_well`` and
+    ``lead`` rest on the counts of ill-defined slots, which the host's LAPACK decides: they steer ``find_drawn_seed`` and are kept
+    in ``figures``, not asserted.  ``ref``: the composition without the ill-defined slots -- what the kernel must arrive at
+    whenever none of its own ill-defined slots out-polls the winner."""
+    f = drawn_conditions(case)
+    assert f["api_equal"], "the restated composition is not GeometrySolvers.pnp"
+    assert 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4, "a plane with %d well-defined, %d ill-defined slots" % (f["n_well"], f["n_ill"])
+    assert f["margin"] >= MARGIN, "a residual within a relative %g of the threshold (%g)" % (MARGIN, f["margin"])
+    assert f["zmargin"] >= MARGIN, "a depth within %g of zero (%g)" % (MARGIN, f["zmargin"])
+    assert f["route_free"], "a well-defined slot's votes depend on the route to the DLT's null vector"
+    assert f["consensus"] >= 6, "a consensus of %d" % f["consensus"]
+    assert f["cond"] >= LM_COND, "a refinement's normal matrix is ill conditioned (%g)" % f["cond"]
+    case.update(comp=f["comp"], x=f["x"], X=f["X"], well=f["well"], figures={k: v for k, v in f.items() if k not in ("comp", "x", "X", "well")})
+    if with_ref:
+        case["ref"] = without_ill_defined(case, f["comp"], f["well"])
+        assert conclusive(case["ref"]) and int(min(case["ref"]["n1raw"].min(), case["ref"]["n2raw"].min())) >= 6
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def make_drawn_case(key):
+    """The drawn case of DRAWN_SEEDS[key] with its float64 composition, ``well`` [2B,hyp] and points; conditions asserted."""
+    return _drawn_checked(build_drawn(DRAWN_SEEDS[key], *key))
+
+
+@functools.lru_cache(maxsize=None)
+def ill_winner_case():
+    """The drawn case of ILL_WINNER: where it was searched, the reference's winner is ill-defined on some plane."""
+    return _drawn_checked(build_drawn(ILL_WINNER[1], *ILL_WINNER[0]), with_ref=False)
+
+
+def coincident_pick(case):
+    """``pick`` with the entries COINCIDENT set to that of the first: six matches of one pixel, six coincident 3-D points."""
+    pick = case["pick"].clone()
+    pick[list(COINCIDENT)] = int(pick[COINCIDENT[0]])
+    return pick
+
+
+def crafted_sets(case, slots=CRAFTED_SLOTS):
+    """``sets`` with the given slots of sample 0 overwritten by degenerate sets, one kind per slot, cycling: six copies of one
+    index; two indices three times each; three indices twice each; the six matches COINCIDENT (one pixel under
+    ``coincident_pick``).  Every index stays inside [0, num)."""
+    num = case["num"]
+    sets = case["sets"].clone()
+    for i, slot in enumerate(slots):
+        a = [(7 * i + 3 + 11 * j) % num for j in range(3)]
+        rows = ([a[0]] * 6, [a[0]] * 3 + [a[1]] * 3, [a[0], a[0], a[1], a[1], a[2], a[2]], list(COINCIDENT))
+        sets[0, slot] = torch.tensor(rows[i % 4], dtype=sets.dtype)
+    assert int(sets.min()) >= 0 and int(sets.max()) < num
+    return sets
+
+
+def rotation_figures(Rh):
+    """Of rotations [...,3,3] float64: (max |R^T R - I|, |det R - 1|); NaN where R is not finite."""
+    eye = torch.eye(3, dtype=torch.float64)
+    return (Rh.transpose(-1, -2).matmul(Rh) - eye).abs().amax((-1, -2)), (torch.det(Rh) - 1.0).abs()

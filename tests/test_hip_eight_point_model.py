@@ -155,3 +155,84 @@ def test_the_step_with_the_term_is_captured_and_equals_the_eager_step():
         del g
         torch.cuda.synchronize()
         convs.set_deterministic(before)
+
+
+# ------------------------------------------------------------------------------------------------ the term through models.py
+# A rigid scene of tests/eight_point_cases.py (its depth map as the disparity, its flows, a camera matrix per sample) through
+# ``geometric_draw`` and ``eight_point_term``: the draw's wiring by bits, the loss and the pose gradient against float64 autograd
+# of compute_eight_point_loss's expression on the oracle's [t]x R with the kernel's own F64 as the constant target.  The pose's
+# translation is scaled by 40 (as the kernel-level loss test's second scale): at scale 1 every |F_pred - F| lies beyond smooth-L1's
+# knee for sample 0 and exchanging the two directions' targets moves its loss by 6e-6 only; at 40 both orderings are visible.
+# "Visible": some sample's loss moves by more than 100 x LOSS_TOL (the largest move over the samples; at B = 3 one sample moves by
+# 2.7e-4 only under the exchange), which is what a per-sample comparison at LOSS_TOL needs.
+LOSS_TOL, GRAD_TOL = 5e-6, 2e-5           # the kernel-level test's (tests/test_hip_eight_point.py)
+MODEL_SCENES = ((2, 12, 20), (3, 12, 20))
+
+
+def _scene(shape):
+    from tests import eight_point_cases as EC
+    B, H, W = shape
+    case = EC.build(0, B, H, W, int(0.3 * H * W), 64, 64, True)
+    pose = EC.pose_vectors(case)
+    pose[:, :, :3] *= 40.0
+    m = _bare(False, True)
+    m.ratio, m.num, m.ransac_iters = 0.3, 64, 64
+    return case, pose, m
+
+
+def _on_device(case, pose):
+    g = lambda t: t.to(dev()).contiguous()   # noqa: E731
+    return dict(disp=g(case["disp_t"]), fb=g(case["flow_bwd"]), ff=g(case["flow_fwd"]), K=g(case["K"]), Ki=g(case["K_inv"]),
+                pose=g(pose).requires_grad_(True))
+
+
+@pytest.mark.parametrize("shape", MODEL_SCENES)
+def test_the_term_is_the_operator_on_the_models_own_draw(shape):
+    """After the same seed, ``geometric_draw`` followed by a direct ``fundamental_ransac`` on ``minimal_sets_device`` gives the bits
+    of ``eight_point_term(..., return_F=True)``; the draw is with replacement."""
+    from unsupervised_depth_opticalflow_egomotion_amd import eight_point, ops
+    case, pose, m = _scene(shape)
+    B = case["B"]
+    x = _on_device(case, pose)
+    torch.manual_seed(7)
+    idx, pick = m.geometric_draw(x["disp"], x["pose"], x["fb"], x["ff"], x["K"])
+    assert tuple(idx.shape) == (2 * B, 72) and tuple(pick.shape) == (64,) and pick.unique().numel() < 64
+    sets = m.minimal_sets_device(B, 64, dev())
+    assert tuple(sets.shape) == (B, 64, 8)
+    F32, F64, info = eight_point.fundamental_ransac(x["fb"], x["ff"], idx, pick, sets, 0.1)
+    direct = eight_point.EightPointLossFn.apply(ops.PoseMatsFn.apply(x["pose"].reshape(2 * B, 6))[1], x["K"], x["Ki"], F32)
+    torch.manual_seed(7)
+    loss, F64m = m.eight_point_term(x["disp"], x["pose"], x["fb"], x["ff"], x["K"], x["Ki"], return_F=True)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(F64).all()) and int(info[:, 1].min()) >= 8
+    assert torch.equal(F64m.view(torch.int64), F64.view(torch.int64)) and torch.equal(loss.detach().view(torch.int32), direct.detach().view(torch.int32))
+    torch.manual_seed(8)                                            # another seed, another draw
+    _, other = m.eight_point_term(x["disp"], x["pose"], x["fb"], x["ff"], x["K"], x["Ki"], return_F=True)
+    assert not torch.equal(other, F64)
+
+
+@pytest.mark.parametrize("shape", MODEL_SCENES)
+def test_the_term_and_its_pose_gradient_equal_float64_autograd_of_the_reference_expression(shape):
+    from tests.test_hip_eight_point import WEIGHTS_OF, _loss_reference
+    case, pose, m = _scene(shape)
+    B = case["B"]
+    x = _on_device(case, pose)
+    w = torch.tensor(WEIGHTS_OF[B])
+    torch.manual_seed(7)
+    loss, F64 = m.eight_point_term(x["disp"], x["pose"], x["fb"], x["ff"], x["K"], x["Ki"], return_F=True)
+    (loss * w.to(dev())).sum().backward()
+    torch.cuda.synchronize()
+    F64 = F64.cpu()
+    l64, g64, _ = _loss_reference(F64, case["K"], case["K_inv"], pose, w)
+    l32, g32, _ = _loss_reference(F64, case["K"], case["K_inv"], pose, w, dtype=torch.float32)
+    fl = float(((l32.double() - l64).abs() / l64.abs()).max())
+    fg = float((g32.double() - g64).abs().max() / g64.abs().max())
+    el = float(((loss.detach().double().cpu() - l64).abs() / l64.abs()).max())
+    eg = float((x["pose"].grad.double().cpu() - g64).abs().max() / g64.abs().max())
+    print("EBOUND eight_point model %dx%dx%d: loss %.3e (%g)  dpose %.3e (%g); the reference expression in fp32 on the CPU against "
+          "float64: loss %.3e  dpose %.3e" % (shape + (el, LOSS_TOL, eg, GRAD_TOL, fl, fg)))
+    assert tuple(loss.shape) == (B,) and el <= LOSS_TOL and eg <= GRAD_TOL
+    # the case tells the orderings apart with the kernel's own target: the directions' planes exchanged, or E's row d*B + b
+    swapped = _loss_reference(torch.cat([F64[B:], F64[:B]], 0), case["K"], case["K_inv"], pose, w)[0]
+    rows = _loss_reference(F64, case["K"], case["K_inv"], pose.reshape(2, B, 6).permute(1, 0, 2).contiguous(), w)[0]
+    assert float(((swapped - l64).abs() / l64).max()) > 100 * LOSS_TOL and float(((rows - l64).abs() / l64).max()) > 100 * LOSS_TOL

@@ -165,3 +165,85 @@ def test_the_step_with_the_term_is_captured_and_equals_the_eager_step():
         del g
         torch.cuda.synchronize()
         convs.set_deterministic(before)
+
+
+# ------------------------------------------------------------------------------------------------ the term through models.py
+# A rigid scene of tests/pnp_cases.py (its depth map as the disparity, its flows, a camera matrix per sample) through
+# ``geometric_draw`` and ``pnp_term``: the draw's wiring by bits -- line 509's ``K[0]`` for every sample included, which a case with
+# one K per sample can tell from ``K[b]`` -- the loss and the pose gradient against float64 autograd of compute_pnp_loss's
+# expression ((T, axis-angle) against (translation, Euler), beta = 0.5) with the kernel's own P64 as the constant target.
+LOSS_TOL, GRAD_TOL = 5e-6, 2e-5           # the kernel-level test's (tests/test_hip_pnp.py)
+MODEL_SCENES = ((2, 12, 20), (3, 12, 20))
+MODEL_BETA = 0.5
+
+
+def _scene(shape):
+    from tests import pnp_cases as PC
+    B, H, W = shape
+    case = PC.build(0, B, H, W, int(0.3 * H * W), 64, 64, True)
+    m = _bare(False, False, True, beta=MODEL_BETA)
+    m.ratio, m.num, m.ransac_iters = 0.3, 64, 64
+    return case, PC.pose_vectors(case), m
+
+
+def _on_device(case, pose):
+    g = lambda t: t.to(dev()).contiguous()   # noqa: E731
+    return dict(disp=g(case["disp_t"]), fb=g(case["flow_bwd"]), ff=g(case["flow_fwd"]), K=g(case["K"]), Ki=g(case["K_inv"]),
+                pose=g(pose).requires_grad_(True))
+
+
+@pytest.mark.parametrize("shape", MODEL_SCENES)
+def test_the_term_is_the_operator_on_the_models_own_draw_with_the_first_camera(shape):
+    """After the same seed, ``geometric_draw`` followed by a direct ``pnp_ransac`` on ``minimal_sets_device(k=6)`` with
+    ``K[:1].expand(B, 3, 3)`` gives the bits of ``pnp_term(..., return_pose=True)``; the call with ``K`` itself does not."""
+    from unsupervised_depth_opticalflow_egomotion_amd import pnp
+    case, pose, m = _scene(shape)
+    B = case["B"]
+    x = _on_device(case, pose)
+    assert not torch.equal(case["K"][0], case["K"][1])
+    torch.manual_seed(7)
+    idx, pick = m.geometric_draw(x["disp"], x["pose"], x["fb"], x["ff"], x["K"])
+    assert tuple(idx.shape) == (2 * B, 72) and tuple(pick.shape) == (64,) and pick.unique().numel() < 64
+    sets = m.minimal_sets_device(B, 64, dev(), k=6)
+    assert tuple(sets.shape) == (B, 64, 6)
+    K0 = x["K"][:1].expand(B, 3, 3).contiguous()
+    P32, P64, info = pnp.pnp_ransac(x["fb"], x["ff"], x["disp"], idx, pick, sets, K0, x["Ki"], iters=20, thresh=1.0)
+    _, own, _ = pnp.pnp_ransac(x["fb"], x["ff"], x["disp"], idx, pick, sets, x["K"], x["Ki"], iters=20, thresh=1.0)
+    direct = pnp.PnpLossFn.apply(x["pose"], P32, MODEL_BETA)
+    torch.manual_seed(7)
+    loss, P64m = m.pnp_term(x["disp"], x["pose"], x["fb"], x["ff"], x["K"], x["Ki"], return_pose=True)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(P64).all())
+    assert torch.equal(P64m.view(torch.int64), P64.view(torch.int64)) and torch.equal(loss.detach().view(torch.int32), direct.detach().view(torch.int32))
+    planes = [d * B + b for d in range(2) for b in range(1, B)]      # every sample but the first sees another camera
+    assert not torch.equal(own[planes], P64m[planes]) and torch.equal(own[[0, B]], P64m[[0, B]])
+    torch.manual_seed(8)                                            # another seed, another draw
+    _, other = m.pnp_term(x["disp"], x["pose"], x["fb"], x["ff"], x["K"], x["Ki"], return_pose=True)
+    assert not torch.equal(other, P64)
+
+
+@pytest.mark.parametrize("shape", MODEL_SCENES)
+def test_the_term_and_its_pose_gradient_equal_float64_autograd_of_the_reference_expression(shape):
+    from tests.test_hip_pnp import WEIGHTS_OF, _loss_reference
+    case, pose, m = _scene(shape)
+    B = case["B"]
+    x = _on_device(case, pose)
+    w = torch.tensor(WEIGHTS_OF[B])
+    torch.manual_seed(7)
+    loss, P64 = m.pnp_term(x["disp"], x["pose"], x["fb"], x["ff"], x["K"], x["Ki"], return_pose=True)
+    (loss * w.to(dev())).sum().backward()
+    torch.cuda.synchronize()
+    P64 = P64.cpu()
+    l64, g64 = _loss_reference(P64, pose, MODEL_BETA, w)
+    l32, g32 = _loss_reference(P64, pose, MODEL_BETA, w, dtype=torch.float32)
+    fl = float(((l32.double() - l64).abs() / l64.abs()).max())
+    fg = float((g32.double() - g64).abs().max() / g64.abs().max())
+    el = float(((loss.detach().double().cpu() - l64).abs() / l64.abs()).max())
+    eg = float((x["pose"].grad.double().cpu() - g64).abs().max() / g64.abs().max())
+    print("EBOUND pnp model %dx%dx%d: loss %.3e (%g)  dpose %.3e (%g); the reference expression in fp32 on the CPU against float64: "
+          "loss %.3e  dpose %.3e" % (shape + (el, LOSS_TOL, eg, GRAD_TOL, fl, fg)))
+    assert tuple(loss.shape) == (B,) and el <= LOSS_TOL and eg <= GRAD_TOL
+    # the case tells the orderings apart with the kernel's own target: the directions' planes exchanged, or pose row d*B + b
+    swapped = _loss_reference(torch.cat([P64[B:], P64[:B]], 0), pose, MODEL_BETA, w)[0]
+    rows = _loss_reference(P64, pose.reshape(2, B, 6).permute(1, 0, 2).contiguous(), MODEL_BETA, w)[0]
+    assert float(((swapped - l64).abs() / l64).max()) > 100 * LOSS_TOL and float(((rows - l64).abs() / l64).max()) > 100 * LOSS_TOL

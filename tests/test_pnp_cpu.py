@@ -158,3 +158,116 @@ def test_the_edge_cases_meet_their_conditions(name):
         assert num == PC.MATCH_TILE and hyp == 2 * PC.HYP_TILE
     if name in ("b1", "b3"):
         assert B == int(name[1]) and tuple(c["P"].shape) == (2 * B, 6)
+
+
+def _drawn_layout(case, key):
+    B, H, W, k, num, hyp, noisy = key
+    assert case["pick"].dtype == torch.int64 and tuple(case["pick"].shape) == (num,) and int(case["pick"].min()) >= 0 and int(case["pick"].max()) < k
+    assert case["pick"].unique().numel() < num                                         # drawn with replacement: some pixel repeats
+    s = case["sets"]
+    assert s.dtype == torch.int32 and tuple(s.shape) == (B, hyp, 6) and int(s.min()) >= 0 and int(s.max()) < num
+    m = PC.solvers()
+    m.ransac_iters = hyp
+    assert torch.equal(s.long(), m._minimal_sets(B, num, 6, "cpu"))                     # the class's own draw
+    well = case["well"]
+    assert well.dtype == torch.bool and tuple(well.shape) == (2 * B, hyp)
+    assert not bool((well & ~torch.cat([PC.distinct_pixels(case)] * 2, 0)).any())      # a repeated pixel is never well-defined
+
+
+@pytest.mark.parametrize("key", PC.DRAWN_SHAPES)
+def test_the_drawn_cases_meet_their_conditions(key):
+    case = PC.make_drawn_case(key)                                  # asserts the conditions itself
+    B, H, W, k, num, hyp, noisy = key
+    _drawn_layout(case, key)
+    f, c, well = case["figures"], case["comp"], case["well"]
+    assert f["api_equal"] and 4 * f["n_well"] >= hyp and f["n_ill"] >= 4 and f["margin"] >= PC.MARGIN and f["zmargin"] >= PC.MARGIN
+    assert f["route_free"] and f["consensus"] >= 6 and f["cond"] >= PC.LM_COND
+    # ``winner_well`` and ``lead`` rest on counts that the host's LAPACK decides: printed, not asserted.  What every host agrees on
+    # is the composition without the ill-defined slots
+    ref = case["ref"]
+    top = c["counts"].max(1)[0]
+    assert PC.conclusive(ref) and bool(torch.gather(well, 1, ref["best"].view(-1, 1)).all())
+    assert torch.equal(ref["counts"][well], c["counts"][well]) and int(ref["counts"][~well].max()) == 0
+    print("DRAWN pnp winner well-defined %s lead %d (this host's LAPACK)" % (f["winner_well"].tolist(), f["lead"]))
+    print("DRAWN pnp %s seed %d: well-defined slots per plane %s of %d; winner's count %s, best ill-defined count %s; margin %.3e"
+          % ("x".join(str(int(v)) for v in key), PC.DRAWN_SEEDS[key], well.sum(1).tolist(), hyp, top.tolist(),
+             [int(c["counts"][p][~well[p]].max()) for p in range(2 * B)], f["margin"]))
+
+
+def test_the_drawn_shapes_are_the_ones_the_slots_need():
+    assert PC.DRAWN_SHAPES == ((2, 12, 20, 72, 64, 64, True), (2, 20, 24, 320, 300, 70, True), (3, 13, 19, 72, 70, 33, True))
+    num, hyp = PC.DRAWN_SHAPES[1][4], PC.DRAWN_SHAPES[1][5]
+    assert max(PC.CRAFTED_SLOTS) == hyp - 1 and {0, 31, 32, 63, 64} < set(PC.CRAFTED_SLOTS) and hyp > PC.HYP_TILE
+    assert len(set(PC.COINCIDENT)) == 6 and max(PC.COINCIDENT) < num
+
+
+def test_the_ill_winner_case_meets_its_conditions():
+    case = PC.ill_winner_case()
+    key, seed = PC.ILL_WINNER
+    _drawn_layout(case, key)
+    f, c, well = case["figures"], case["comp"], case["well"]
+    won = ~torch.gather(well, 1, c["best"].view(-1, 1)).squeeze(1)           # this host's LAPACK decides: printed, not asserted
+    assert f["consensus"] >= 6 and "ref" not in case
+    print("DRAWN pnp ill-defined winner seed %d: planes %s, counts %s" % (seed, won.nonzero().flatten().tolist(), c["counts"].max(1)[0].tolist()))
+
+
+def test_continued_from_the_references_own_table_is_the_composition():
+    """Bit for bit, every entry: ``continued`` is the composition's own code after the table."""
+    cases = [PC.make_case(key) for key in PC.SHAPES] + [PC.make_drawn_case(key) for key in PC.DRAWN_SHAPES]
+    cases += [PC.ill_winner_case(), PC.fallback_case(), PC.make_edge_case("zero")]     # through both fall-backs as well
+    for case in cases:
+        c = case["comp"]
+        k = PC.continued(case, c["Rh"], c["Th"])
+        for name in c:
+            a, b = c[name], k[name]
+            assert a.dtype == b.dtype and torch.equal(a.view(torch.int64) if a.dtype == torch.float64 else a,
+                                                      b.view(torch.int64) if b.dtype == torch.float64 else b), name
+
+
+def test_continued_follows_the_table_it_is_given():
+    """Another table, another winner: with the reference's winning slot of plane 0 made non-finite the runner-up takes over."""
+    case = PC.make_drawn_case(PC.DRAWN_SHAPES[0])
+    c = case["comp"]
+    Rh = c["Rh"].clone()
+    best = int(c["best"][0])
+    Rh[0, best] = float("nan")
+    k = PC.continued(case, Rh, c["Th"])
+    counts = c["counts"][0].clone()
+    counts[best] = -1
+    assert int(k["counts"][0, best]) == 0 and int(k["best"][0]) == int(counts.argmax())
+    assert torch.equal(k["P"][1:], c["P"][1:]) and PC.conclusive(PC.continued(case, c["Rh"], c["Th"]))
+
+
+def test_the_crafted_sets_are_degenerate_and_in_range():
+    case = dict(PC.make_drawn_case(PC.DRAWN_SHAPES[1]))
+    before = case["pick"]
+    case["pick"] = PC.coincident_pick(case)
+    assert case["pick"][list(PC.COINCIDENT)].unique().numel() == 1 and int((case["pick"] != before).sum()) <= 5
+    sets = PC.crafted_sets(case)
+    assert int(sets.min()) >= 0 and int(sets.max()) < case["num"] and torch.equal(sets[1], case["sets"][1])
+    assert [sets[0, s].unique().numel() for s in PC.CRAFTED_SLOTS] == [1, 2, 3, 6, 1, 2]
+    assert not bool(PC.distinct_pixels(case, sets)[0, list(PC.CRAFTED_SLOTS)].any())   # the fourth kind: six matches, one pixel
+    well = PC.well_defined(case, sets)
+    B = case["B"]
+    assert not bool(well[0, list(PC.CRAFTED_SLOTS)].any()) and not bool(well[B, list(PC.CRAFTED_SLOTS)].any())
+    x, X = PC.points_of(case)
+    assert float((X[0, list(PC.COINCIDENT)] - X[0, PC.COINCIDENT[0]]).abs().max()) == 0.0          # coincident 3-D points
+    comp = PC.composition_of(case, x, X, sets=sets)
+    orth, det = PC.rotation_figures(comp["Rh"])                     # the reference itself leaves a rotation there
+    assert float(orth[0, list(PC.CRAFTED_SLOTS)].max()) < 1e-12 and float(det[0, list(PC.CRAFTED_SLOTS)].max()) < 1e-12
+
+
+@pytest.mark.parametrize("B", [2, 3])
+def test_the_model_scene_tells_the_plane_and_row_orderings_apart(B):
+    """tests/test_hip_pnp_model.py's scene, float64 on the CPU with the analytic pose as the target: exchanging the two directions'
+    targets (plane d*B + b read as (1-d)*B + b), or reading the pose's row d*B + b for (b, d), moves some sample's loss by more
+    than 100 x the loss tolerance; and the samples' cameras differ, so ``K[0]`` for every sample is not ``K[b]``."""
+    from tests.test_hip_pnp import WEIGHTS_OF, _loss_reference
+    case = PC.build(0, B, 12, 20, 72, 64, 64, True)
+    w = torch.tensor(WEIGHTS_OF[B])
+    pose, target = PC.pose_vectors(case), case["P_true"]
+    base = _loss_reference(target, pose, 0.5, w)[0]
+    swapped = _loss_reference(torch.cat([target[B:], target[:B]], 0), pose, 0.5, w)[0]
+    rows = _loss_reference(target, pose.reshape(2, B, 6).permute(1, 0, 2).contiguous(), 0.5, w)[0]
+    assert float(((swapped - base).abs() / base).max()) > 100 * 5e-6 and float(((rows - base).abs() / base).max()) > 100 * 5e-6
+    assert all(float((case["K"][b] - case["K"][0]).abs().max()) > 1e-2 for b in range(1, B))

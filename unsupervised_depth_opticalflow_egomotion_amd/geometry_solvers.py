@@ -206,8 +206,11 @@ class GeometrySolvers:
         return torch.maximum(d1, d2)
 
     def _minimal_sets(self, b, n, k, device):
-        """ransac_iters index sets of k matches per sample [b,h,k] from a generator seeded with ransac_seed (a set may
-        repeat an index: such a hypothesis is degenerate and simply loses the vote)."""
+        """ransac_iters index sets of k matches per sample [b,h,k] from a generator seeded with ransac_seed.  A set may
+        repeat an index (or two of its matches one pixel: the draw of the matches is with replacement too).  Such a
+        hypothesis has a null space of two or more dimensions and the vector taken from it is decided by rounding; it
+        usually polls few votes, but nothing refuses it one: it can reach the maximum count and win (measured rates:
+        profiles/ransac_degenerate_sets.txt)."""
         g = torch.Generator(device="cpu")
         g.manual_seed(int(self.ransac_seed) + 1000003 * n + 7919 * k)
         return torch.randint(0, n, (b, int(self.ransac_iters), k), generator=g).to(device)
