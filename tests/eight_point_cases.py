@@ -1,10 +1,7 @@
 """Inputs of the eight-point-term tests (tests/test_eight_point_cpu.py, tests/test_hip_eight_point.py): a helper, not a conftest.
 
-A case is a tiny two-view problem: a smooth non-planar depth in [2, 20], per sample and direction a pose with a long baseline
-(|t| about 1.5) and a small rotation, the exact rigid flow of that depth, 30 % of the pixels with their flow replaced by gross
-outliers (3 to 8 px off, either sign, both axes), optionally 0.02 px of Gaussian noise on the rest; a pixel-ordered ``idx``, a
-seeded duplicate-free ``pick`` (so that no two matches of a plane coincide), seeded duplicate-free ``sets`` and the analytic
-``F_true = K^-T [t]x R K^-1 / (.)[2,2]`` of every plane.
+A case is the two-view problem of tests/ransac_cases.py with sets of 8 and the analytic ``F_true = K^-T [t]x R K^-1 / (.)[2,2]``
+of every plane.
 
 ``composition`` restates lines 236-262 of geometry_solvers.py from the class's own pieces (``_eight_point``,
 ``_epipolar_residual``) so that the votes and the weights can be looked at; ``make_case`` asserts that its F is bit for bit what
@@ -20,15 +17,13 @@ import functools
 import numpy as np
 import torch
 
-from tests.triangle_cases import _rotation, _smooth
+from tests import ransac_cases as RC
+from tests.ransac_cases import (CRAFTED_SLOTS, HYP_TILE, LEAD, MARGIN, MATCH_TILE, NOISE_PX, OUTLIER_SHARE, WEIGHTS_OF,  # noqa: F401
+                                distinct_pixels, pose_vectors, solvers)
 
 THRESH = 0.1
-MARGIN = 1e-6
 GAP = 10.0
-NOISE_PX = 0.02
-OUTLIER_SHARE = 0.3
-# the scoring kernel's tiles (csrc/ops_eight_point.hip): EP_MATCH_TILE matches per block, EP_HYP_TILE hypotheses per LDS round
-MATCH_TILE, HYP_TILE = 256, 64
+rel_margin = functools.partial(RC.rel_margin, thresh=THRESH)
 # (B, H, W, k, num, hyp, noisy) -> seed; found with find_seed(*key).  The third shape: num above MATCH_TILE (two blocks per
 # plane, the second partly filled), hyp above HYP_TILE and no multiple of it
 SEEDS = {
@@ -52,71 +47,24 @@ EDGE_SEEDS = {
 EDGE_SHAPES = tuple(sorted(EDGE_SEEDS))
 
 
-def solvers(sets=None):
-    """GeometrySolvers with ``_minimal_sets`` overridden on the instance to return ``sets`` [B,hyp,8]."""
-    from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers
-    m = GeometrySolvers()
-    if sets is not None:
-        m.ransac_iters = int(sets.shape[1])
-        m._minimal_sets = lambda b, n, k, device: sets.to(device).long()
-    return m
-
-
 def build(seed, B, H, W, k, num, hyp, noisy):
-    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them.  ``disp_t``: the depth map the flows
-    were rendered from (what the model-level tests hand the draw as the disparity)."""
-    rng = np.random.default_rng(seed)
-    K = np.zeros((B, 3, 3))
-    flows = np.zeros((2, B, 2, H, W))
+    """The tensors of a case (RC.scene; no conditions checked) with ``F_true`` [2B,3,3] and the poses ``T34`` [B,2,3,4], float64."""
+    case, K, pose = RC.scene(seed, B, H, W, k, num, hyp, noisy, 8)
     F_true = np.zeros((2, B, 3, 3))
-    pose = np.zeros((B, 2, 3, 4))
-    depths = np.zeros((B, 1, H, W))
-    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
     for b in range(B):
-        f = 0.9 * W * rng.uniform(0.95, 1.05)
-        K[b] = [[f, 0, (W - 1) / 2.0 + rng.uniform(-0.5, 0.5)], [0, f * rng.uniform(0.97, 1.03), (H - 1) / 2.0 + rng.uniform(-0.5, 0.5)],
-                [0, 0, 1]]
-        depth = _smooth(rng, H, W, 2.0, 20.0)
-        depths[b, 0] = depth
         Ki = np.linalg.inv(K[b])
-        X = depth[None] * np.einsum("ij,jhw->ihw", Ki, np.stack([xs, ys, np.ones_like(xs)]))
         for d in range(2):
-            sign = rng.choice([-1.0, 1.0], 2)
-            t = np.array([sign[0] * rng.uniform(1.0, 1.4), sign[1] * rng.uniform(0.7, 1.0), rng.uniform(-0.3, 0.3)])
-            R = _rotation(rng.uniform(-0.02, 0.02, 3))
-            pose[b, d, :, :3], pose[b, d, :, 3] = R, t
-            p = np.einsum("ij,jhw->ihw", K[b] @ R, X) + (K[b] @ t)[:, None, None]
-            u, v = p[0] / p[2] - xs, p[1] / p[2] - ys
-            if noisy:
-                u = u + NOISE_PX * rng.standard_normal((H, W))
-                v = v + NOISE_PX * rng.standard_normal((H, W))
-            out = rng.random((H, W)) < OUTLIER_SHARE
-            u = np.where(out, u + rng.choice([-1.0, 1.0], (H, W)) * rng.uniform(3.0, 8.0, (H, W)), u)
-            v = np.where(out, v + rng.choice([-1.0, 1.0], (H, W)) * rng.uniform(3.0, 8.0, (H, W)), v)
-            flows[d, b, 0], flows[d, b, 1] = u, v
+            Rm, t = np.ascontiguousarray(pose[d, b, :, :3]), pose[d, b, :, 3]
             tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
-            Ft = Ki.T @ (tx @ R) @ Ki
+            Ft = Ki.T @ (tx @ Rm) @ Ki
             F_true[d, b] = Ft / Ft[2, 2]
-    idx = np.stack([np.sort(rng.choice(H * W, k, replace=False)) for _ in range(2 * B)]).astype(np.int32)
-    pick = rng.permutation(k)[:num].astype(np.int64)
-    sets = np.stack([np.stack([rng.choice(num, 8, replace=False) for _ in range(hyp)]) for _ in range(B)]).astype(np.int32)
-    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.float32)))   # noqa: E731
-    K32 = f32(K)
-    return dict(B=B, H=H, W=W, k=k, num=num, hyp=hyp, noisy=noisy, seed=seed, K=K32, K_inv=torch.inverse(K32.double()).float(),
-                flow_bwd=f32(flows[0]), flow_fwd=f32(flows[1]), disp_t=f32(depths), idx=torch.from_numpy(idx),
-                pick=torch.from_numpy(pick), sets=torch.from_numpy(sets), F_true=torch.from_numpy(F_true).reshape(2 * B, 3, 3), T34=torch.from_numpy(pose))
+    case.update(F_true=torch.from_numpy(F_true).reshape(2 * B, 3, 3), T34=torch.from_numpy(np.ascontiguousarray(pose.transpose(1, 0, 2, 3))))
+    return case
 
 
 def matches_of(case, flow_bwd=None, flow_fwd=None):
     """[2B,4,num] fp32: (x, y, x + u, y + v) of pixel idx[p][pick[j]], the sums in fp32 -- what sample_match gathers."""
-    B, H, W = case["B"], case["H"], case["W"]
-    out = []
-    for d, flow in enumerate((case["flow_bwd"] if flow_bwd is None else flow_bwd, case["flow_fwd"] if flow_fwd is None else flow_fwd)):
-        pix = case["idx"][d * B:(d + 1) * B].long()[:, case["pick"]]
-        x, y = (pix % W).float(), torch.div(pix, W, rounding_mode="floor").float()
-        uv = torch.gather(flow.reshape(B, 2, H * W), 2, pix.unsqueeze(1).expand(-1, 2, -1))
-        out.append(torch.stack([x, y, x + uv[:, 0], y + uv[:, 1]], 1))
-    return torch.cat(out, 0)
+    return torch.cat([torch.stack([x, y, x + u, y + v], 1) for _, x, y, u, v in RC.gathered(case, flow_bwd, flow_fwd)], 0)
 
 
 def normal_matrix(m, w):
@@ -136,12 +84,8 @@ def composition(matches, sets, thresh=THRESH):
     w1, w2 [2B,n] (after the fall-backs), n1raw / n2raw (before them), e1 (the first refit's residuals), e2 (the second's, not
     used by the estimate), F [2B,3,3] float64 scaled.
 
-    Each direction goes through on its own, B planes at a time, as ``compute_fundmental_mat`` is called: a batched ``eigh`` /
-    ``svd`` / ``bmm`` may round differently at another batch size (seen at B = 1 and B = 3 on another host), and the equality
-    with the class's own result that ``make_case`` asserts is one of bits."""
-    B = sets.shape[0]
-    halves = [_composition(matches[d * B:(d + 1) * B], sets, thresh) for d in range(2)]
-    return {k: torch.cat([h[k] for h in halves], 0) for k in halves[0]}
+    Each direction goes through on its own, as ``compute_fundmental_mat`` is called (RC.per_direction)."""
+    return RC.per_direction(lambda m: _composition(m, sets, thresh), sets.shape[0], matches)
 
 
 def _composition(matches, sets, thresh):
@@ -185,17 +129,11 @@ def conditions(case):
     c = composition(m32, case["sets"])
     s = solvers(case["sets"])
     F_api = torch.cat([s.compute_fundmental_mat(m32[:B].double()), s.compute_fundmental_mat(m32[B:].double())], 0)
-    t = THRESH * THRESH
-    finite = lambda e: e[torch.isfinite(e)]   # noqa: E731
-    margin = min(float(((finite(e) - t).abs() / t).min()) for e in (c["err"], c["e1"], c["e2"]))
-    inl = c["err"] <= t
-    top = c["counts"] == c["counts"].max(1, keepdim=True)[0]
-    win = torch.gather(inl, 1, c["best"].view(-1, 1, 1).expand(-1, 1, inl.shape[2]))
-    same = bool(((inl == win) | ~top.unsqueeze(2)).all())
-    ev = torch.linalg.eigvalsh(normal_matrix(m32.double(), c["w2"]))
-    return dict(comp=c, api_equal=torch.equal(F_api, c["F"]), margin=margin, same_set=same,
-                consensus=int(min(c["n1raw"].min(), c["n2raw"].min())), gap=float((ev[:, 1] / ev[:, 0].clamp_min(1e-300)).min()),
-                sep=float(((ev[:, 1] - ev[:, 0]) / ev[:, 8]).min()), matches=m32)
+    margin = min(rel_margin(c[k]) for k in ("err", "e1", "e2"))
+    gap, sep = isolation(normal_matrix(m32.double(), c["w2"]))
+    return dict(comp=c, api_equal=torch.equal(F_api, c["F"]), margin=margin,
+                same_set=RC.same_set(c["err"] <= THRESH * THRESH, c["counts"], c["best"]), consensus=RC.consensus(c),
+                gap=float(gap.min()), sep=float(sep.min()), matches=m32)
 
 
 def well_conditioned(f, fallback=False):
@@ -207,24 +145,16 @@ def well_conditioned(f, fallback=False):
 def find_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, fallback=False):
     """The first seed from ``start`` whose case meets the conditions (run once on the CPU; the result goes into SEEDS or
     EDGE_SEEDS)."""
-    for seed in range(start, start + tries):
-        if well_conditioned(conditions(build(seed, B, H, W, k, num, hyp, noisy)), fallback):
-            return seed
-    raise RuntimeError("no seed found")
+    return RC.find_seed(lambda seed: build(seed, B, H, W, k, num, hyp, noisy), conditions, lambda f, case: well_conditioned(f, fallback),
+                       start, tries)
 
 
 def _checked(case, fallback=False):
     f = conditions(case)
-    assert f["api_equal"], "the restated composition is not compute_fundmental_mat"
-    assert f["margin"] >= MARGIN, "a residual within a relative %g of the threshold (%g)" % (MARGIN, f["margin"])
-    assert f["same_set"], "two hypotheses reach the maximum count with different inlier sets"
-    if fallback:
-        assert f["consensus"] < 8, "no plane falls back (smallest consensus %d)" % f["consensus"]
-    else:
-        assert f["consensus"] >= 8, "a consensus of %d" % f["consensus"]
-    assert f["gap"] >= GAP and f["sep"] >= 1e-7, "the null direction of the final normal matrix is not isolated (%g, %g)" % (f["gap"], f["sep"])
-    case.update(comp=f["comp"], matches=f["matches"], figures={k: v for k, v in f.items() if k not in ("comp", "matches")})
-    return case
+    falls = (f["consensus"] < 8, "no plane falls back (smallest consensus %d)" % f["consensus"])
+    return RC.checked(case, f, ("comp", "matches"), RC.case_checks(f, "compute_fundmental_mat") + [
+        falls if fallback else (f["consensus"] >= 8, "a consensus of %d" % f["consensus"]),
+        (f["gap"] >= GAP and f["sep"] >= 1e-7, "the null direction of the final normal matrix is not isolated (%g, %g)" % (f["gap"], f["sep"]))])
 
 
 @functools.lru_cache(maxsize=None)
@@ -266,12 +196,23 @@ def reference_spread(case):
     return float((svd_route_F(case) - ref).abs().max() / ref.abs().max())
 
 
-def pose_vectors(case, seed=0):
-    """A pose [B,2,6] near nothing in particular (the loss tests need a generic E, not the true one)."""
-    g = torch.Generator().manual_seed(77 + seed)
-    p = torch.randn(case["B"], 2, 6, generator=g) * 0.1
-    p[:, :, :3] += torch.tensor([1.0, 0.5, 0.1])
-    return p
+def loss_reference(F64, K, K_inv, pose, weights, dtype=torch.float64):
+    """float64: compute_eight_point_loss's expression per direction and sample, fed the given F, on the oracle's [t]x R; the
+    gradient of sum(weights * loss) with respect to the pose and to E.  ``dtype`` = float32: the same expression in fp32 (its
+    distance to the float64 one is what fp32 alone costs)."""
+    from oracle import loss_stack_oracle as O
+    import torch.nn.functional as F
+    B = K.shape[0]
+    pose = pose.to(dtype).requires_grad_(True)
+    E = torch.stack([O.compute_essential_matrix(pose[:, d]) for d in range(2)], 1)          # [B,2,3,3]
+    E.retain_grad()
+    Kt_inv = torch.inverse(K.double().permute(0, 2, 1)).to(dtype)
+    loss = 0
+    for d in range(2):
+        pred = Kt_inv.bmm(E[:, d].bmm(K_inv.to(dtype)))
+        loss = loss + F.smooth_l1_loss(pred, F64[d * B:(d + 1) * B].to(dtype), reduction="none").mean((1, 2))
+    (loss * weights.to(dtype)).sum().backward()
+    return loss.detach(), pose.grad, E.grad.reshape(2 * B, 3, 3)
 
 
 # ------------------------------------------------------------------------------------------------ the product's own draws
@@ -283,12 +224,10 @@ def pose_vectors(case, seed=0):
 # well-defined and 4 ill-defined slots, no residual of a well-defined slot or of a refit lies within MARGIN of the threshold, every
 # consensus has 8 members and the null direction of BOTH refits' normal matrices is isolated (``continued`` needs the first's as
 # well).  Steering the search only, NOT asserted: the reference's winner is well-defined and leads every ill-defined slot's count by
-# LEAD.  Those counts rest on vectors that the host's LAPACK picks by rounding (one host polls 8 below the winner where another
-# polls 6), so the figure is printed by the CPU test and LEAD is twice the 8 first asked for; what is asserted in its place is the
-# composition without the ill-defined slots (``without_ill_defined``), which every host agrees on and the kernel must reproduce.
+# LEAD (tests/ransac_cases.py); the figure is printed by the CPU test, and what is asserted in its place is the composition
+# without the ill-defined slots (``without_ill_defined``), which every host agrees on and the kernel must reproduce.
 # The last shape has hyp = 70: the hypothesis kernel's second and third block and the scoring kernel's second LDS round, for the
-# slots 0, 31, 32, 63, 64 and 69 of the isolation tests.
-LEAD = 16
+# slots 0, 31, 32, 63, 64 and 69 of the isolation tests (CRAFTED_SLOTS).
 DRAWN_SEEDS = {
     (2, 12, 20, 72, 64, 64, True): 11,
     (3, 13, 19, 72, 70, 33, True): 162,
@@ -300,29 +239,7 @@ DRAWN_SHAPES = tuple(sorted(DRAWN_SEEDS))
 # than ``eigh`` does, whose second refit keeps 9 matches of fewer than 8 distinct pixels (its normal matrix has no isolated null
 # direction: inconclusive); at 3 the kernel's own winners all have 8 distinct pixels (ill-defined by the isolation figures only)
 ILL_WINNER = ((2, 12, 20, 72, 64, 64, True), 5)
-# the slots the isolation tests overwrite: the first and last thread of the hypothesis kernel's first two blocks (32 threads
-# each), the first thread of the third and the last slot; 63 / 64 are also the end of the scoring kernel's first LDS round and
-# the start of its second
-CRAFTED_SLOTS = (0, 31, 32, 63, 64, 69)
-
-
-def build_drawn(seed, B, H, W, k, num, hyp, noisy):
-    """``build`` with ``pick`` drawn with replacement from a generator seeded with ``seed`` and ``sets`` the class's own
-    ``_minimal_sets(B, num, 8, "cpu")`` at ``ransac_iters = hyp`` (a function of the shape alone)."""
-    case = build(seed, B, H, W, k, num, hyp, noisy)
-    g = torch.Generator().manual_seed(seed)
-    case["pick"] = torch.randint(0, k, (num,), generator=g)
-    m = solvers()
-    m.ransac_iters = hyp
-    case["sets"] = m._minimal_sets(B, num, 8, "cpu").to(torch.int32)
-    return case
-
-
-def distinct_pixels(case, sets=None):
-    """bool [B,hyp]: the 8 matches of the set are 8 distinct pixels (``idx`` is duplicate-free, so of either direction's plane)."""
-    sets = case["sets"] if sets is None else sets
-    px = case["pick"][sets.long()].sort(2)[0]
-    return (px[:, :, 1:] != px[:, :, :-1]).all(2)
+build_drawn = functools.partial(RC.build_drawn, build, 8)          # (seed, B, H, W, k, num, hyp, noisy)
 
 
 def isolation(M):
@@ -347,24 +264,14 @@ def well_defined(case, sets=None):
     return iso & torch.cat([distinct_pixels(case, sets)] * 2, 0)
 
 
-def rel_margin(e, keep=None, thresh=THRESH):
-    """The smallest relative distance of a finite residual to the threshold (inf if there is none); ``keep``: a mask."""
-    t = thresh * thresh
-    e = e if keep is None else e[keep]
-    e = e[torch.isfinite(e)]
-    return float(((e - t).abs() / t).min()) if e.numel() else float("inf")
-
-
 def continued(case, Fh):
     """The float64 composition CONTINUED FROM A GIVEN HYPOTHESIS TABLE Fh [2B,hyp,3,3] (float64; the kernel's own, say): every
     hypothesis recounted from that table, argmax (ties: the lowest index), w1, the fall-back, the refit, w2, its fall-back, the
     second refit -- ``_continue``, the very code ``composition`` runs after its own table.  Added: ``margin`` (the smallest
     relative distance to the threshold of any residual it used: every recount and both refits'), and ``gap1`` / ``sep1`` /
     ``gap2`` / ``sep2`` [2B], the isolation figures of the two refits' normal matrices."""
-    B = case["B"]
     m = matches_of(case).double()
-    halves = [_continue(m[d * B:(d + 1) * B], Fh[d * B:(d + 1) * B].double(), THRESH) for d in range(2)]
-    c = {k: torch.cat([h[k] for h in halves], 0) for k in halves[0]}
+    c = RC.per_direction(lambda mh, Fhh: _continue(mh, Fhh, THRESH), case["B"], m, Fh.double())
     c["margin"] = min(rel_margin(c[k]) for k in ("err", "e1", "e2"))
     c["gap1"], c["sep1"] = isolation(normal_matrix(m, c["w1"]))
     c["gap2"], c["sep2"] = isolation(normal_matrix(m, c["w2"]))
@@ -385,58 +292,39 @@ def drawn_conditions(case):
     s = solvers(case["sets"])
     F_api = torch.cat([s.compute_fundmental_mat(m32[:B].double()), s.compute_fundmental_mat(m32[B:].double())], 0)
     wd = well_defined(case)
-    top = c["counts"].max(1)[0]
-    ill_top = torch.where(wd, torch.full_like(c["counts"], -10 ** 6), c["counts"]).max(1)[0]
     margin = min(rel_margin(c["err"], wd.unsqueeze(2).expand_as(c["err"])), rel_margin(c["e1"]), rel_margin(c["e2"]))
     gap, sep = (torch.minimum(a, b) for a, b in zip(isolation(normal_matrix(m32.double(), c["w1"])),
                                                     isolation(normal_matrix(m32.double(), c["w2"]))))
-    return dict(comp=c, matches=m32, well=wd, api_equal=torch.equal(F_api, c["F"]), n_well=int(wd.sum(1).min()),
-                n_ill=int((~wd).sum(1).min()), margin=margin, winner_well=torch.gather(wd, 1, c["best"].view(-1, 1)).squeeze(1),
-                lead=int((top - ill_top).min()), consensus=int(min(c["n1raw"].min(), c["n2raw"].min())), gap=float(gap.min()),
-                sep=float(sep.min()))
+    return dict(comp=c, matches=m32, well=wd, api_equal=torch.equal(F_api, c["F"]), margin=margin, gap=float(gap.min()),
+                sep=float(sep.min()), **RC.drawn_figures(wd, c))
 
 
 def drawn_ok(f, case, ill_winner=False):
     ok = f["api_equal"] and 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4 and f["margin"] >= MARGIN and f["consensus"] >= 8
-    ok = ok and f["gap"] >= GAP and f["sep"] >= 1e-7
-    if ill_winner:
-        return ok and not bool(f["winner_well"].all())
-    return ok and bool(f["winner_well"].all()) and f["lead"] >= LEAD
+    return RC.drawn_accept(ok and f["gap"] >= GAP and f["sep"] >= 1e-7, f, ill_winner)
 
 
 def find_drawn_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, ill_winner=False):
     """The first seed from ``start`` whose drawn case meets the conditions (run once on the CPU; the result goes into DRAWN_SEEDS
     or ILL_WINNER)."""
-    for seed in range(start, start + tries):
-        case = build_drawn(seed, B, H, W, k, num, hyp, noisy)
-        if drawn_ok(drawn_conditions(case), case, ill_winner):
-            return seed
-    raise RuntimeError("no seed found")
+    return RC.find_seed(lambda seed: build_drawn(seed, B, H, W, k, num, hyp, noisy), drawn_conditions,
+                       lambda f, case: drawn_ok(f, case, ill_winner), start, tries)
 
 
 def without_ill_defined(case, comp, well):
-    """The composition with the ill-defined slots refused a vote: ``continued`` from the reference's table with those slots made
-    non-finite.  Nothing in it rests on a vector that rounding picked, so it is the same on every host."""
-    Fh = comp["Fh"].clone()
-    Fh[~well] = float("nan")
-    return continued(case, Fh)
+    """RC.without_ill_defined: ``continued`` from the reference's table with the ill-defined slots made non-finite."""
+    return RC.without_ill_defined(continued, case, well, comp["Fh"])
 
 
 def _drawn_checked(case, with_ref=True):
-    """Asserts what does not depend on the host: the figures of the well-defined slots and of the refits.  ``winner_well`` and
-    ``lead`` rest on the counts of ill-defined slots, which the host's LAPACK decides (one host polls 8 below the winner where
-    another polls 6): they steer ``find_drawn_seed`` and are kept in ``figures``, not asserted.  ``ref``: the composition without
-    the ill-defined slots -- what the kernel must arrive at whenever none of its own ill-defined slots out-polls the winner."""
+    """RC.drawn_checks and the isolation of both refits' null directions; ``winner_well`` and ``lead`` are kept in ``figures``, not
+    asserted.  ``ref``: the composition without the ill-defined slots."""
     f = drawn_conditions(case)
-    assert f["api_equal"], "the restated composition is not compute_fundmental_mat"
-    assert 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4, "a plane with %d well-defined, %d ill-defined slots" % (f["n_well"], f["n_ill"])
-    assert f["margin"] >= MARGIN, "a residual within a relative %g of the threshold (%g)" % (MARGIN, f["margin"])
-    assert f["consensus"] >= 8, "a consensus of %d" % f["consensus"]
-    assert f["gap"] >= GAP and f["sep"] >= 1e-7, "the null direction of a refit's normal matrix is not isolated (%g, %g)" % (f["gap"], f["sep"])
-    case.update(comp=f["comp"], matches=f["matches"], well=f["well"], figures={k: v for k, v in f.items() if k not in ("comp", "matches", "well")})
+    RC.checked(case, f, ("comp", "matches", "well"), RC.drawn_checks(f, case, 8, "compute_fundmental_mat") + [
+        (f["gap"] >= GAP and f["sep"] >= 1e-7, "the null direction of a refit's normal matrix is not isolated (%g, %g)" % (f["gap"], f["sep"]))])
     if with_ref:
         case["ref"] = without_ill_defined(case, f["comp"], f["well"])
-        assert conclusive(case["ref"]) and int(min(case["ref"]["n1raw"].min(), case["ref"]["n2raw"].min())) >= 8
+        assert conclusive(case["ref"]) and RC.consensus(case["ref"]) >= 8
     return case
 
 

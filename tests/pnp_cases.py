@@ -1,11 +1,7 @@
 """Inputs of the PnP-term tests (tests/test_pnp_cpu.py, tests/test_hip_pnp.py): a helper, not a conftest.
 
-A case is the tiny two-view problem of tests/eight_point_cases.py -- a smooth non-planar depth in [2, 20], per sample its own
-``K``, per sample and direction a pose with a long baseline and a small rotation, the exact rigid flow of that depth, 30 % of the
-pixels with their flow replaced by gross outliers, optionally 0.02 px of Gaussian noise on the rest; a pixel-ordered ``idx``, a
-seeded duplicate-free ``pick``, seeded duplicate-free ``sets`` (of 6) -- which also keeps the depth map the flows were rendered
-from (the operator's ``disp_t``: the reference passes the raw disparity as "depth") and the analytic pose (T, axis-angle) of
-every plane.
+A case is the two-view problem of tests/ransac_cases.py with sets of 6; the test uses its depth map (the operator's ``disp_t``:
+the reference passes the raw disparity as "depth") and the analytic pose (T, axis-angle) of every plane, ``P_true``.
 
 ``points_of`` forms what the operator forms: the point ``K_inv (x, y, 1) depth`` in float64 from the fp32 inputs, and the matched
 pixel ``(x + u, y + v)`` with the sums in fp32.  ``composition`` restates the robust branch of ``GeometrySolvers.pnp`` from the
@@ -21,18 +17,15 @@ excluded:
 best count stays below 6 on some plane, so that the "all matches" fall-back runs: (a)-(d) only."""
 import functools
 
-import numpy as np
 import torch
 
-from tests.triangle_cases import _rotation, _smooth
+from tests import ransac_cases as RC
+from tests.ransac_cases import (CRAFTED_SLOTS, HYP_TILE, LEAD, MARGIN, MATCH_TILE, NOISE_PX, OUTLIER_SHARE, WEIGHTS_OF,  # noqa: F401
+                                distinct_pixels, pose_vectors, solvers)
 
 THRESH = 1.0
 ITERS = 20
-MARGIN = 1e-6
-NOISE_PX = 0.02
-OUTLIER_SHARE = 0.3
-# the scoring kernel's tiles (csrc/ops_pnp.hip): PNP_MATCH_TILE matches per block, PNP_HYP_TILE hypotheses per LDS round
-MATCH_TILE, HYP_TILE = 256, 64
+rel_margin = functools.partial(RC.rel_margin, thresh=THRESH)
 # (B, H, W, k, num, hyp, noisy) -> seed; found with find_seed(*key).  The last shape: num above MATCH_TILE (two blocks per
 # plane, the second partly filled), hyp above HYP_TILE and no multiple of it
 SEEDS = {
@@ -59,58 +52,14 @@ EDGE_SEEDS = {
 EDGE_SHAPES = tuple(sorted(EDGE_SEEDS))
 
 
-def solvers(sets=None):
-    """GeometrySolvers with ``_minimal_sets`` overridden on the instance to return ``sets`` [b,hyp,6]."""
-    from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers
-    m = GeometrySolvers()
-    if sets is not None:
-        m.ransac_iters = int(sets.shape[1])
-        m._minimal_sets = lambda b, n, k, device: sets.to(device).long()
-    return m
-
-
 def build(seed, B, H, W, k, num, hyp, noisy, rot=0.02):
-    """The tensors of a case (no conditions checked): fp32 values, as the operator takes them.  ``rot``: the range of each of the
+    """The tensors of a case (RC.scene; no conditions checked) with ``P_true`` [2B,6] float64.  ``rot``: the range of each of the
     pose's three rotation angles (the default draws today's cases bit for bit)."""
     from unsupervised_depth_opticalflow_egomotion_amd.geometry_solvers import GeometrySolvers as S
-    rng = np.random.default_rng(seed)
-    K = np.zeros((B, 3, 3))
-    flows = np.zeros((2, B, 2, H, W))
-    depths = np.zeros((B, 1, H, W))
-    pose = np.zeros((2, B, 3, 4))
-    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
-    for b in range(B):
-        f = 0.9 * W * rng.uniform(0.95, 1.05)
-        K[b] = [[f, 0, (W - 1) / 2.0 + rng.uniform(-0.5, 0.5)], [0, f * rng.uniform(0.97, 1.03), (H - 1) / 2.0 + rng.uniform(-0.5, 0.5)],
-                [0, 0, 1]]
-        depth = _smooth(rng, H, W, 2.0, 20.0)
-        depths[b, 0] = depth
-        Ki = np.linalg.inv(K[b])
-        X = depth[None] * np.einsum("ij,jhw->ihw", Ki, np.stack([xs, ys, np.ones_like(xs)]))
-        for d in range(2):
-            sign = rng.choice([-1.0, 1.0], 2)
-            t = np.array([sign[0] * rng.uniform(1.0, 1.4), sign[1] * rng.uniform(0.7, 1.0), rng.uniform(-0.3, 0.3)])
-            R = _rotation(rng.uniform(-rot, rot, 3))
-            pose[d, b, :, :3], pose[d, b, :, 3] = R, t
-            p = np.einsum("ij,jhw->ihw", K[b] @ R, X) + (K[b] @ t)[:, None, None]
-            u, v = p[0] / p[2] - xs, p[1] / p[2] - ys
-            if noisy:
-                u = u + NOISE_PX * rng.standard_normal((H, W))
-                v = v + NOISE_PX * rng.standard_normal((H, W))
-            out = rng.random((H, W)) < OUTLIER_SHARE
-            u = np.where(out, u + rng.choice([-1.0, 1.0], (H, W)) * rng.uniform(3.0, 8.0, (H, W)), u)
-            v = np.where(out, v + rng.choice([-1.0, 1.0], (H, W)) * rng.uniform(3.0, 8.0, (H, W)), v)
-            flows[d, b, 0], flows[d, b, 1] = u, v
-    idx = np.stack([np.sort(rng.choice(H * W, k, replace=False)) for _ in range(2 * B)]).astype(np.int32)
-    pick = rng.permutation(k)[:num].astype(np.int64)
-    sets = np.stack([np.stack([rng.choice(num, 6, replace=False) for _ in range(hyp)]) for _ in range(B)]).astype(np.int32)
-    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.float32)))   # noqa: E731
-    K32 = f32(K)
+    case, _, pose = RC.scene(seed, B, H, W, k, num, hyp, noisy, 6, rot)
     T34 = torch.from_numpy(pose).reshape(2 * B, 3, 4)
-    P_true = torch.cat([T34[:, :, 3], S._so3_log(T34[:, :, :3].contiguous())], 1)
-    return dict(B=B, H=H, W=W, k=k, num=num, hyp=hyp, noisy=noisy, seed=seed, K=K32, K_inv=torch.inverse(K32.double()).float(),
-                flow_bwd=f32(flows[0]), flow_fwd=f32(flows[1]), disp_t=f32(depths), idx=torch.from_numpy(idx),
-                pick=torch.from_numpy(pick), sets=torch.from_numpy(sets), P_true=P_true)
+    case["P_true"] = torch.cat([T34[:, :, 3], S._so3_log(T34[:, :, :3].contiguous())], 1)
+    return case
 
 
 def points_of(case, flow_bwd=None, flow_fwd=None, disp_t=None):
@@ -120,11 +69,8 @@ def points_of(case, flow_bwd=None, flow_fwd=None, disp_t=None):
     disp = (case["disp_t"] if disp_t is None else disp_t).reshape(B, H * W)
     Ki = case["K_inv"].double()
     xs, Xs = [], []
-    for d, flow in enumerate((case["flow_bwd"] if flow_bwd is None else flow_bwd, case["flow_fwd"] if flow_fwd is None else flow_fwd)):
-        pix = case["idx"][d * B:(d + 1) * B].long()[:, case["pick"]]
-        x, y = (pix % W).float(), torch.div(pix, W, rounding_mode="floor").float()
-        uv = torch.gather(flow.reshape(B, 2, H * W), 2, pix.unsqueeze(1).expand(-1, 2, -1))
-        xs.append(torch.stack([x + uv[:, 0], y + uv[:, 1]], 2).double())
+    for pix, x, y, u, v in RC.gathered(case, flow_bwd, flow_fwd):
+        xs.append(torch.stack([x + u, y + v], 2).double())
         xd, yd = x.double(), y.double()
         ray = torch.stack([(Ki[:, i, 0:1] * xd + Ki[:, i, 1:2] * yd) + Ki[:, i, 2:3] for i in range(3)], 2)      # [B,num,3]
         Xs.append(ray * torch.gather(disp, 1, pix).double().unsqueeze(2))
@@ -241,19 +187,14 @@ def conditions(case):
         s = solvers(case["sets"][b].unsqueeze(0).expand(2, -1, -1))
         api.append(s.pnp(x[b::B], X[b::B], case["K"][b].double(), iterations=ITERS))
     P_api = torch.stack([api[p % B][p // B] for p in range(2 * B)], 0)
-    t = THRESH * THRESH
-    finite = lambda e: e[torch.isfinite(e)]   # noqa: E731
-    margin = min(float(((finite(e) - t).abs() / t).min()) for e in (c["err"], c["e1"], c["e2"]))
-    zmargin = min(float(finite(z).abs().min()) for z in (c["zh"], c["z1"], c["z2"]))
+    margin = min(rel_margin(c[k]) for k in ("err", "e1", "e2"))
+    zmargin = min(abs_margin(c[k]) for k in ("zh", "z1", "z2"))
     votes = []
     for b in range(B):
         v = composition(x[b::B], X[b::B], case["K"][b], case["sets"][b], route="eigh", votes_only=True)
         votes.append(torch.equal(v["inl"], torch.stack([c["inl"][b], c["inl"][B + b]], 0)))
-    top = c["counts"] == c["counts"].max(1, keepdim=True)[0]
-    win = torch.gather(c["inl"], 1, c["best"].view(-1, 1, 1).expand(-1, 1, c["inl"].shape[2]))
-    same = bool(((c["inl"] == win) | ~top.unsqueeze(2)).all())
-    return dict(comp=c, api_equal=torch.equal(P_api, c["P"]), margin=margin, zmargin=zmargin, route_free=all(votes), same_set=same,
-                consensus=int(min(c["n1raw"].min(), c["n2raw"].min())), best_min=int(c["n1raw"].min()), x=x, X=X)
+    return dict(comp=c, api_equal=torch.equal(P_api, c["P"]), margin=margin, zmargin=zmargin, route_free=all(votes),
+                same_set=RC.same_set(c["inl"], c["counts"], c["best"]), consensus=RC.consensus(c), best_min=int(c["n1raw"].min()), x=x, X=X)
 
 
 def well_conditioned(f, fallback=False):
@@ -264,25 +205,17 @@ def well_conditioned(f, fallback=False):
 def find_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, fallback=False, rot=0.02):
     """The first seed from ``start`` whose case meets the conditions (run once on the CPU; the result goes into SEEDS / FALLBACK /
     EDGE_SEEDS)."""
-    for seed in range(start, start + tries):
-        if well_conditioned(conditions(build(seed, B, H, W, k, num, hyp, noisy, rot)), fallback):
-            return seed
-    raise RuntimeError("no seed found")
+    return RC.find_seed(lambda seed: build(seed, B, H, W, k, num, hyp, noisy, rot), conditions,
+                        lambda f, case: well_conditioned(f, fallback), start, tries)
 
 
 def _checked(case, fallback):
     f = conditions(case)
-    assert f["api_equal"], "the restated composition is not GeometrySolvers.pnp"
-    assert f["margin"] >= MARGIN, "a residual within a relative %g of the threshold (%g)" % (MARGIN, f["margin"])
-    assert f["zmargin"] >= MARGIN, "a depth within %g of zero (%g)" % (MARGIN, f["zmargin"])
-    assert f["route_free"], "the votes depend on the route to the DLT's null vector"
-    assert f["same_set"], "two hypotheses reach the maximum count with different inlier sets"
-    if fallback:
-        assert f["best_min"] < 6, "no plane needs the fall-back (smallest best count %d)" % f["best_min"]
-    else:
-        assert f["consensus"] >= 6, "a consensus of %d" % f["consensus"]
-    case.update(comp=f["comp"], x=f["x"], X=f["X"], figures={k: v for k, v in f.items() if k not in ("comp", "x", "X")})
-    return case
+    falls = (f["best_min"] < 6, "no plane needs the fall-back (smallest best count %d)" % f["best_min"])
+    return RC.checked(case, f, ("comp", "x", "X"), RC.case_checks(f, "GeometrySolvers.pnp") + [
+        (f["zmargin"] >= MARGIN, "a depth within %g of zero (%g)" % (MARGIN, f["zmargin"])),
+        (f["route_free"], "the votes depend on the route to the DLT's null vector"),
+        falls if fallback else (f["consensus"] >= 6, "a consensus of %d" % f["consensus"])])
 
 
 @functools.lru_cache(maxsize=None)
@@ -304,12 +237,19 @@ def make_edge_case(name):
     return _checked(build(seed, *key, rot=rot), fallback)
 
 
-def pose_vectors(case, seed=0, scale=1.0):
-    """A pose [B,2,6] near nothing in particular (the loss tests need a generic pose, not the true one)."""
-    g = torch.Generator().manual_seed(77 + seed)
-    p = torch.randn(case["B"], 2, 6, generator=g) * 0.1
-    p[:, :, :3] += torch.tensor([1.0, 0.5, 0.1])
-    return p * scale
+def loss_reference(P64, pose, beta, weights, dtype=torch.float64):
+    """float64: compute_pnp_loss's expression per direction and sample, fed the given pose estimate; the gradient of
+    sum(weights * loss) with respect to the pose vector.  ``dtype`` = float32: the same expression in fp32."""
+    import torch.nn.functional as F
+    B = pose.shape[0]
+    pose = pose.to(dtype).requires_grad_(True)
+    loss = 0
+    for d in range(2):
+        est = P64[d * B:(d + 1) * B].to(dtype)
+        term = F.l1_loss(est[:, :3], pose[:, d, :3], reduction="none") + beta * F.l1_loss(est[:, 3:], pose[:, d, 3:], reduction="none")
+        loss = loss + term.mean(1)
+    (loss * weights.to(dtype)).sum().backward()
+    return loss.detach(), pose.grad
 
 
 # ------------------------------------------------------------------------------------------------ the product's own draws
@@ -327,7 +267,6 @@ def pose_vectors(case, seed=0, scale=1.0):
 # kernel's Jacobi -- the winner's count -- and, being the lower slot, is elected (the poses agree to 6.5e-10 all the same: its
 # inlier set is the winner's).
 GAP = 10.0
-LEAD = 16
 LM_COND = 1e-7       # smallest over largest eigenvalue of J^T J: a float64 solve leaves the step a relative 1e-9, below P_BOUND
 DRAWN_SEEDS = {
     (2, 12, 20, 72, 64, 64, True): 8,
@@ -339,27 +278,8 @@ DRAWN_SHAPES = tuple(sorted(DRAWN_SEEDS))
 # and 3 meet that too and were passed over after one run on the device: the kernel's own winners there all have 6 distinct pixels
 # (ill-defined by the isolation figures only), and the case is for a winner that repeats a match
 ILL_WINNER = ((2, 12, 20, 72, 64, 64, True), 5)
-CRAFTED_SLOTS = (0, 31, 32, 63, 64, 69)          # see tests/eight_point_cases.py
 COINCIDENT = (5, 50, 95, 140, 185, 230)          # the matches whose ``pick`` the fourth kind of crafted set moves onto one pixel
-
-
-def build_drawn(seed, B, H, W, k, num, hyp, noisy):
-    """``build`` with ``pick`` drawn with replacement from a generator seeded with ``seed`` and ``sets`` the class's own
-    ``_minimal_sets(B, num, 6, "cpu")`` at ``ransac_iters = hyp`` (a function of the shape alone)."""
-    case = build(seed, B, H, W, k, num, hyp, noisy)
-    g = torch.Generator().manual_seed(seed)
-    case["pick"] = torch.randint(0, k, (num,), generator=g)
-    m = solvers()
-    m.ransac_iters = hyp
-    case["sets"] = m._minimal_sets(B, num, 6, "cpu").to(torch.int32)
-    return case
-
-
-def distinct_pixels(case, sets=None):
-    """bool [B,hyp]: the 6 matches of the set are 6 distinct pixels (``idx`` is duplicate-free, so of either direction's plane)."""
-    sets = case["sets"] if sets is None else sets
-    px = case["pick"][sets.long()].sort(2)[0]
-    return (px[:, :, 1:] != px[:, :, :-1]).all(2)
+build_drawn = functools.partial(RC.build_drawn, build, 6)          # (seed, B, H, W, k, num, hyp, noisy)
 
 
 def _plane_sets(case, sets):
@@ -386,15 +306,8 @@ def well_defined(case, sets=None):
     return torch.stack(iso, 0) & torch.cat([distinct_pixels(case, sets)] * 2, 0)
 
 
-def rel_margin(e, keep=None, thresh=THRESH):
-    """The smallest relative distance of a finite residual to the threshold (inf if there is none); ``keep``: a mask."""
-    t = thresh * thresh
-    e = e if keep is None else e[keep]
-    e = e[torch.isfinite(e)]
-    return float(((e - t).abs() / t).min()) if e.numel() else float("inf")
-
-
 def abs_margin(z, keep=None):
+    """The smallest distance of a finite depth to zero (inf if there is none); ``keep``: a mask."""
     z = z if keep is None else z[keep]
     z = z[torch.isfinite(z)]
     return float(z.abs().min()) if z.numel() else float("inf")
@@ -465,59 +378,41 @@ def drawn_conditions(case):
         mine = torch.stack([c["inl"][b], c["inl"][B + b]], 0)
         well = torch.stack([wd[b], wd[B + b]], 0)
         votes.append(torch.equal(v["inl"][well], mine[well]))
-    top = c["counts"].max(1)[0]
-    ill_top = torch.where(wd, torch.full_like(c["counts"], -10 ** 6), c["counts"]).max(1)[0]
     cond = torch.cat([torch.minimum(lm_condition(x[p:p + 1], X[p:p + 1], case["K"][p % B], c["P"][p:p + 1], c["w1"][p:p + 1]),
                                     lm_condition(x[p:p + 1], X[p:p + 1], case["K"][p % B], c["P"][p:p + 1], c["w2"][p:p + 1]))
                       for p in range(2 * B)])
-    return dict(comp=c, x=x, X=X, well=wd, api_equal=torch.equal(P_api, c["P"]), n_well=int(wd.sum(1).min()), n_ill=int((~wd).sum(1).min()),
-                margin=margin, zmargin=zmargin, route_free=all(votes), winner_well=torch.gather(wd, 1, c["best"].view(-1, 1)).squeeze(1),
-                lead=int((top - ill_top).min()), consensus=int(min(c["n1raw"].min(), c["n2raw"].min())), cond=float(cond.min()))
+    return dict(comp=c, x=x, X=X, well=wd, api_equal=torch.equal(P_api, c["P"]), margin=margin, zmargin=zmargin, route_free=all(votes),
+                cond=float(cond.min()), **RC.drawn_figures(wd, c))
 
 
 def drawn_ok(f, case, ill_winner=False):
     ok = f["api_equal"] and 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4 and f["margin"] >= MARGIN and f["zmargin"] >= MARGIN
-    ok = ok and f["route_free"] and f["consensus"] >= 6 and f["cond"] >= LM_COND
-    if ill_winner:
-        return ok and not bool(f["winner_well"].all())
-    return ok and bool(f["winner_well"].all()) and f["lead"] >= LEAD
+    return RC.drawn_accept(ok and f["route_free"] and f["consensus"] >= 6 and f["cond"] >= LM_COND, f, ill_winner)
 
 
 def find_drawn_seed(B, H, W, k, num, hyp, noisy, start=0, tries=2000, ill_winner=False):
     """The first seed from ``start`` whose drawn case meets the conditions (run once on the CPU; the result goes into DRAWN_SEEDS
     or ILL_WINNER)."""
-    for seed in range(start, start + tries):
-        case = build_drawn(seed, B, H, W, k, num, hyp, noisy)
-        if drawn_ok(drawn_conditions(case), case, ill_winner):
-            return seed
-    raise RuntimeError("no seed found")
+    return RC.find_seed(lambda seed: build_drawn(seed, B, H, W, k, num, hyp, noisy), drawn_conditions,
+                        lambda f, case: drawn_ok(f, case, ill_winner), start, tries)
 
 
 def without_ill_defined(case, comp, well):
-    """The composition with the ill-defined slots refused a vote: ``continued`` from the reference's table with those slots made
-    non-finite.  Nothing in it rests on a vector that rounding picked, so it is the same on every host."""
-    Rh = comp["Rh"].clone()
-    Rh[~well] = float("nan")
-    return continued(case, Rh, comp["Th"])
+    """RC.without_ill_defined: ``continued`` from the reference's table with the ill-defined slots made non-finite."""
+    return RC.without_ill_defined(continued, case, well, comp["Rh"], comp["Th"])
 
 
 def _drawn_checked(case, with_ref=True):
-    """Asserts what does not depend on the host: the figures of the well-defined slots and of the refinements.  ``winner_well`` and
-    ``lead`` rest on the counts of ill-defined slots, which the host's LAPACK decides: they steer ``find_drawn_seed`` and are kept
-    in ``figures``, not asserted.  ``ref``: the composition without the ill-defined slots -- what the kernel must arrive at
-    whenever none of its own ill-defined slots out-polls the winner."""
+    """RC.drawn_checks and the term's own: depths, the route to the null vector, both refinements' conditioning; ``winner_well``
+    and ``lead`` are kept in ``figures``, not asserted.  ``ref``: the composition without the ill-defined slots."""
     f = drawn_conditions(case)
-    assert f["api_equal"], "the restated composition is not GeometrySolvers.pnp"
-    assert 4 * f["n_well"] >= case["hyp"] and f["n_ill"] >= 4, "a plane with %d well-defined, %d ill-defined slots" % (f["n_well"], f["n_ill"])
-    assert f["margin"] >= MARGIN, "a residual within a relative %g of the threshold (%g)" % (MARGIN, f["margin"])
-    assert f["zmargin"] >= MARGIN, "a depth within %g of zero (%g)" % (MARGIN, f["zmargin"])
-    assert f["route_free"], "a well-defined slot's votes depend on the route to the DLT's null vector"
-    assert f["consensus"] >= 6, "a consensus of %d" % f["consensus"]
-    assert f["cond"] >= LM_COND, "a refinement's normal matrix is ill conditioned (%g)" % f["cond"]
-    case.update(comp=f["comp"], x=f["x"], X=f["X"], well=f["well"], figures={k: v for k, v in f.items() if k not in ("comp", "x", "X", "well")})
+    RC.checked(case, f, ("comp", "x", "X", "well"), RC.drawn_checks(f, case, 6, "GeometrySolvers.pnp") + [
+        (f["zmargin"] >= MARGIN, "a depth within %g of zero (%g)" % (MARGIN, f["zmargin"])),
+        (f["route_free"], "a well-defined slot's votes depend on the route to the DLT's null vector"),
+        (f["cond"] >= LM_COND, "a refinement's normal matrix is ill conditioned (%g)" % f["cond"])])
     if with_ref:
         case["ref"] = without_ill_defined(case, f["comp"], f["well"])
-        assert conclusive(case["ref"]) and int(min(case["ref"]["n1raw"].min(), case["ref"]["n2raw"].min())) >= 6
+        assert conclusive(case["ref"]) and RC.consensus(case["ref"]) >= 6
     return case
 
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from tests import eight_point_cases as EC
+from tests import ransac_cases as RC
 
 
 @pytest.mark.parametrize("key", EC.SHAPES)
@@ -84,14 +85,6 @@ def test_the_header_declares_the_new_entries():
     assert lib.dfe_eight_point_ws_bytes(0, 8, 8) == 0
 
 
-def _crc(case, names):
-    import zlib
-    c = 0
-    for n in names:
-        c = zlib.crc32(case[n].contiguous().numpy().tobytes(), c)
-    return c
-
-
 def test_the_existing_tables_and_their_draws_are_unchanged():
     """SHAPES keeps its four keys in their places, and the generator-only tensors of every existing case (the camera matrices:
     the first draws; idx, pick and sets: the last) carry the checksums taken before the edge table existed."""
@@ -99,7 +92,7 @@ def test_the_existing_tables_and_their_draws_are_unchanged():
             (2, 13, 19, 72, 70, 33, True): (0, 3405646239), (2, 20, 24, 320, 300, 70, True): (1, 2126196865)}
     assert EC.SHAPES == tuple(sorted(want)) and EC.SEEDS == {k: v[0] for k, v in want.items()}
     for key, (seed, crc) in want.items():
-        assert _crc(EC.build(seed, *key), ("K", "idx", "pick", "sets")) == crc, key
+        assert RC.crc(EC.build(seed, *key), ("K", "idx", "pick", "sets")) == crc, key
 
 
 @pytest.mark.parametrize("name", EC.EDGE_SHAPES)
@@ -141,18 +134,8 @@ def test_the_reference_spread_is_rounding_noise_on_the_existing_cases():
 
 
 def _drawn_layout(case, key):
-    B, H, W, k, num, hyp, noisy = key
-    assert case["pick"].dtype == torch.int64 and tuple(case["pick"].shape) == (num,) and int(case["pick"].min()) >= 0 and int(case["pick"].max()) < k
-    assert case["pick"].unique().numel() < num                                         # drawn with replacement: some pixel repeats
-    s = case["sets"]
-    assert s.dtype == torch.int32 and tuple(s.shape) == (B, hyp, 8) and int(s.min()) >= 0 and int(s.max()) < num
-    m = EC.solvers()
-    m.ransac_iters = hyp
-    assert torch.equal(s.long(), m._minimal_sets(B, num, 8, "cpu"))                     # the class's own draw
-    assert any(row.unique().numel() < 8 for row in s.reshape(-1, 8))
-    well = case["well"]
-    assert well.dtype == torch.bool and tuple(well.shape) == (2 * B, hyp)
-    assert not bool((well & ~torch.cat([EC.distinct_pixels(case)] * 2, 0)).any())      # a repeated pixel is never well-defined
+    RC.drawn_layout(8, case, key)
+    assert any(row.unique().numel() < 8 for row in case["sets"].reshape(-1, 8))
 
 
 @pytest.mark.parametrize("key", EC.DRAWN_SHAPES)
@@ -249,7 +232,7 @@ def test_the_model_scene_tells_the_plane_and_row_orderings_apart(B):
     """tests/test_hip_eight_point_model.py's scene, float64 on the CPU with the analytic F as the target: exchanging the two
     directions' targets (plane d*B + b read as (1-d)*B + b), or reading E's row d*B + b for (b, d), moves some sample's loss by
     more than 100 x the loss tolerance, at the translation scale 40 the test uses."""
-    from tests.test_hip_eight_point import WEIGHTS_OF, _loss_reference
+    WEIGHTS_OF, _loss_reference = EC.WEIGHTS_OF, EC.loss_reference
     case = EC.build(0, B, 12, 20, 72, 64, 64, True)
     w = torch.tensor(WEIGHTS_OF[B])
     F = case["F_true"]

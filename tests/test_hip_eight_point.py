@@ -1,11 +1,11 @@
 """The eight-point operator (eight_point.py over csrc/ops_eight_point.hip) against the float64 composition of
 ``GeometrySolvers.compute_fundmental_mat`` / ``compute_eight_point_loss`` on the same sets, on the cases of
 tests/eight_point_cases.py: (B, H, W, k, num, hyp) = (2, 12, 20, 72, 64, 32) without and with noise, (2, 13, 19, 72, 70, 33) and
-(2, 20, 24, 320, 300, 70) -- num above the scoring kernel's match tile (EP_MATCH_TILE = 256: two blocks per plane, the second
-partly filled) and hyp above its hypothesis tile (EP_HYP_TILE = 64) and no multiple of it.  Every buffer of the raw entry points
-is carved out of a guarded one.  The edge cases (EC.EDGE_SEEDS): both fall-backs of the consensus (fewer than 8 votes: all
-matches; fewer than 8 inliers of the first refit: its set is kept), num = 256 and hyp = 128 (exactly one match tile and two
-hypothesis tiles), B = 1 and B = 3.
+(2, 20, 24, 320, 300, 70) -- num above the scoring kernel's match tile (dfe::ransac::MATCH_TILE = 256: two blocks per plane, the
+second partly filled) and hyp above its hypothesis tile (HYP_TILE = 64) and no multiple of it.  Every buffer of the raw entry
+points is carved out of a guarded one (tests/ransac_run.py, which also holds the test bodies shared with tests/test_hip_pnp.py).
+The edge cases (EC.EDGE_SEEDS): both fall-backs of the consensus (fewer than 8 votes: all matches; fewer than 8 inliers of the
+first refit: its set is kept), num = 256 and hyp = 128 (exactly one match tile and two hypothesis tiles), B = 1 and B = 3.
 
 Votes and weights are integers and the cases keep every residual a relative 1e-6 away from the threshold: they must be EQUAL.
 ``F64``: max |F - F_comp| / max |F_comp| over all cases measured on the device is 1.786e-11
@@ -14,7 +14,6 @@ compiler -- and is asserted to lie below the composition's own distance to ``F_t
 the project's written tolerances, 5e-6 relative and 2e-5 of the gradient's scale.  An edge case is held to
 max(F_BOUND, 16 x y), y = the float64 composition's own spread on that case between ``eigh`` of the normal matrix and ``svd``
 of the design matrix (EC.reference_spread, CPU only; profiles/eight_point_ebound.txt)."""
-import ctypes
 import functools
 
 import pytest
@@ -22,56 +21,30 @@ import torch
 
 from tests import eight_point_cases as EC
 from tests import guarded as G
+from tests import ransac_run as RR
+from tests.ransac_run import P, _bits, _tag
 
 pytestmark = pytest.mark.gpu
 
 F_MEASURED = 1.786e-11
 F_BOUND = 16.0 * F_MEASURED
-P = ctypes.c_void_p
-WEIGHTS_OF = {1: (0.7,), 2: (0.7, 1.3), 3: (0.7, 1.3, 0.9)}         # a different cotangent per sample
-
-
-def _i32(carved):
-    return carved.view.contiguous().view(torch.int32).cpu()
-
-
-def _doubles_written(carved):
-    """``Carved.written`` for a buffer of doubles: every double finite and neither of its words the sentinel.  (``written`` reads
-    the words as floats, and the low word of a finite double is a NaN or an infinity once in 128 doubles: seen at B = 3.)"""
-    words = _i32(carved)
-    return bool(torch.isfinite(carved.view.contiguous().view(torch.float64)).all()) and bool((words != G.SENTINEL).all())
+WEIGHTS_OF = EC.WEIGHTS_OF
 
 
 def raw_ransac(case, sets=None, flow_bwd=None, flow_fwd=None, offsets=(1, 2, 3, 2)):
-    """dfe_fundamental_ransac with the flows, every output and the workspace carved -> dict of CPU tensors (``Fh``: the
-    hypotheses section of the workspace, [2B,hyp,3,3] doubles, bits as the kernel left them); guards checked."""
+    """dfe_fundamental_ransac through RR.raw_ransac -> dict of CPU tensors (``Fh``: the hypotheses section of the workspace,
+    [2B,hyp,3,3] doubles, bits as the kernel left them); guards checked."""
     from unsupervised_depth_opticalflow_egomotion_amd import _lib, eight_point
     lib = _lib.get_lib()
-    B, H, W, k, num = (case[n] for n in ("B", "H", "W", "k", "num"))
-    sets = (case["sets"] if sets is None else sets).cuda().contiguous()
-    hyp = sets.shape[1]
-    fb = G.Carved((B, 2, H, W), offset_floats=offsets[0], fill=case["flow_bwd"] if flow_bwd is None else flow_bwd)
-    ff = G.Carved((B, 2, H, W), offset_floats=offsets[1], fill=case["flow_fwd"] if flow_fwd is None else flow_fwd)
-    idx, pick = case["idx"].cuda(), case["pick"].cuda()
-    F64 = G.Carved((2 * B * 9, 2), offset_floats=offsets[3])          # doubles: 8-byte aligned, not 16
-    F32 = G.Carved((2 * B, 9), offset_floats=offsets[2])
-    info = G.Carved((2 * B, 4), offset_floats=1)
-    sec = eight_point.workspace_sections(B, num, hyp)
-    assert lib.dfe_eight_point_ws_bytes(B, num, hyp) == sec["bytes"]
-    ws = G.Carved((sec["bytes"] // 4,), offset_floats=0)
-    _lib.check(lib.dfe_fundamental_ransac(P(fb.ptr), P(ff.ptr), P(idx.data_ptr()), P(pick.data_ptr()), P(sets.data_ptr()), P(F64.ptr),
-                                          P(F32.ptr), P(info.ptr), P(ws.ptr), B, H, W, k, num, hyp, EC.THRESH, _lib.stream_ptr()),
-               "dfe_fundamental_ransac")
-    torch.cuda.synchronize()
-    for c in (fb, ff, F64, F32, info, ws):
-        assert c.intact()
-    words = _i32(ws)
-    sl = lambda name, n: words[sec[name] // 4:sec[name] // 4 + n]   # noqa: E731
-    Fh = sl("Fh", 2 * 2 * B * hyp * 9).clone().view(torch.float64).reshape(2 * B, hyp, 3, 3)
-    return dict(Fh=Fh, F64=F64.view.contiguous().view(torch.float64).cpu().reshape(2 * B, 3, 3), F32=F32.cpu().reshape(2 * B, 3, 3),
-                info=_i32(info).reshape(2 * B, 4), counts=sl("counts", 2 * B * hyp).reshape(2 * B, hyp),
-                w1=sl("w1", 2 * B * num).reshape(2 * B, num), w2=sl("w2", 2 * B * num).reshape(2 * B, num),
-                written=_doubles_written(F64) and F32.written() and info.written())
+
+    def launch(*args):
+        B, _, _, _, num, hyp = dims = args[-1]
+        assert lib.dfe_eight_point_ws_bytes(B, num, hyp) == eight_point.workspace_sections(B, num, hyp)["bytes"]
+        _lib.check(lib.dfe_fundamental_ransac(*args[:-1], *dims, EC.THRESH, _lib.stream_ptr()), "dfe_fundamental_ransac")
+    out = RR.raw_ransac(case, launch, eight_point.workspace_sections, 9, ("Fh", 9), sets, flow_bwd, flow_fwd, offsets)
+    n, hyp = out["info"].shape[0], out["counts"].shape[1]
+    out.update(Fh=out.pop("table").reshape(n, hyp, 3, 3), F64=out.pop("est64").reshape(n, 3, 3), F32=out.pop("est32").reshape(n, 3, 3))
+    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -95,26 +68,16 @@ def rel_err(F, ref):
 @pytest.mark.parametrize("key", EC.SHAPES)
 def test_votes_sets_and_info_equal_the_composition(key):
     case, out = result(key)
-    c = case["comp"]
-    assert out["written"]
-    assert torch.equal(out["counts"].long(), c["counts"])                       # every hypothesis, as integers
-    assert torch.equal(out["w1"].long(), c["w1"].long()) and torch.equal(out["w2"].long(), c["w2"].long())
-    info = out["info"].long()
-    assert torch.equal(info[:, 0], c["best"]) and torch.equal(info[:, 1], c["counts"].max(1)[0])
-    assert torch.equal(info[:, 2], c["w1"].sum(1).long()) and torch.equal(info[:, 3], c["w2"].sum(1).long())
-    assert torch.equal(info[:, 1], out["w1"].sum(1).long())                     # the consensus is the winner's inlier set (>= 8)
+    RR._equal_decisions(out, case["comp"])
+    assert torch.equal(out["info"][:, 1].long(), out["w1"].sum(1).long())       # the consensus is the winner's inlier set (>= 8)
 
 
 @pytest.mark.parametrize("name", EC.EDGE_SHAPES)
 def test_edge_votes_sets_and_info_equal_the_composition(name):
     case, out = edge_result(name)
     c, num = case["comp"], case["num"]
-    assert out["written"]
-    assert torch.equal(out["counts"].long(), c["counts"])
-    assert torch.equal(out["w1"].long(), c["w1"].long()) and torch.equal(out["w2"].long(), c["w2"].long())
+    RR._equal_decisions(out, c)
     info = out["info"].long()
-    assert torch.equal(info[:, 0], c["best"]) and torch.equal(info[:, 1], c["counts"].max(1)[0])
-    assert torch.equal(info[:, 2], c["w1"].sum(1).long()) and torch.equal(info[:, 3], c["w2"].sum(1).long())
     first, second = c["n1raw"] < 8, c["n2raw"] < 8
     assert torch.equal(info[~first, 1], out["w1"][~first].sum(1).long())        # a consensus is the winner's inlier set
     if EC.EDGE_SEEDS[name][2]:
@@ -139,7 +102,7 @@ def test_edge_f64_against_the_composition(name):
     e = rel_err(out["F64"], ref)
     dist = min(float((ref[p] - case["F_true"][p]).abs().max() / case["F_true"][p].abs().max()) for p in range(ref.shape[0]))
     print("EBOUND eight_point F64 edge %s %s max|dF|/max|F| %.3e; y (eigh against svd, float64) %.3e bound %.3e; the composition's "
-          "distance to F_true: min %.3e" % (name, "x".join(str(int(v)) for v in EC.EDGE_SEEDS[name][0]), e, y, bound, dist))
+          "distance to F_true: min %.3e" % (name, _tag(EC.EDGE_SEEDS[name][0]), e, y, bound, dist))
     assert bound < dist                     # otherwise the case could not tell the estimate from the truth
     assert torch.equal(out["F32"], out["F64"].float())
     assert e <= bound, (e, bound)
@@ -152,7 +115,7 @@ def test_f64_against_the_composition_and_f32_is_its_rounding():
         ref = case["comp"]["F"]
         assert bool(torch.isfinite(out["F64"]).all())
         e = rel_err(out["F64"], ref)
-        print("EBOUND eight_point F64 %s max|dF|/max|F| %.3e" % ("x".join(str(int(v)) for v in key), e))
+        print("EBOUND eight_point F64 %s max|dF|/max|F| %.3e" % (_tag(key), e))
         worst = max(worst, e)
         assert torch.equal(out["F32"], out["F64"].float())                      # rounded once: bit equality
         if case["noisy"]:
@@ -164,18 +127,7 @@ def test_f64_against_the_composition_and_f32_is_its_rounding():
 
 
 def test_tied_counts_go_to_the_lowest_index():
-    """Two identical hypotheses: the winner of plane (d = 0, b = 0) is copied to another slot of sample 0's sets; both have the
-    maximum count of that plane and the lower slot wins.  The estimate does not move."""
-    key = EC.SHAPES[0]
-    case, out = result(key)
-    best = int(case["comp"]["best"][0])
-    slot = 0 if best != 0 else 1
-    sets = case["sets"].clone()
-    sets[0, slot] = sets[0, best]
-    tied = raw_ransac(case, sets=sets)
-    assert int(tied["counts"][0, slot]) == int(tied["counts"][0, best]) == int(out["info"][0, 1])
-    assert int(tied["info"][0, 0]) == min(slot, best) and int(tied["info"][0, 1]) == int(out["info"][0, 1])
-    assert torch.equal(tied["w1"][0], out["w1"][0]) and torch.equal(tied["F64"][0], out["F64"][0])
+    RR.tied_counts_go_to_the_lowest_index(*result(EC.SHAPES[0]), raw_ransac, "F64")
 
 
 @pytest.mark.parametrize("key", EC.SHAPES[1:3])
@@ -202,25 +154,6 @@ def test_properties_on_the_products_own_sets(key):
     assert int(info[:, 1].min()) >= 8
 
 
-def _loss_reference(F64, K, K_inv, pose, weights, dtype=torch.float64):
-    """float64: compute_eight_point_loss's expression per direction and sample, fed the given F, on the oracle's [t]x R; the
-    gradient of sum(weights * loss) with respect to the pose and to E.  ``dtype`` = float32: the same expression in fp32 (its
-    distance to the float64 one is what fp32 alone costs)."""
-    from oracle import loss_stack_oracle as O
-    import torch.nn.functional as F
-    B = K.shape[0]
-    pose = pose.to(dtype).requires_grad_(True)
-    E = torch.stack([O.compute_essential_matrix(pose[:, d]) for d in range(2)], 1)          # [B,2,3,3]
-    E.retain_grad()
-    Kt_inv = torch.inverse(K.double().permute(0, 2, 1)).to(dtype)
-    loss = 0
-    for d in range(2):
-        pred = Kt_inv.bmm(E[:, d].bmm(K_inv.to(dtype)))
-        loss = loss + F.smooth_l1_loss(pred, F64[d * B:(d + 1) * B].to(dtype), reduction="none").mean((1, 2))
-    (loss * weights.to(dtype)).sum().backward()
-    return loss.detach(), pose.grad, E.grad.reshape(2 * B, 3, 3)
-
-
 @pytest.mark.parametrize("scale", [1.0, 40.0])
 def test_loss_and_gradient_against_float64(scale):
     """``scale`` = 40 puts most differences beyond smooth-L1's knee (|d| >= 1), 1 keeps them in the quadratic part."""
@@ -239,7 +172,7 @@ def _loss_against_float64(case, out, scale, tag=""):
     w = torch.tensor(WEIGHTS_OF[B])
     pose = EC.pose_vectors(case)
     pose[:, :, :3] *= scale
-    l64, gpose64, gE64 = _loss_reference(out["F64"], case["K"], case["K_inv"], pose, w)
+    l64, gpose64, gE64 = EC.loss_reference(out["F64"], case["K"], case["K_inv"], pose, w)
     Kc = G.Carved((B, 3, 3), offset_floats=1, fill=case["K"])
     Kic = G.Carved((B, 3, 3), offset_floats=3, fill=case["K_inv"])
     Fc = G.Carved((2 * B, 3, 3), offset_floats=2, fill=out["F32"])
@@ -250,9 +183,7 @@ def _loss_against_float64(case, out, scale, tag=""):
     (loss * w.cuda()).sum().backward()
     torch.cuda.synchronize()
     assert Kc.intact() and Kic.intact() and Fc.intact()
-    el = float(((loss.detach().double().cpu() - l64).abs() / l64.abs()).max())
-    eg = float((p.grad.double().cpu() - gpose64).abs().max() / gpose64.abs().max())
-    ee = float((E.grad.double().cpu() - gE64).abs().max() / gE64.abs().max())
+    el, eg, ee = RR.loss_errors(loss, l64, (p.grad, gpose64), (E.grad, gE64))
     print("EBOUND eight_point loss%s scale %g: loss %.3e (5e-6)  dpose %.3e  dE %.3e (2e-5)" % (tag, scale, el, eg, ee))
     assert el <= 5e-6 and eg <= 2e-5 and ee <= 2e-5
 
@@ -275,12 +206,10 @@ def _guarded_loss_entry_points(results):
             Kt = eight_point.inverse_transposed(case["K"].cuda())
         ins = [G.Carved((2 * B, 9), offset_floats=1, fill=E), G.Carved((B, 9), offset_floats=2, fill=Kt),
                G.Carved((B, 9), offset_floats=3, fill=case["K_inv"]), G.Carved((2 * B, 9), offset_floats=0, fill=out["F32"])]
-        loss, gloss, gE = G.Carved((B,), offset_floats=1), G.Carved((B,), offset_floats=3, fill=torch.tensor(WEIGHTS_OF[B])), G.Carved((2 * B, 9), offset_floats=1)
         st = _lib.stream_ptr()
-        _lib.check(lib.dfe_eight_point_loss_fwd(*[P(c.ptr) for c in ins], P(loss.ptr), B, st), "fwd")
-        _lib.check(lib.dfe_eight_point_loss_bwd(*[P(c.ptr) for c in ins], P(gloss.ptr), P(gE.ptr), B, st), "bwd")
-        torch.cuda.synchronize()
-        assert all(c.intact() for c in ins + [loss, gloss, gE]) and loss.written() and gE.written()
+        RR.guarded_loss_entry_points(B, ins, G.Carved((2 * B, 9), offset_floats=1), WEIGHTS_OF[B],
+                                     lambda *a: _lib.check(lib.dfe_eight_point_loss_fwd(*a, B, st), "fwd"),
+                                     lambda *a: _lib.check(lib.dfe_eight_point_loss_bwd(*a, B, st), "bwd"))
         assert float(torch.inverse(case["K"].double().permute(0, 2, 1)).sub(Kt.double().cpu()).abs().max()) < 1e-6
 
 
@@ -374,11 +303,6 @@ def null_space_bounds(case, sets, well, tag):
     return tuple(NULL_FACTOR * w for w in worst)
 
 
-def check_well_defined_counts(out, comp, well):
-    """Stage 1."""
-    assert torch.equal(out["counts"].long()[well], comp["counts"][well])
-
-
 def check_ill_defined_slots(case, out, sets, well, tag, only=None):
     """Stage 2 on the ill-defined slots (``only``: a further mask)."""
     bounds = null_space_bounds(case, sets, well, tag)
@@ -394,16 +318,11 @@ def check_ill_defined_slots(case, out, sets, well, tag, only=None):
     assert all(g <= b for g, b in zip(got, bounds)), (got, bounds)
 
 
-def check_scoring(out, cont):
-    """Stage 3: every slot's count is the float64 recount from the kernel's own table; a (slot, match) pair within MARGIN of the
-    threshold is left out, and a second such pair makes the case inconclusive."""
-    t = EC.THRESH * EC.THRESH
-    err = cont["err"]
-    near = torch.isfinite(err) & ((err - t).abs() / t < EC.MARGIN)
-    assert int(near.sum()) <= 1, "inconclusive: %d residuals within MARGIN of the threshold" % int(near.sum())
-    sure = (err <= t) & ~near
-    got = out["counts"].long()
-    assert bool((got >= sure.sum(2)).all() and (got <= sure.sum(2) + near.sum(2)).all())
+def stages(case, out, cont, sets, well, tag, only=None):
+    """Stages 2 to 4 of a run on ``sets`` (``well``: EC.well_defined of them; ``only``: a further mask for stage 2)."""
+    check_ill_defined_slots(case, out, sets, well, tag, only)
+    RR.check_scoring(out, cont["err"], cont["err"] <= EC.THRESH * EC.THRESH, EC.THRESH, EC.MARGIN)
+    check_consensus_and_estimate(case, out, cont, tag)
 
 
 def check_consensus_and_estimate(case, out, cont, tag):
@@ -431,97 +350,36 @@ def drawn_result(key):
     return case, out, EC.continued(case, out["Fh"])
 
 
-def _tag(key):
-    return "x".join(str(int(v)) for v in key)
-
-
 @pytest.mark.parametrize("key", EC.DRAWN_SHAPES)
 def test_drawn_sets_stage_by_stage(key):
     case, out, cont = drawn_result(key)
-    assert out["written"]
-    check_well_defined_counts(out, case["comp"], case["well"])
-    check_ill_defined_slots(case, out, case["sets"], case["well"], "drawn " + _tag(key))
-    check_scoring(out, cont)
-    check_consensus_and_estimate(case, out, cont, "drawn " + _tag(key))
-    # the seed was chosen for a well-defined winner: none of the kernel's ill-defined slots out-polls it, and the estimate is the
-    # composition's without those slots (case["ref"]: the same on every host)
+    RR.drawn_sets_stage_by_stage(case, out, cont, stages, key)
     ref = case["ref"]
-    assert torch.equal(out["info"].long()[:, 0], ref["best"]) and torch.equal(out["w2"].long(), ref["w2"].long())
     bound = max(F_BOUND, 16.0 * EC.reference_spread(dict(matches=case["matches"], comp=ref)))
     assert rel_err(out["F64"], ref["F"]) <= bound
 
 
 def test_a_winner_with_repeated_matches_reaches_both_refits():
-    """The case whose reference winner is ill-defined: stages 2-4 alone.  The kernel's own winner of some plane repeats a match,
-    and its consensus goes through both refits with neither fall-back."""
     case = EC.ill_winner_case()
     out = raw_ransac(case)
-    cont = EC.continued(case, out["Fh"])
-    assert out["written"]
-    check_ill_defined_slots(case, out, case["sets"], case["well"], "ill-defined winner")
-    check_scoring(out, cont)
-    check_consensus_and_estimate(case, out, cont, "ill-defined winner")
-    best = out["info"].long()[:, 0]
-    repeats = ~torch.cat([EC.distinct_pixels(case)] * 2, 0)
-    won = torch.gather(repeats, 1, best.view(-1, 1)).squeeze(1)
-    assert bool(won.any()), "no plane's winner repeats a match"
-    assert bool((cont["n1raw"][won] >= 8).all() and (cont["n2raw"][won] >= 8).all())
-    assert torch.equal(out["info"].long()[won, 1], out["w1"][won].sum(1).long())      # the consensus is the winner's own set
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int64) if t.dtype == torch.float64 else t.contiguous().view(torch.int32)
+    RR.a_winner_with_repeated_matches(case, out, EC.continued(case, out["Fh"]), stages, 8)
 
 
 def _crafted_run(slots, tag):
-    """The hyp = 70 case with ``slots`` of sample 0's sets overwritten by degenerate sets (EC.crafted_sets): every other slot and
-    the other sample bit-equal to the unmodified run, the overwritten slots through stages 2 and 3, the outputs through stage 4."""
-    key = EC.DRAWN_SHAPES[1]
-    case, base, _ = drawn_result(key)
-    B, hyp = case["B"], case["hyp"]
-    assert hyp == 70 and B == 2
-    sets = EC.crafted_sets(case, slots)
-    out = raw_ransac(case, sets=sets)
-    assert out["written"]
-    touched = torch.zeros(2 * B, hyp, dtype=torch.bool)
-    for d in range(2):
-        touched[d * B, list(slots)] = True
-    well = EC.well_defined(case, sets)
-    assert not bool(well[touched].any()) and torch.equal(well[~touched], case["well"][~touched])
-    assert torch.equal(_bits(out["Fh"])[~touched], _bits(base["Fh"])[~touched])              # no slot's slice leaks into another's
-    assert torch.equal(out["counts"][~touched], base["counts"][~touched])
-    for d in range(2):                                                                       # sample 1: every output
-        p = d * B + 1
-        for name in ("F64", "F32", "info", "w1", "w2", "counts", "Fh"):
-            assert torch.equal(_bits(out[name][p]), _bits(base[name][p])), (name, p)
-    cont = EC.continued(case, out["Fh"])
-    check_ill_defined_slots(case, out, sets, well, tag, only=touched)
-    check_scoring(out, cont)
-    check_consensus_and_estimate(case, out, cont, tag)
-    return case, base, out
+    """RR.crafted_run on the hyp = 70 drawn case, against its unmodified run."""
+    case, base, _ = drawn_result(EC.DRAWN_SHAPES[1])
+    return RR.crafted_run(EC, case, base, raw_ransac, stages, ("Fh",), ("F64", "F32"), slots, tag)
 
 
 def test_degenerate_sets_stay_inside_their_own_slice():
     """Slots 0, 31, 32, 63, 64 and 69 (the ends of the hypothesis kernel's 32-thread blocks and of the scoring kernel's 64-slot
     LDS round) hold eight copies of one index, two indices four times, four indices twice.  No winner is among them: the
     estimate does not move."""
-    case, base, out = _crafted_run(EC.CRAFTED_SLOTS, "crafted slots")
-    assert not any(int(b) in EC.CRAFTED_SLOTS for b in base["info"][:, 0])
-    for name in ("F64", "F32", "info", "w1", "w2"):
-        assert torch.equal(_bits(out[name]), _bits(base[name])), name
+    RR.degenerate_sets_stay_inside_their_own_slice(drawn_result(EC.DRAWN_SHAPES[1])[1], _crafted_run, ("F64", "F32"))
 
 
 def test_a_degenerate_set_in_the_winning_slot_hands_over_to_the_runner_up():
-    key = EC.DRAWN_SHAPES[1]
-    case, base, _ = drawn_result(key)
-    best = int(base["info"][0, 0])
-    slots = EC.CRAFTED_SLOTS[:5] + (best,)
-    assert best not in EC.CRAFTED_SLOTS[:5]
-    case, base, out = _crafted_run(slots, "crafted winner")
-    counts = base["counts"][0].clone()
-    counts[list(slots)] = -1
-    assert int(out["counts"][0, best]) < int(counts.max())                  # the degenerate set polls less than the runner-up
-    assert int(out["info"][0, 0]) == int(counts.argmax()) and int(out["info"][0, 1]) == int(counts.max())
+    RR.a_degenerate_winning_slot_hands_over_to_the_runner_up(drawn_result(EC.DRAWN_SHAPES[1])[1], _crafted_run)
 
 
 def test_a_nan_match_leaves_its_hypotheses_without_a_vote():

@@ -1,11 +1,12 @@
 """The PnP operator (pnp.py over csrc/ops_pnp.hip) against the float64 composition of ``GeometrySolvers.pnp`` on the same sets and on
 float64 points formed as the operator forms them, on the cases of tests/pnp_cases.py: (B, H, W, k, num, hyp) = (2, 12, 20, 72, 64,
 32) without and with noise, (2, 13, 19, 72, 70, 33) and (2, 20, 24, 320, 300, 70) -- num above the scoring kernel's match tile
-(PNP_MATCH_TILE = 256: two blocks per plane, the second partly filled) and hyp above its hypothesis tile (PNP_HYP_TILE = 64) and no
-multiple of it -- plus the case whose first refinement falls back to all matches.  Every buffer of the raw entry points is carved
-out of a guarded one.  The edge cases (PC.EDGE_SEEDS): planes without a single vote (best count 0, winner slot 0, both fall-backs),
-rotations of 0.13 to 0.37 rad and of none at all (so3_log's series branch), num = 256 and hyp = 128 (exactly one match tile and
-two hypothesis tiles), B = 1 and B = 3.  An edge case is held to max(P_BOUND, 10 x y), y = the composition at 40 iterations
+(dfe::ransac::MATCH_TILE = 256: two blocks per plane, the second partly filled) and hyp above its hypothesis tile (HYP_TILE = 64)
+and no multiple of it -- plus the case whose first refinement falls back to all matches.  Every buffer of the raw entry points is
+carved out of a guarded one (tests/ransac_run.py, which also holds the test bodies shared with tests/test_hip_eight_point.py).
+The edge cases (PC.EDGE_SEEDS): planes without a single vote (best count 0, winner slot 0, both fall-backs), rotations of 0.13
+to 0.37 rad and of none at all (so3_log's series branch), num = 256 and hyp = 128 (exactly one match tile and two hypothesis
+tiles), B = 1 and B = 3.  An edge case is held to max(P_BOUND, 10 x y), y = the composition at 40 iterations
 against itself at 20 on that case.
 
 Votes and weights are integers and the cases keep every residual a relative 1e-6 away from the threshold: they must be EQUAL.
@@ -24,6 +25,8 @@ import torch
 
 from tests import guarded as G
 from tests import pnp_cases as PC
+from tests import ransac_run as RR
+from tests.ransac_run import P, _bits, _equal_decisions, _tag
 
 pytestmark = pytest.mark.gpu
 
@@ -31,48 +34,27 @@ P_MEASURED = 1.273e-09
 P_BOUND = 10.0 * P_MEASURED
 TRUE_MEASURED = 1.212e-07
 TRUE_BOUND = 10.0 * TRUE_MEASURED
-P = ctypes.c_void_p
-WEIGHTS_OF = {1: (0.7,), 2: (0.7, 1.3), 3: (0.7, 1.3, 0.9)}         # a different cotangent per sample
-
-
-def _i32(carved):
-    return carved.view.contiguous().view(torch.int32).cpu()
+WEIGHTS_OF = PC.WEIGHTS_OF
 
 
 def raw_ransac(case, sets=None, flow_bwd=None, flow_fwd=None, disp_t=None, offsets=(1, 2, 3, 2), iters=PC.ITERS):
-    """dfe_pnp_ransac with the flows, the disparity, the camera matrices, every output and the workspace carved -> dict of CPU
-    tensors (``Rh`` [2B,hyp,3,3], ``Th`` [2B,hyp,3]: the hypotheses section of the workspace, bits as the kernel left them);
-    guards checked."""
+    """dfe_pnp_ransac through RR.raw_ransac, the disparity and the camera matrices carved as well -> dict of CPU tensors (``Rh``
+    [2B,hyp,3,3], ``Th`` [2B,hyp,3]: the hypotheses section of the workspace, bits as the kernel left them); guards checked."""
     from unsupervised_depth_opticalflow_egomotion_amd import _lib, pnp
     lib = _lib.get_lib()
-    B, H, W, k, num = (case[n] for n in ("B", "H", "W", "k", "num"))
-    sets = (case["sets"] if sets is None else sets).cuda().contiguous()
-    hyp = sets.shape[1]
-    fb = G.Carved((B, 2, H, W), offset_floats=offsets[0], fill=case["flow_bwd"] if flow_bwd is None else flow_bwd)
-    ff = G.Carved((B, 2, H, W), offset_floats=offsets[1], fill=case["flow_fwd"] if flow_fwd is None else flow_fwd)
+    B, H, W = case["B"], case["H"], case["W"]
     dt = G.Carved((B, 1, H, W), offset_floats=offsets[2], fill=case["disp_t"] if disp_t is None else disp_t)
     Kc = G.Carved((B, 9), offset_floats=1, fill=case["K"].reshape(B, 9))
     Kic = G.Carved((B, 9), offset_floats=3, fill=case["K_inv"].reshape(B, 9))
-    idx, pick = case["idx"].cuda(), case["pick"].cuda()
-    P64 = G.Carved((2 * B * 6, 2), offset_floats=offsets[3])          # doubles: 8-byte aligned, not 16
-    P32 = G.Carved((2 * B, 6), offset_floats=offsets[2])
-    info = G.Carved((2 * B, 4), offset_floats=1)
-    sec = pnp.workspace_sections(B, num, hyp)
-    assert lib.dfe_pnp_ws_bytes(B, num, hyp) == sec["bytes"]
-    ws = G.Carved((sec["bytes"] // 4,), offset_floats=0)
-    _lib.check(lib.dfe_pnp_ransac(P(fb.ptr), P(ff.ptr), P(dt.ptr), P(idx.data_ptr()), P(pick.data_ptr()), P(sets.data_ptr()), P(Kc.ptr),
-                                  P(Kic.ptr), P(P64.ptr), P(P32.ptr), P(info.ptr), P(ws.ptr), B, H, W, k, num, hyp, iters, PC.THRESH,
-                                  _lib.stream_ptr()), "dfe_pnp_ransac")
-    torch.cuda.synchronize()
-    for c in (fb, ff, dt, Kc, Kic, P64, P32, info, ws):
-        assert c.intact()
-    words = _i32(ws)
-    sl = lambda name, n: words[sec[name] // 4:sec[name] // 4 + n]   # noqa: E731
-    Ph = sl("Ph", 2 * 2 * B * hyp * 12).clone().view(torch.float64).reshape(2 * B, hyp, 12)
-    return dict(Rh=Ph[:, :, :9].reshape(2 * B, hyp, 3, 3).clone(), Th=Ph[:, :, 9:].clone(), P64=P64.view.contiguous().view(torch.float64).cpu().reshape(2 * B, 6), P32=P32.cpu().reshape(2 * B, 6),
-                info=_i32(info).reshape(2 * B, 4), counts=sl("counts", 2 * B * hyp).reshape(2 * B, hyp),
-                w1=sl("w1", 2 * B * num).reshape(2 * B, num), w2=sl("w2", 2 * B * num).reshape(2 * B, num),
-                written=P32.written() and info.written())
+
+    def launch(fb, ff, idx, pick, sets, P64, P32, info, ws, dims):
+        assert lib.dfe_pnp_ws_bytes(B, dims[4], dims[5]) == pnp.workspace_sections(B, dims[4], dims[5])["bytes"]
+        _lib.check(lib.dfe_pnp_ransac(fb, ff, P(dt.ptr), idx, pick, sets, P(Kc.ptr), P(Kic.ptr), P64, P32, info, ws, *dims, iters,
+                                      PC.THRESH, _lib.stream_ptr()), "dfe_pnp_ransac")
+    out = RR.raw_ransac(case, launch, pnp.workspace_sections, 6, ("Ph", 12), sets, flow_bwd, flow_fwd, offsets, more=(dt, Kc, Kic))
+    Ph = out.pop("table")
+    out.update(Rh=Ph[:, :, :9].reshape(2 * B, -1, 3, 3).clone(), Th=Ph[:, :, 9:].clone(), P64=out.pop("est64"), P32=out.pop("est32"))
+    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,15 +74,6 @@ def edge_result(name):
 def rel_err(Pd, ref):
     """the largest difference of a plane's pose relative to that pose's scale, over the planes"""
     return float(((Pd - ref).abs().amax(1) / ref.abs().amax(1)).max())
-
-
-def _equal_decisions(out, c):
-    assert out["written"]
-    assert torch.equal(out["counts"].long(), c["counts"])                       # every hypothesis, as integers
-    assert torch.equal(out["w1"].long(), c["w1"].long()) and torch.equal(out["w2"].long(), c["w2"].long())
-    info = out["info"].long()
-    assert torch.equal(info[:, 0], c["best"]) and torch.equal(info[:, 1], c["counts"].max(1)[0])
-    assert torch.equal(info[:, 2], c["w1"].sum(1).long()) and torch.equal(info[:, 3], c["w2"].sum(1).long())
 
 
 @pytest.mark.parametrize("key", PC.SHAPES)
@@ -137,7 +110,7 @@ def test_edge_p64_against_the_composition(name):
     e = rel_err(out["P64"], ref)
     norms = out["P64"][:, 3:].norm(dim=1)
     print("EBOUND pnp P64 edge %s %s max|dP|/max|P| %.3e; y (the composition at 40 iterations against itself at 20) %.3e bound %.3e; "
-          "axis-angle norms %.3e to %.3e" % (name, "x".join(str(int(v)) for v in PC.EDGE_SEEDS[name][0]), e, y, bound,
+          "axis-angle norms %.3e to %.3e" % (name, _tag(PC.EDGE_SEEDS[name][0]), e, y, bound,
                                               float(norms.min()), float(norms.max())))
     assert torch.equal(out["P32"], out["P64"].float())                          # rounded once: bit equality
     assert e <= bound, (e, bound)
@@ -160,7 +133,7 @@ def test_p64_against_the_composition_and_p32_is_its_rounding():
         e = rel_err(out["P64"], ref)
         yard = rel_err(PC.composition_of(case, case["x"], case["X"], iterations=2 * PC.ITERS)["P"], ref)
         print("EBOUND pnp P64 %s max|dP|/max|P| %.3e; the composition at 40 iterations against itself at 20: %.3e"
-              % ("x".join(str(int(v)) for v in key), e, yard))
+              % (_tag(key), e, yard))
         worst = max(worst, e)
         assert torch.equal(out["P32"], out["P64"].float())                      # rounded once: bit equality
     print("EBOUND pnp P64 all cases %.3e bound %.3e" % (worst, P_BOUND))
@@ -191,33 +164,7 @@ def test_the_fallback_case_refines_over_all_matches_first():
 
 
 def test_tied_counts_go_to_the_lowest_index():
-    """Two identical hypotheses: the winner of plane (d = 0, b = 0) is copied to another slot of sample 0's sets; both have the
-    maximum count of that plane and the lower slot wins.  The estimate does not move."""
-    key = PC.SHAPES[0]
-    case, out = result(key)
-    best = int(case["comp"]["best"][0])
-    slot = 0 if best != 0 else 1
-    sets = case["sets"].clone()
-    sets[0, slot] = sets[0, best]
-    tied = raw_ransac(case, sets=sets)
-    assert int(tied["counts"][0, slot]) == int(tied["counts"][0, best]) == int(out["info"][0, 1])
-    assert int(tied["info"][0, 0]) == min(slot, best) and int(tied["info"][0, 1]) == int(out["info"][0, 1])
-    assert torch.equal(tied["w1"][0], out["w1"][0]) and torch.equal(tied["P64"][0], out["P64"][0])
-
-
-def _loss_reference(P64, pose, beta, weights, dtype=torch.float64):
-    """float64: compute_pnp_loss's expression per direction and sample, fed the given pose estimate; the gradient of
-    sum(weights * loss) with respect to the pose vector.  ``dtype`` = float32: the same expression in fp32."""
-    import torch.nn.functional as F
-    B = pose.shape[0]
-    pose = pose.to(dtype).requires_grad_(True)
-    loss = 0
-    for d in range(2):
-        est = P64[d * B:(d + 1) * B].to(dtype)
-        term = F.l1_loss(est[:, :3], pose[:, d, :3], reduction="none") + beta * F.l1_loss(est[:, 3:], pose[:, d, 3:], reduction="none")
-        loss = loss + term.mean(1)
-    (loss * weights.to(dtype)).sum().backward()
-    return loss.detach(), pose.grad
+    RR.tied_counts_go_to_the_lowest_index(*result(PC.SHAPES[0]), raw_ransac, "P64")
 
 
 @pytest.mark.parametrize("scale", [1.0, 40.0])
@@ -240,7 +187,7 @@ def _loss_against_float64(case, out, scale, at, tag=""):
     w = torch.tensor(WEIGHTS_OF[B])
     pose = PC.pose_vectors(case, scale=scale)
     pose[at, 0, 4] = out["P32"][0 * B + at, 4]
-    l64, g64 = _loss_reference(out["P32"].double(), pose, beta, w)
+    l64, g64 = PC.loss_reference(out["P32"].double(), pose, beta, w)
     assert float(g64[at, 0, 4]) == 0.0
     Pc = G.Carved((2 * B, 6), offset_floats=2, fill=out["P32"])
     p = pose.cuda().requires_grad_(True)
@@ -248,8 +195,7 @@ def _loss_against_float64(case, out, scale, at, tag=""):
     (loss * w.cuda()).sum().backward()
     torch.cuda.synchronize()
     assert Pc.intact()
-    el = float(((loss.detach().double().cpu() - l64).abs() / l64.abs()).max())
-    eg = float((p.grad.double().cpu() - g64).abs().max() / g64.abs().max())
+    el, eg = RR.loss_errors(loss, l64, (p.grad, g64))
     print("EBOUND pnp loss%s scale %g: loss %.3e (5e-6)  dpose %.3e (2e-5)" % (tag, scale, el, eg))
     assert el <= 5e-6 and eg <= 2e-5
     assert float(p.grad[at, 0, 4]) == 0.0 and int((p.grad == 0).sum()) == 1
@@ -269,13 +215,11 @@ def _guarded_loss_entry_points(results):
     for case, out in results:
         B = case["B"]
         ins = [G.Carved((B, 2, 6), offset_floats=1, fill=PC.pose_vectors(case)), G.Carved((2 * B, 6), offset_floats=3, fill=out["P32"])]
-        loss, gloss, gp = G.Carved((B,), offset_floats=1), G.Carved((B,), offset_floats=3, fill=torch.tensor(WEIGHTS_OF[B])), G.Carved((B, 2, 6), offset_floats=2)
         st = _lib.stream_ptr()
         beta = ctypes.c_float(0.5)
-        _lib.check(lib.dfe_pnp_loss_fwd(*[P(c.ptr) for c in ins], P(loss.ptr), B, beta, st), "fwd")
-        _lib.check(lib.dfe_pnp_loss_bwd(*[P(c.ptr) for c in ins], P(gloss.ptr), P(gp.ptr), B, beta, st), "bwd")
-        torch.cuda.synchronize()
-        assert all(c.intact() for c in ins + [loss, gloss, gp]) and loss.written() and gp.written()
+        RR.guarded_loss_entry_points(B, ins, G.Carved((B, 2, 6), offset_floats=2), WEIGHTS_OF[B],
+                                     lambda *a: _lib.check(lib.dfe_pnp_loss_fwd(*a, B, beta, st), "fwd"),
+                                     lambda *a: _lib.check(lib.dfe_pnp_loss_bwd(*a, B, beta, st), "bwd"))
 
 
 def test_refusals_come_before_any_launch():
@@ -396,11 +340,6 @@ def rotation_bounds(comp, well, tag):
     return NULL_FACTOR * o, NULL_FACTOR * d
 
 
-def check_well_defined_counts(out, comp, well):
-    """Stage 1."""
-    assert torch.equal(out["counts"].long()[well], comp["counts"][well])
-
-
 def check_ill_defined_slots(out, comp, well, tag, only=None):
     """Stage 2 on the ill-defined slots (``only``: a further mask)."""
     ob, db = rotation_bounds(comp, well, tag)
@@ -417,16 +356,12 @@ def check_ill_defined_slots(out, comp, well, tag, only=None):
     assert o <= ob and d <= db, (o, ob, d, db)
 
 
-def check_scoring(out, cont):
-    """Stage 3: every slot's count is the float64 recount from the kernel's own table; a (slot, match) pair within MARGIN of the
-    threshold (or with a depth within MARGIN of zero) is left out, and a second such pair makes the case inconclusive."""
-    t = PC.THRESH * PC.THRESH
-    err, z = cont["err"], cont["zh"]
-    near = (torch.isfinite(err) & ((err - t).abs() / t < PC.MARGIN)) | (torch.isfinite(z) & (z.abs() < PC.MARGIN))
-    assert int(near.sum()) <= 1, "inconclusive: %d residuals within MARGIN of the threshold" % int(near.sum())
-    sure = cont["inl"] & ~near
-    got = out["counts"].long()
-    assert bool((got >= sure.sum(2)).all() and (got <= sure.sum(2) + near.sum(2)).all())
+def stages(case, out, cont, sets, well, tag, only=None):
+    """Stages 2 to 4 of a run on ``sets`` (``well``: PC.well_defined of them; ``only``: a further mask for stage 2)."""
+    comp = case["comp"] if sets is case["sets"] else PC.composition_of(case, case["x"], case["X"], sets=sets)
+    check_ill_defined_slots(out, comp, well, tag, only)
+    RR.check_scoring(out, cont["err"], cont["inl"], PC.THRESH, PC.MARGIN, z=cont["zh"])
+    check_consensus_and_estimate(case, out, cont, tag)
 
 
 def check_consensus_and_estimate(case, out, cont, tag):
@@ -451,46 +386,20 @@ def drawn_result(key):
     return case, out, PC.continued(case, out["Rh"], out["Th"])
 
 
-def _tag(key):
-    return "x".join(str(int(v)) for v in key)
-
-
 @pytest.mark.parametrize("key", PC.DRAWN_SHAPES)
 def test_drawn_sets_stage_by_stage(key):
     case, out, cont = drawn_result(key)
-    assert out["written"]
-    check_well_defined_counts(out, case["comp"], case["well"])
-    check_ill_defined_slots(out, case["comp"], case["well"], "drawn " + _tag(key))
-    check_scoring(out, cont)
-    check_consensus_and_estimate(case, out, cont, "drawn " + _tag(key))
-    # the seed was chosen for a well-defined winner: none of the kernel's ill-defined slots out-polls it, and the estimate is the
-    # composition's without those slots (case["ref"]: the same on every host)
+    RR.drawn_sets_stage_by_stage(case, out, cont, stages, key)
     ref = case["ref"]
-    assert torch.equal(out["info"].long()[:, 0], ref["best"]) and torch.equal(out["w2"].long(), ref["w2"].long())
     again = PC.continued(case, torch.where(case["well"].view(*case["well"].shape, 1, 1), ref["Rh"], torch.full_like(ref["Rh"], float("nan"))),
                          ref["Th"], iterations=2 * PC.ITERS)
     assert rel_err(out["P64"], ref["P"]) <= max(P_BOUND, 10.0 * rel_err(again["P"], ref["P"]))
 
 
 def test_a_winner_with_repeated_matches_reaches_both_refinements():
-    """The case whose reference winner is ill-defined: stages 2-4 alone.  The kernel's own winner of some plane repeats a match,
-    and its consensus goes through both refinements with neither fall-back."""
     case = PC.ill_winner_case()
     out = raw_ransac(case)
-    cont = PC.continued(case, out["Rh"], out["Th"])
-    check_ill_defined_slots(out, case["comp"], case["well"], "ill-defined winner")
-    check_scoring(out, cont)
-    check_consensus_and_estimate(case, out, cont, "ill-defined winner")
-    best = out["info"].long()[:, 0]
-    repeats = ~torch.cat([PC.distinct_pixels(case)] * 2, 0)
-    won = torch.gather(repeats, 1, best.view(-1, 1)).squeeze(1)
-    assert bool(won.any()), "no plane's winner repeats a match"
-    assert bool((cont["n1raw"][won] >= 6).all() and (cont["n2raw"][won] >= 6).all())
-    assert torch.equal(out["info"].long()[won, 1], out["w1"][won].sum(1).long())      # the consensus is the winner's own set
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int64) if t.dtype == torch.float64 else t.contiguous().view(torch.int32)
+    RR.a_winner_with_repeated_matches(case, out, PC.continued(case, out["Rh"], out["Th"]), stages, 6)
 
 
 @functools.lru_cache(maxsize=None)
@@ -506,52 +415,20 @@ def coincident_result():
 
 
 def _crafted_run(slots, tag):
-    """The baseline with ``slots`` of sample 0's sets overwritten by degenerate sets (PC.crafted_sets): every other slot and the
-    other sample bit-equal to the baseline's run, the overwritten slots through stages 2 and 3, the outputs through stage 4."""
+    """RR.crafted_run on the coincident baseline."""
     case, base = coincident_result()
-    B, hyp = case["B"], case["hyp"]
-    assert hyp == 70 and B == 2
-    sets = PC.crafted_sets(case, slots)
-    out = raw_ransac(case, sets=sets)
-    touched = torch.zeros(2 * B, hyp, dtype=torch.bool)
-    for d in range(2):
-        touched[d * B, list(slots)] = True
-    well = PC.well_defined(case, sets)
-    assert not bool(well[touched].any()) and torch.equal(well[~touched], case["well"][~touched])
-    for name in ("Rh", "Th", "counts"):                                                      # no slot's slice leaks into another's
-        assert torch.equal(_bits(out[name])[~touched], _bits(base[name])[~touched]), name
-    for d in range(2):                                                                       # sample 1: every output
-        p = d * B + 1
-        for name in ("P64", "P32", "info", "w1", "w2", "counts", "Rh", "Th"):
-            assert torch.equal(_bits(out[name][p]), _bits(base[name][p])), (name, p)
-    comp = PC.composition_of(case, case["x"], case["X"], sets=sets)
-    cont = PC.continued(case, out["Rh"], out["Th"])
-    check_ill_defined_slots(out, comp, well, tag, only=touched)
-    check_scoring(out, cont)
-    check_consensus_and_estimate(case, out, cont, tag)
-    return case, base, out
+    return RR.crafted_run(PC, case, base, raw_ransac, stages, ("Rh", "Th"), ("P64", "P32"), slots, tag)
 
 
 def test_degenerate_sets_stay_inside_their_own_slice():
     """Slots 0, 31, 32, 63, 64 and 69 (the ends of the hypothesis kernel's 32-thread blocks and of the scoring kernel's 64-slot
     LDS round) hold six copies of one index, two indices three times, three indices twice, and six matches of one pixel (six
     coincident points).  No winner is among them: the estimate does not move."""
-    case, base, out = _crafted_run(PC.CRAFTED_SLOTS, "crafted slots")
-    assert not any(int(b) in PC.CRAFTED_SLOTS for b in base["info"][:, 0])
-    for name in ("P64", "P32", "info", "w1", "w2"):
-        assert torch.equal(_bits(out[name]), _bits(base[name])), name
+    RR.degenerate_sets_stay_inside_their_own_slice(coincident_result()[1], _crafted_run, ("P64", "P32"))
 
 
 def test_a_degenerate_set_in_the_winning_slot_hands_over_to_the_runner_up():
-    case, base = coincident_result()
-    best = int(base["info"][0, 0])
-    slots = PC.CRAFTED_SLOTS[:5] + (best,)
-    assert best not in PC.CRAFTED_SLOTS[:5]
-    case, base, out = _crafted_run(slots, "crafted winner")
-    counts = base["counts"][0].clone()
-    counts[list(slots)] = -1
-    assert int(out["counts"][0, best]) < int(counts.max())                  # the degenerate set polls less than the runner-up
-    assert int(out["info"][0, 0]) == int(counts.argmax()) and int(out["info"][0, 1]) == int(counts.max())
+    RR.a_degenerate_winning_slot_hands_over_to_the_runner_up(coincident_result()[1], _crafted_run)
 
 
 def test_a_nan_match_leaves_its_hypotheses_without_a_vote():

@@ -1,61 +1,23 @@
 """GPU: ``cfg.enable_pnp`` end to end, at the configurations tests/test_hip_eight_point_model.py uses -- Model_geometry.loss_stack with
 and without the switch (2 x 64 x 208 loss-stack inputs, no network), the shared draw with all three geometric switches on, and one
 256 x 832 step eager and captured in a hipGraph (capture raises on any host read: the no-host-sync proof)."""
-import copy
-
-import numpy as np
 import pytest
 import torch
 
+from tests import pnp_cases as PC
+from tests.geom_model import _bare, _on_device, _run_stack, captured_step_equals_the_eager_step, dev
 from unsupervised_depth_opticalflow_egomotion_amd import convs, synthetic
 from unsupervised_depth_opticalflow_egomotion_amd.models import get_model
-from unsupervised_depth_opticalflow_egomotion_amd.train_step import DEFAULT_CFG, GraphedTrainStep, make_cfg, make_optimizer, total_loss, train_step
+from unsupervised_depth_opticalflow_egomotion_amd.train_step import DEFAULT_CFG, make_cfg, total_loss
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def _stack_inputs(seed=3):
-    inp = synthetic.make_loss_stack_inputs(2, 64, 208, 3, seed=seed)
-
-    def t(a, grad=True):
-        x = torch.from_numpy(np.ascontiguousarray(a)).float().to(dev())
-        return x.requires_grad_(True) if grad else x
-    disps = [[t(a) for a in lst] for lst in inp.disps]
-    return dict(imgs=[t(a, False) for a in inp.imgs], disps=disps, pose=t(inp.pose), fb=[t(a) for a in inp.flows_bwd],
-                ff=[t(a) for a in inp.flows_fwd], K=t(inp.K, False), Ki=t(inp.K_inv, False))
-
-
-def _bare(triangle, eight, pnp, beta=1):
-    m = get_model("geom").__new__(get_model("geom"))        # the loss stack needs no network
-    torch.nn.Module.__init__(m)
-    cfg = make_cfg(enable_triangle=triangle, enable_eight_point=eight, enable_pnp=pnp)
-    m.dataset, m.num_scales = cfg.dataset, 3
-    m.flow_consist_alpha, m.flow_consist_beta = cfg.flow_consist_alpha, cfg.flow_consist_beta
-    m.ratio, m.num, m.beta = 0.3, 6000, beta
-    m.enable_depth_ssim = m.enable_depth_consis = False
-    m.enable_triangle, m.enable_eight_point, m.enable_pnp = triangle, eight, pnp
-    return m
-
-
-def _run_stack(triangle, eight, pnp, seed=3, manual_seed=11, beta=1):
-    x = _stack_inputs(seed)
-    m = _bare(triangle, eight, pnp, beta)
-    torch.manual_seed(manual_seed)
-    lp, _ = m.loss_stack(x["imgs"][0], x["imgs"][1], x["imgs"][2], x["disps"][0], x["disps"][1], x["disps"][2], x["pose"], x["fb"],
-                         x["ff"], x["K"], x["Ki"])
-    torch.cuda.synchronize()
-    return m, x, lp
 
 
 def test_switch_off_the_pack_is_the_parents():
     """Off: the placeholder is still ``_zeros2``'s tagged tensor, and nothing of the pack depends on the new code -- the same
     bits as with the switch on, term by term, for every other key."""
-    _, _, off = _run_stack(False, False, False)
-    m, _, on = _run_stack(False, False, True)
+    _, _, off = _run_stack(enable_triangle=False, enable_eight_point=False, enable_pnp=False)
+    m, _, on = _run_stack(enable_triangle=False, enable_eight_point=False, enable_pnp=True)
     assert getattr(off["loss_pnp"], "_dfe_zero_placeholder", False) and tuple(off["loss_pnp"].shape) == (2,)
     assert float(off["loss_pnp"].detach().abs().max()) == 0.0
     assert list(on) == list(off)
@@ -67,7 +29,7 @@ def test_switch_off_the_pack_is_the_parents():
 
 
 def test_switch_on_the_term_is_finite_and_trains_the_pose_alone():
-    m, x, on = _run_stack(False, False, True, beta=0.5)
+    m, x, on = _run_stack(enable_triangle=False, enable_eight_point=False, enable_pnp=True, beta=0.5)
     e = on["loss_pnp"]
     assert tuple(e.shape) == (2,) and e.grad_fn is not None and bool(torch.isfinite(e).all()) and float(e.detach().abs().min()) > 0
     assert not getattr(e, "_dfe_zero_placeholder", False)
@@ -120,9 +82,9 @@ def test_pose_net_parameters_alone_receive_gradient_from_the_term():
 def test_all_three_switches_share_one_selection_and_one_draw():
     def offset():
         return int(torch.cuda.get_rng_state(dev())[8:16].view(torch.int64))
-    m1, _, two = _run_stack(True, True, False)
+    m1, _, two = _run_stack(enable_triangle=True, enable_eight_point=True, enable_pnp=False)
     off_two = offset()
-    m2, _, three = _run_stack(True, True, True)
+    m2, _, three = _run_stack(enable_triangle=True, enable_eight_point=True, enable_pnp=True)
     off_three = offset()
     assert torch.equal(three["loss_triangle"].detach(), two["loss_triangle"].detach())              # the same bits
     assert torch.equal(three["loss_eight_point"].detach(), two["loss_eight_point"].detach())
@@ -131,40 +93,12 @@ def test_all_three_switches_share_one_selection_and_one_draw():
     torch.randint(0, int(0.3 * 64 * 208), [6000], device=dev())
     assert off_three == off_two == offset()                         # the generator advanced by exactly one draw
     assert float(three["loss_pnp"].detach().abs().min()) > 0
-    m3, _, alone = _run_stack(False, False, True)
+    m3, _, alone = _run_stack(enable_triangle=False, enable_eight_point=False, enable_pnp=True)
     assert torch.equal(three["loss_pnp"].detach(), alone["loss_pnp"].detach()) and torch.equal(m2.pnp_pose, m3.pnp_pose)
 
 
 def test_the_step_with_the_term_is_captured_and_equals_the_eager_step():
-    before = convs.DETERMINISTIC
-    convs.set_deterministic(True)
-    g = None
-    try:
-        cfg = make_cfg(num_scales=3, img_hw=(256, 832), mode="geom", enable_pnp=True)
-        torch.manual_seed(0)
-        model = get_model("geom")(cfg).to(dev()).train()
-        init = copy.deepcopy(model.state_dict())
-        opt = make_optimizer(model, 1e-4, capturable=True)
-        batch = [torch.from_numpy(a).to(dev()) for a in synthetic.make_triplet_batch(1, 256, 832, 3, seed=1)]
-        g = GraphedTrainStep(model, opt, batch, cfg, warmup=1)
-        torch.manual_seed(5)
-        loss_g, lp_g, _ = g(batch)
-        torch.cuda.synchronize()
-        lp_g = {k: v.detach().clone() for k, v in lp_g.items()}
-        twin = get_model("geom")(cfg).to(dev()).train()
-        twin.load_state_dict(init)
-        opt_t = make_optimizer(twin, 1e-4)
-        torch.manual_seed(5)
-        loss_e, lp_e, _ = train_step(twin, opt_t, batch, cfg)
-        torch.cuda.synchronize()
-        assert bool(torch.isfinite(lp_g["loss_pnp"]).all()) and float(lp_g["loss_pnp"].abs().min()) > 0
-        for k in lp_e:
-            assert torch.equal(lp_g[k], lp_e[k].detach()), k
-        assert float(loss_g.detach()) == float(loss_e.detach())
-    finally:
-        del g
-        torch.cuda.synchronize()
-        convs.set_deterministic(before)
+    captured_step_equals_the_eager_step("loss_pnp", enable_pnp=True)
 
 
 # ------------------------------------------------------------------------------------------------ the term through models.py
@@ -178,18 +112,11 @@ MODEL_BETA = 0.5
 
 
 def _scene(shape):
-    from tests import pnp_cases as PC
     B, H, W = shape
     case = PC.build(0, B, H, W, int(0.3 * H * W), 64, 64, True)
-    m = _bare(False, False, True, beta=MODEL_BETA)
+    m = _bare(enable_triangle=False, enable_eight_point=False, enable_pnp=True, beta=MODEL_BETA)
     m.ratio, m.num, m.ransac_iters = 0.3, 64, 64
     return case, PC.pose_vectors(case), m
-
-
-def _on_device(case, pose):
-    g = lambda t: t.to(dev()).contiguous()   # noqa: E731
-    return dict(disp=g(case["disp_t"]), fb=g(case["flow_bwd"]), ff=g(case["flow_fwd"]), K=g(case["K"]), Ki=g(case["K_inv"]),
-                pose=g(pose).requires_grad_(True))
 
 
 @pytest.mark.parametrize("shape", MODEL_SCENES)
@@ -224,7 +151,7 @@ def test_the_term_is_the_operator_on_the_models_own_draw_with_the_first_camera(s
 
 @pytest.mark.parametrize("shape", MODEL_SCENES)
 def test_the_term_and_its_pose_gradient_equal_float64_autograd_of_the_reference_expression(shape):
-    from tests.test_hip_pnp import WEIGHTS_OF, _loss_reference
+    WEIGHTS_OF, _loss_reference = PC.WEIGHTS_OF, PC.loss_reference
     case, pose, m = _scene(shape)
     B = case["B"]
     x = _on_device(case, pose)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.geom_model import _run_stack, dev
 from unsupervised_depth_opticalflow_egomotion_amd import convs, ops, synthetic
 from unsupervised_depth_opticalflow_egomotion_amd.models import get_model
 from unsupervised_depth_opticalflow_egomotion_amd.train_step import GraphedTrainStep, make_cfg, make_optimizer, total_loss, train_step
@@ -12,45 +13,9 @@ from unsupervised_depth_opticalflow_egomotion_amd.train_step import GraphedTrain
 pytestmark = pytest.mark.gpu
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
-def _stack_inputs(seed=3):
-    inp = synthetic.make_loss_stack_inputs(2, 64, 208, 3, seed=seed)
-
-    def t(a, grad=True):
-        x = torch.from_numpy(np.ascontiguousarray(a)).float().to(dev())
-        return x.requires_grad_(True) if grad else x
-    disps = [[t(a) for a in lst] for lst in inp.disps]
-    return dict(imgs=[t(a, False) for a in inp.imgs], disps=disps, pose=t(inp.pose), fb=[t(a) for a in inp.flows_bwd],
-                ff=[t(a) for a in inp.flows_fwd], K=t(inp.K, False), Ki=t(inp.K_inv, False))
-
-
-def _bare(enable):
-    m = get_model("geom").__new__(get_model("geom"))        # the loss stack needs no network
-    torch.nn.Module.__init__(m)
-    cfg = make_cfg(enable_triangle=enable)
-    m.dataset, m.num_scales = cfg.dataset, 3
-    m.flow_consist_alpha, m.flow_consist_beta = cfg.flow_consist_alpha, cfg.flow_consist_beta
-    m.ratio, m.num, m.beta = 0.3, 6000, 1
-    m.enable_depth_ssim = m.enable_depth_consis = False
-    m.enable_triangle = enable
-    return m
-
-
-def _run_stack(enable, seed=3, manual_seed=11):
-    x = _stack_inputs(seed)
-    m = _bare(enable)
-    torch.manual_seed(manual_seed)
-    lp, _ = m.loss_stack(x["imgs"][0], x["imgs"][1], x["imgs"][2], x["disps"][0], x["disps"][1], x["disps"][2], x["pose"], x["fb"],
-                         x["ff"], x["K"], x["Ki"])
-    return m, x, lp
-
-
 def test_the_switch_adds_the_term_and_changes_nothing_else():
-    _, _, off = _run_stack(False)
-    m, x, on = _run_stack(True)
+    _, _, off = _run_stack(enable_triangle=False)
+    m, x, on = _run_stack(enable_triangle=True)
     assert getattr(off["loss_triangle"], "_dfe_zero_placeholder", False) and tuple(off["loss_triangle"].shape) == (2,)
     tri = on["loss_triangle"]
     assert tuple(tri.shape) == (2,) and tri.grad_fn is not None and bool(torch.isfinite(tri).all()) and float(tri.detach().min()) > 0
@@ -68,7 +33,7 @@ def test_the_switch_adds_the_term_and_changes_nothing_else():
 def test_the_term_equals_the_torch_composition_on_its_own_draw():
     """Within the operator bound of tests/test_hip_triangulate.py: error against float64 autograd-free ``triangle_term_torch`` on
     the term's own ``idx`` / ``pick``, normalised by the largest float64 magnitude, at most 4 x max(the fp32 composition's, 2^-24)."""
-    m, x, on = _run_stack(True)
+    m, x, on = _run_stack(enable_triangle=True)
     idx, pick = m.triangle_draw
     k = int(0.3 * 64 * 208)
     assert idx.dtype == torch.int32 and tuple(idx.shape) == (4, k) and tuple(pick.shape) == (6000,) and pick.dtype == torch.int64
@@ -91,7 +56,7 @@ def test_the_terms_gradients_equal_float64_autograd_on_its_own_draw():
     ``pose_vec2mat``; yardstick: the fp32 composition on the device behind ``PoseMatsFn``, as the term itself is; a different
     cotangent per sample."""
     from oracle import loss_stack_oracle as O
-    m, x, on = _run_stack(True)
+    m, x, on = _run_stack(enable_triangle=True)
     idx, pick = m.triangle_draw
     assert pick.unique().numel() < idx.shape[1] < pick.numel()
     w = torch.tensor([0.7, 1.3])
@@ -121,7 +86,7 @@ def test_the_terms_gradients_equal_float64_autograd_on_its_own_draw():
 
 def test_gradients_reach_every_input_and_repeat_bit_for_bit():
     def grads():
-        _, x, lp = _run_stack(True)
+        _, x, lp = _run_stack(enable_triangle=True)
         lp["loss_triangle"].sum().backward()
         torch.cuda.synchronize()
         return dict(fb=x["fb"][0].grad, ff=x["ff"][0].grad, disp_l=x["disps"][0][0].grad, disp_t=x["disps"][1][0].grad,

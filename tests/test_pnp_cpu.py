@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from tests import pnp_cases as PC
+from tests import ransac_cases as RC
 
 
 def _shape_checks(case, key):
@@ -99,14 +100,6 @@ def test_the_header_declares_the_new_entries():
     assert lib.dfe_pnp_ws_bytes(0, 6, 6) == 0
 
 
-def _crc(case, names):
-    import zlib
-    c = 0
-    for n in names:
-        c = zlib.crc32(case[n].contiguous().numpy().tobytes(), c)
-    return c
-
-
 def test_the_new_keyword_leaves_the_existing_cases_bits():
     """``rot`` defaults to the former constant; SHAPES and FALLBACK keep their entries; the generator-only tensors of every
     existing case (the camera matrices: the first draws; idx, pick and sets: the last) carry the checksums taken before the
@@ -119,7 +112,7 @@ def test_the_new_keyword_leaves_the_existing_cases_bits():
     assert PC.FALLBACK == ((2, 13, 19, 72, 70, 33, True), 1)
     for key, (seed, crc) in want.items():
         case = PC.build(seed, *key)
-        assert _crc(case, ("K", "idx", "pick", "sets")) == crc, key
+        assert RC.crc(case, ("K", "idx", "pick", "sets")) == crc, key
         explicit = PC.build(seed, *key, rot=0.02)
         assert all(torch.equal(case[n], explicit[n]) for n in case if torch.is_tensor(case[n]))
 
@@ -160,25 +153,11 @@ def test_the_edge_cases_meet_their_conditions(name):
         assert B == int(name[1]) and tuple(c["P"].shape) == (2 * B, 6)
 
 
-def _drawn_layout(case, key):
-    B, H, W, k, num, hyp, noisy = key
-    assert case["pick"].dtype == torch.int64 and tuple(case["pick"].shape) == (num,) and int(case["pick"].min()) >= 0 and int(case["pick"].max()) < k
-    assert case["pick"].unique().numel() < num                                         # drawn with replacement: some pixel repeats
-    s = case["sets"]
-    assert s.dtype == torch.int32 and tuple(s.shape) == (B, hyp, 6) and int(s.min()) >= 0 and int(s.max()) < num
-    m = PC.solvers()
-    m.ransac_iters = hyp
-    assert torch.equal(s.long(), m._minimal_sets(B, num, 6, "cpu"))                     # the class's own draw
-    well = case["well"]
-    assert well.dtype == torch.bool and tuple(well.shape) == (2 * B, hyp)
-    assert not bool((well & ~torch.cat([PC.distinct_pixels(case)] * 2, 0)).any())      # a repeated pixel is never well-defined
-
-
 @pytest.mark.parametrize("key", PC.DRAWN_SHAPES)
 def test_the_drawn_cases_meet_their_conditions(key):
     case = PC.make_drawn_case(key)                                  # asserts the conditions itself
     B, H, W, k, num, hyp, noisy = key
-    _drawn_layout(case, key)
+    RC.drawn_layout(6, case, key)
     f, c, well = case["figures"], case["comp"], case["well"]
     assert f["api_equal"] and 4 * f["n_well"] >= hyp and f["n_ill"] >= 4 and f["margin"] >= PC.MARGIN and f["zmargin"] >= PC.MARGIN
     assert f["route_free"] and f["consensus"] >= 6 and f["cond"] >= PC.LM_COND
@@ -204,7 +183,7 @@ def test_the_drawn_shapes_are_the_ones_the_slots_need():
 def test_the_ill_winner_case_meets_its_conditions():
     case = PC.ill_winner_case()
     key, seed = PC.ILL_WINNER
-    _drawn_layout(case, key)
+    RC.drawn_layout(6, case, key)
     f, c, well = case["figures"], case["comp"], case["well"]
     won = ~torch.gather(well, 1, c["best"].view(-1, 1)).squeeze(1)           # this host's LAPACK decides: printed, not asserted
     assert f["consensus"] >= 6 and "ref" not in case
@@ -262,7 +241,7 @@ def test_the_model_scene_tells_the_plane_and_row_orderings_apart(B):
     """tests/test_hip_pnp_model.py's scene, float64 on the CPU with the analytic pose as the target: exchanging the two directions'
     targets (plane d*B + b read as (1-d)*B + b), or reading the pose's row d*B + b for (b, d), moves some sample's loss by more
     than 100 x the loss tolerance; and the samples' cameras differ, so ``K[0]`` for every sample is not ``K[b]``."""
-    from tests.test_hip_pnp import WEIGHTS_OF, _loss_reference
+    WEIGHTS_OF, _loss_reference = PC.WEIGHTS_OF, PC.loss_reference
     case = PC.build(0, B, 12, 20, 72, 64, 64, True)
     w = torch.tensor(WEIGHTS_OF[B])
     pose, target = PC.pose_vectors(case), case["P_true"]
