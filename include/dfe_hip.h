@@ -923,6 +923,36 @@ int dfe_pnp_ransac(const float* flow_bwd, const float* flow_fwd, const float* di
 int dfe_pnp_loss_fwd(const float* pose, const float* P32, float* loss, int B, float beta, void* stream);
 int dfe_pnp_loss_bwd(const float* pose, const float* P32, const float* gloss, float* gpose, int B, float beta, void* stream);
 
+/* ---- eight-point epipolar map  model_geometry.py:318-353 (compute_epipolar_map_8pF), call site :831-835 ------------------------
+ * The dense epipolar distance of a flow under a GIVEN fundamental matrix (dfe_fundamental_ransac's F32, not the pose's), its plain
+ * mean (compute_epipolar_loss, :413-418) and that mean's gradient to the flow.  Per pixel (x, y) of a plane with flow (u, v) and
+ * F row-major, in fp32, evaluated as written (no contraction):
+ *   l = F (x, y, 1)^T, each row as fma(F1, y, F0 * x) + F2;   s = ((x + u) * l0 + (y + v) * l1) + l2;
+ *   div = sqrtf(l0*l0 + l1*l1) + 1e-6f;   dist = |s| / div, sqrtf and the division correctly rounded (the map feeds masks).
+ * Plane p = d*B + b of the loss entries is direction d of sample b (d = 0: flow_bwd, 1: flow_fwd) and reads F32[p].  F is a
+ * constant.  A thread owns quads of four consecutive pixels; where H*W % 4 == 0 and every flow, map and gradient pointer of
+ * the call is on 16 bytes a quad moves as 16-byte accesses, otherwise as element accesses -- same assignment, same arithmetic, same
+ * bits.  Every loop is bounded by the shape; a non-finite F or flow makes that plane's (that sample's) results non-finite and
+ * nothing else.  No float atomics, no arrival ticket: bitwise reproducible.
+ * dfe_epipolar_map: reads flow [P,2,H,W] and F32 [P,9], writes every element of dist [P,H,W]; plane p reads flow[p] and F32[p].
+ *   One launch, no workspace.
+ * dfe_epipolar_loss_fwd: reads flow_bwd, flow_fwd [B,2,H,W] and F32 [2B,9]; loss[b] = mean_HW dist(plane b) + mean_HW dist(plane
+ *   B + b), every element of loss [B] written.  Sums in double: per block its threads' sums by a fixed tree -> ws, then one block
+ *   per sample adds the partials of its two planes in an order fixed by block and thread index, divides each by H*W, adds, rounds
+ *   once.  ws: dfe_epipolar_ws_bytes(B, H, W) bytes (one double per block and plane) on 8 bytes, no initialisation, every byte
+ *   written.  Two launches.
+ * dfe_epipolar_loss_bwd: reads the same inputs and gloss [B] (l, s and div are recomputed: nothing else is saved); writes every
+ *   element of gflow_bwd and gflow_fwd [B,2,H,W]: (gloss[b] / (float)(H*W)) * sgn(s) * (l0, l1) / div, sgn(0) = 0.  One launch, no
+ *   workspace.
+ * Refusals before the first launch: a null pointer -> DFE_ERR_NULL; B (P) < 1, B > 16384 (P > 32768), H or W < 1, H*W >= 2^28, ws
+ * not on 8 bytes -> DFE_ERR_DIMS.  flows, maps, gradients: 4-byte alignment suffices. */
+long dfe_epipolar_ws_bytes(int B, int H, int W);
+int dfe_epipolar_loss_fwd(const float* flow_bwd, const float* flow_fwd, const float* F32, float* loss, void* ws, int B, int H, int W,
+                          void* stream);
+int dfe_epipolar_loss_bwd(const float* flow_bwd, const float* flow_fwd, const float* F32, const float* gloss, float* gflow_bwd,
+                          float* gflow_fwd, int B, int H, int W, void* stream);
+int dfe_epipolar_map(const float* flow, const float* F32, float* dist, int P, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a geometric term costs in the training step (B = 4, 256x832, geom mode, one GPU).
 
-  python tools/geom_term_bench.py --term {triangle,eight_point,pnp} [--steps 60] [--warmup 10] [--rounds 3] [--graph] [--kernels]
+  python tools/geom_term_bench.py --term {triangle,eight_point,pnp,epipolar_8pf} [--steps 60] [--warmup 10] [--rounds 3] [--graph] [--kernels]
 
 Three configurations of the same model and batch, timed in turn, ``--rounds`` times, the order rotating so that a drift of the
 box hits them alike (as profiles/deterministic_mode.txt alternates its pairs):
@@ -15,12 +15,17 @@ box hits them alike (as profiles/deterministic_mode.txt alternates its pairs):
                        ``torch.inverse``;
           pnp          ``compute_pnp_loss`` per direction: ``svd`` over 2 x B x 256 systems of 12x12, a [B,256,num,3] float64
                        temporary per direction, 30 rounds of ``torch.linalg.solve`` (which raises on a singular system: the
-                       composition is then left out with a line).
+                       composition is then left out with a line);
+          epipolar_8pf ``compute_epipolar_map_8pF`` per direction on the step's matches (``compute_fundmental_mat`` as for
+                       eight_point, then the dense map in torch: a bmm over [b,3,H*W] and a dozen elementwise kernels with
+                       their autograd) and ``compute_epipolar_loss``; the fused RANSAC is not run beside it.
 ``--graph`` times off / fused as GraphedTrainStep replays, and tries the composition too: if its capture is refused the line
 says so.  One window = ``--steps`` steps after ``--warmup``, the device synchronised before and after; ms/step is the window's
 wall time over its steps.  The requirement is (fused - off) below (torch - off) by more than the run-to-run spread of off; the
 script prints the medians, the spreads and that verdict.  ``--kernels`` (a run of its own: the profiler slows the host) prints
-the device time of the term's launches in one fused step.
+the device time of the term's launches in one fused step; for epipolar_8pf also the achieved bytes/s of the two dense kernels
+against their shape-derived byte counts, and the part of the term that is dfe_fundamental_ransac (k_ep_*; paid once when
+``enable_eight_point`` is on as well).
 
 The tool sets no time limit of its own: run it under ``timeout``, each mode as a process of its own.  It replaces
 tools/triangle_bench.py, tools/eight_point_bench.py and tools/pnp_bench.py, which profiles/*_term.txt cite."""
@@ -72,9 +77,13 @@ class TriangleComposition(Model_geometry):
 class EightPointComposition(Model_geometry):
     """The term as the parent tree could have switched it on: compute_eight_point_loss per direction on the step's matches."""
 
-    def eight_point_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, K_inv, draw=None, return_F=False):
+    def step_fundamental(self, flow_bwd0, flow_fwd0, idx, pick):          # the fused RANSAC is not run beside the composition
+        return None, torch.zeros(2 * flow_bwd0.shape[0], 3, 3, dtype=torch.float64, device=flow_bwd0.device)
+
+    def eight_point_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, K_inv, draw=None, return_F=False, F=None):
         b = flow_bwd0.shape[0]
         loss = None
+        draw = draw if draw is not None else getattr(self, "triangle_draw", None)
         for d, match, _ in step_matches(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, draw):
             term = self.compute_eight_point_loss(match, pose[:, d].contiguous(), K, K_inv).reshape(1).expand(b)
             loss = term if loss is None else loss + term
@@ -94,11 +103,35 @@ class PnpComposition(Model_geometry):
         return (loss, torch.zeros(2 * b, 6, dtype=torch.float64, device=flow_bwd0.device)) if return_pose else loss
 
 
+class EpipolarComposition(Model_geometry):
+    """The term in plain torch: compute_epipolar_map_8pF per direction on the step's matches, then the plain mean."""
+
+    def step_fundamental(self, flow_bwd0, flow_fwd0, idx, pick):
+        return None, torch.zeros(2 * flow_bwd0.shape[0], 3, 3, dtype=torch.float64, device=flow_bwd0.device)
+
+    def epipolar_8pf_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, draw=None, F=None):
+        loss = None
+        draw = draw if draw is not None else getattr(self, "triangle_draw", None)
+        for d, match, _ in step_matches(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, draw):
+            dist = self.compute_epipolar_map_8pF(match, pose[:, d].contiguous(), (flow_bwd0, flow_fwd0)[d], K, None)
+            term = self.compute_epipolar_loss(dist, None)
+            loss = term if loss is None else loss + term
+        return loss
+
+
+def epipolar_bytes():
+    """Shape-derived traffic of the two dense kernels at (B, H, W): the forward pass reads two flow planes per plane and writes one
+    double per block; the backward pass reads them again and writes two gradient planes per plane."""
+    planes = 2 * B * 2 * H * W * 4
+    return {"k_epi_loss_part": planes, "k_epi_bwd": 2 * planes}
+
+
 # term -> (the switch and what goes with it, the torch composition, the fused kernels' names, whether --graph tries the composition)
 TERMS = {
     "triangle": (dict(enable_triangle=True, w_triangle=0.001), TriangleComposition, r"k_tri_\w+|k_topk_select", False),
     "eight_point": (dict(enable_eight_point=True), EightPointComposition, r"k_ep_\w+|k_topk_select", True),
     "pnp": (dict(enable_pnp=True), PnpComposition, r"k_pnp_\w+|k_topk_select", True),
+    "epipolar_8pf": (dict(enable_epipolar_8pf=True), EpipolarComposition, r"k_epi_\w+|k_ep_\w+|k_topk_select", True),
 }
 
 
@@ -173,8 +206,17 @@ def main():
     print("# %s, B = %d, %dx%d, geom, %s, %d steps per window after %d warm-up steps, %d rounds"
           % (torch.cuda.get_device_name(0), B, H, W, "graph replay" if args.graph else "eager", args.steps, args.warmup, args.rounds))
     if args.kernels:
-        for name, us in sorted(kernel_times(fns["fused"], pattern).items()):
+        times = kernel_times(fns["fused"], pattern)
+        for name, us in sorted(times.items()):
             print("kernel %-22s launches %d  device time %8.1f us" % (name, len(us), sum(us)))
+        if args.term == "epipolar_8pf":
+            for name, nbytes in epipolar_bytes().items():
+                us = sum(times[name])
+                print("dense  %-22s %.2f MB by shape in %.1f us = %.2f TB/s" % (name, nbytes / 1e6, us, nbytes / us / 1e6))
+            ransac = sum(sum(v) for k, v in times.items() if k.startswith("k_ep_"))
+            dense = sum(sum(v) for k, v in times.items() if k.startswith("k_epi_"))
+            print("term   dfe_fundamental_ransac (k_ep_*) %.1f us; the map's kernels (k_epi_*) %.1f us; selection (k_topk_select) "
+                  "%.1f us" % (ransac, dense, sum(times.get("k_topk_select", []))))
         return
     res = {k: [] for k in kinds}
     for r in range(args.rounds):

@@ -26,7 +26,9 @@
 three lines train through fused kernels behind a switch instead: ``loss_triangle`` (cfg ``enable_triangle``, triangulate.py),
 ``loss_eight_point`` (cfg ``enable_eight_point``, eight_point.py; FM_RANSAC only) and ``loss_pnp`` (cfg ``enable_pnp``, pnp.py;
 the robust branch of ``pnp``), the last two with the minimal sets of ``_minimal_sets`` held on the device by
-``minimal_sets_device``.  The compositions here are their cross-checks."""
+``minimal_sets_device``.  The fourth commented alternative, the epipolar loss by the eight-point method (:831-835), trains behind
+cfg ``enable_epipolar_8pf`` (epipolar.py) under the eight-point term's robust F; ``compute_epipolar_map_8pF`` here is its torch
+statement.  The compositions here are the cross-checks."""
 import torch
 import torch.nn.functional as F
 
@@ -272,6 +274,23 @@ class GeometrySolvers:
         E = compute_essential_matrix(pose_vec)
         F_pred = torch.inverse(intrinsics.permute([0, 2, 1])).bmm(E.bmm(intrinsics_inverse))
         return F.smooth_l1_loss(F_pred, target)
+
+    def compute_epipolar_map_8pF(self, matches, pose, flow, intrinsics, intrinsics_inverse):
+        """The dense epipolar distance map [b,1,h,w] of ``flow`` under the robust fundamental matrix of ``matches`` [b,4,n]
+        (model_geometry.py:318-353) -- ``compute_epipolar_map`` with ``compute_fundmental_mat``'s F in place of the pose's
+        K^-T [t]x R K^-1; ``pose`` and the intrinsics are passed on as the reference passes them and are not used.  Plain torch on
+        any device and float type: the cross-check of epipolar.py's kernels and the composition the bench compares against."""
+        b, _, h, w = flow.size()
+        grid = self.meshgrid(b, h, w).to(device=flow.device, dtype=flow.dtype)
+        ones = torch.ones(b, 1, h * w, device=flow.device, dtype=flow.dtype)
+        p1 = torch.cat([grid.view(b, 2, -1), ones], 1)                               # [b,3,n]
+        p2 = torch.cat([(grid + flow).view(b, 2, -1), ones], 1).transpose(1, 2)      # [b,n,3]
+        Fm = self.compute_fundmental_mat(matches, pose, intrinsics, intrinsics_inverse).to(flow.dtype)
+        line = Fm.view(-1, 3, 3).bmm(p1)                                             # [b,3,n]
+        dist = torch.abs((line.permute(0, 2, 1) * p2).sum(-1, keepdim=True))         # [b,n,1]
+        la, lb = line[:, 0, :].unsqueeze(-1), line[:, 1, :].unsqueeze(-1)
+        div = torch.sqrt(la * la + lb * lb) + 1e-6
+        return (dist / div).view(b, h, w, 1).permute(0, 3, 1, 2)
 
     # ------------------------------------------------------------------ perspective-n-point (model_geometry.py:473-530)
     @staticmethod

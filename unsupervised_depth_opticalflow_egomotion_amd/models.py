@@ -172,9 +172,13 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         self.enable_pnp = bool(getattr(cfg, "enable_pnp", False))
         self.ransac_iters = int(getattr(cfg, "geometric_ransac_iters", GeometrySolvers.ransac_iters))
         self.ransac_seed = int(getattr(cfg, "geometric_ransac_seed", GeometrySolvers.ransac_seed))
-        if self.enable_eight_point and self.dataset == "nyuv2":
-            raise DfeError("enable_eight_point: dataset 'nyuv2' asks for cv2.FM_LMEDS, which the fused term does not build "
-                           "(FM_RANSAC only)")
+        # loss_epipolar by the eight-point method, which the reference keeps commented (model_geometry.py:831-835); off = the
+        # fused stack's loss_epipolar under the pose's F
+        self.enable_epipolar_8pf = bool(getattr(cfg, "enable_epipolar_8pf", False))
+        for switch in ("enable_eight_point", "enable_epipolar_8pf"):
+            if getattr(self, switch) and self.dataset == "nyuv2":
+                raise DfeError("%s: dataset 'nyuv2' asks for cv2.FM_LMEDS, which the fused term does not build "
+                               "(FM_RANSAC only)" % switch)
 
     # ---- inference API (model_geometry.py:282-302)
     def infer_depth(self, img):
@@ -284,7 +288,16 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         return triangulate.triangulate_loss(flow_bwd0, flow_fwd0, disp_t0, disp_l0, disp_r0, T34, K, K_inv, idx, pick,
                                             ops.get_align_corners())
 
-    def eight_point_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, K_inv, draw=None, return_F=False):
+    def step_fundamental(self, flow_bwd0, flow_fwd0, idx, pick):
+        """The step's robust fundamental matrices -> (F32, F64) [2B,3,3] (plane d*B + b): FM_RANSAC at 0.1 px over the matches
+        ``idx[p][pick[j]]`` with ``ransac_iters`` minimal sets held on the device.  One call per step, shared by
+        ``eight_point_term`` and ``epipolar_8pf_term`` when both are on."""
+        from . import eight_point
+        sets = self.minimal_sets_device(flow_bwd0.shape[0], int(pick.shape[0]), flow_bwd0.device)
+        F32, F64, _ = eight_point.fundamental_ransac(flow_bwd0, flow_fwd0, idx, pick, sets, 0.1)
+        return F32, F64
+
+    def eight_point_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, K_inv, draw=None, return_F=False, F=None):
         """``loss_eight_point`` of the commented call site (model_geometry.py:949-950) -> (B,), enabled by
         ``cfg.enable_eight_point``: ``compute_eight_point_loss`` of both directions on the matches of ``geometric_draw``
         (``draw`` = (idx, pick) of this step when the triangulation term has drawn already), as fused launches (eight_point.py):
@@ -294,15 +307,36 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         reproducible.  The mean over the batch is the reference's scalar (mean-reduced smooth-L1 per direction, summed).
 
         Deviations: eight_point.py's docstring (line 565's unnormalised ``F_pred`` kept as written; the triangulation term's draw
-        deviations; cv2's draw cannot be pinned; no LMedS); geom mode only.  ``return_F``: also the step's F [2B,3,3] float64."""
+        deviations; cv2's draw cannot be pinned; no LMedS); geom mode only.  ``return_F``: also the step's F [2B,3,3] float64.
+        ``F`` = (F32, F64) of ``step_fundamental`` when the step has them already (no draw, no RANSAC here then)."""
         from . import eight_point
         B = flow_bwd0.shape[0]
-        idx, pick = draw if draw is not None else self.geometric_draw(disp_t0, pose, flow_bwd0, flow_fwd0, K)
-        sets = self.minimal_sets_device(B, int(pick.shape[0]), flow_bwd0.device)
-        F32, F64, _ = eight_point.fundamental_ransac(flow_bwd0, flow_fwd0, idx, pick, sets, 0.1)
+        if F is None:
+            idx, pick = draw if draw is not None else self.geometric_draw(disp_t0, pose, flow_bwd0, flow_fwd0, K)
+            F = self.step_fundamental(flow_bwd0, flow_fwd0, idx, pick)
+        F32, F64 = F
         E = ops.PoseMatsFn.apply(pose.reshape(2 * B, 6))[1]
         loss = eight_point.EightPointLossFn.apply(E, K, K_inv, F32)
         return (loss, F64) if return_F else loss
+
+    def epipolar_8pf_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, draw=None, F=None):
+        """``loss_epipolar`` by the eight-point method (the commented lines model_geometry.py:831-835) -> (B,), enabled by
+        ``cfg.enable_epipolar_8pf``: ``compute_epipolar_map_8pF`` of both directions -- the dense epipolar distance of the scale-0
+        flow under the robust fundamental matrix of the matches of ``geometric_draw`` (``draw`` = (idx, pick) of this step when
+        another geometric term has drawn already; ``F`` = (F32, F64) of ``step_fundamental`` when the eight-point term has
+        estimated it already) instead of under the pose's K^-T [t]x R K^-1 -- and ``compute_epipolar_loss``'s plain mean, summed
+        over the directions, as fused launches (epipolar.py: two forward, one backward).  F is detached as in the reference,
+        which builds it from numpy: the gradient reaches the two scale-0 flows alone and the pose net gets nothing from the
+        term.  No host read, capturable, bitwise reproducible.  The mean over the batch is the reference's scalar.
+
+        Deviations: the eight-point term's draw deviations (the pixel-ordered top-k set; no "some scores are zero" branch; cv2's
+        RANSAC draw cannot be pinned, the reference of the tests is ``compute_epipolar_map_8pF`` over ``compute_fundmental_mat``
+        on the same sets); FM_RANSAC only; geom mode only."""
+        from . import epipolar
+        if F is None:
+            idx, pick = draw if draw is not None else self.geometric_draw(disp_t0, pose, flow_bwd0, flow_fwd0, K)
+            F = self.step_fundamental(flow_bwd0, flow_fwd0, idx, pick)
+        return epipolar.EpipolarLossFn.apply(flow_bwd0, flow_fwd0, F[0])
 
     def pnp_term(self, disp_t0, pose, flow_bwd0, flow_fwd0, K, K_inv, draw=None, return_pose=False):
         """``loss_pnp`` of the commented call site (model_geometry.py:944-945) -> (B,), enabled by ``cfg.enable_pnp``:
@@ -381,22 +415,32 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         loss_pack = LossRows({k: (active[k] if k in active else _zeros2(dev)) for k in LOSS_ORDER_GEOM})
         loss_pack.rows = active.rows
         tri, eight = getattr(self, "enable_triangle", False), getattr(self, "enable_eight_point", False)
-        pnp_on = getattr(self, "enable_pnp", False)
-        if tri or eight or pnp_on:        # one selection and one draw per step, whichever terms are on
+        pnp_on, epi8 = getattr(self, "enable_pnp", False), getattr(self, "enable_epipolar_8pf", False)
+        F_step = None
+        if tri or eight or pnp_on or epi8:        # one selection and one draw per step, whichever terms are on
             Kc, Kic = K.contiguous(), K_inv.contiguous()
             idx, pick = self.geometric_draw(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc)
             self.triangle_draw = (idx, pick)      # the set and the draw of this step (triangle_term_torch takes them)
+            if eight or epi8:                     # one robust F per step, whichever of the two terms are on
+                F_step = self.step_fundamental(flows_bwd[0], flows_fwd[0], idx, pick)
+                self.eight_point_F = F_step[1].detach()   # the step's fundamental matrices [2B,3,3] (plane d*B + b)
             if tri:
                 loss_pack["loss_triangle"] = self._triangle_from_draw(disp_l[0], disp_t[0], disp_r[0], pose, flows_bwd[0],
                                                                       flows_fwd[0], Kc, Kic, idx, pick)
             if eight:
-                loss_pack["loss_eight_point"], F64 = self.eight_point_term(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc, Kic,
-                                                                           draw=(idx, pick), return_F=True)
-                self.eight_point_F = F64.detach()     # the step's fundamental matrices [2B,3,3] (plane d*B + b)
+                loss_pack["loss_eight_point"] = self.eight_point_term(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc, Kic,
+                                                                      F=F_step)
             if pnp_on:
                 loss_pack["loss_pnp"], P64 = self.pnp_term(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc, Kic, draw=(idx, pick),
                                                            return_pose=True)
                 self.pnp_pose = P64.detach()          # the step's poses [2B,6] = (T, axis-angle) (plane d*B + b)
+            if epi8:
+                # the term replaces the fused stack's row: total_loss sums the stack's terms from ``rows`` and skips their dict
+                # entries, so the map of a switched-on step leaves loss_epipolar out -- the stack's own row (under the pose's F)
+                # then gets no gradient and the pose net nothing from this term, as in the reference
+                loss_pack["loss_epipolar"] = self.epipolar_8pf_term(disp_t[0], pose, flows_bwd[0], flows_fwd[0], Kc, F=F_step)
+                losses, fused = active.rows
+                loss_pack.rows = (losses, {k: i for k, i in fused.items() if k != "loss_epipolar"})
 
         def u8(*names):
             """sample 0, scale 0 of the product of the named masks, decoded from the 1-byte mask pack only when the
@@ -411,7 +455,12 @@ class Model_geometry(LossTerms, GeometrySolvers, nn.Module):
         def epi_masks(which):
             def run():
                 with torch.no_grad():
-                    dist = self.compute_epipolar_map(pose[:, 1].detach(), flows_fwd[0].detach(), K, K_inv)
+                    if epi8:      # :834-835: the masks of the eight-point map, sample 0's forward plane under the step's F
+                        from . import epipolar
+                        B = flows_fwd[0].shape[0]
+                        dist = epipolar.epipolar_map(flows_fwd[0][:1], F_step[0][B:B + 1])
+                    else:
+                        dist = self.compute_epipolar_map(pose[:, 1].detach(), flows_fwd[0].detach(), K, K_inv)
                     rigid, inlier, _ = self.get_rigid_mask(dist)
                 return 255 * (rigid if which == 0 else inlier)[0].cpu().numpy().astype(np.uint8)
             return run

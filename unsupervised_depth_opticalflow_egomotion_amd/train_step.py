@@ -11,7 +11,7 @@ DEFAULT_CFG = dict(
     w_flow_pixel=0.15, w_flow_ssim=0.85, w_flow_smooth=10.0, w_flow_consis=0.01, w_depth_pixel=1.0, w_depth_ssim=0.85,
     w_depth_smooth=0.5, w_depth_consis=0.1, w_depth_flow_consis=1.0, w_epipolar=0.1, w_triangle=0.001, w_pnp=0.1,
     w_8point=0.1, img_hw=(256, 832), lr=1e-4, mode="geom", enable_depth_ssim=False, enable_depth_consis=False,
-    enable_triangle=False, enable_eight_point=False, enable_pnp=False)
+    enable_triangle=False, enable_eight_point=False, enable_pnp=False, enable_epipolar_8pf=False)
 
 LOSS_WEIGHT_ATTR = {
     "loss_flow_pixel": "w_flow_pixel", "loss_flow_ssim": "w_flow_ssim", "loss_flow_smooth": "w_flow_smooth",
